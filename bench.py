@@ -11,17 +11,22 @@ One "step" = one pass of the hot path over one batch of synthetic input that is 
   this mode meets every fp32 parity bar of tests/test_parity_gpu.py. The timed region carries NO instrumentation; the
   per-kernel numbers (`roofline`, `kernels`) come from a second, hipEvent-instrumented pass over the same steps.
 
-Beside `value` the line reports (N = 1 only): the PCIe-inclusive rate (waveforms start in pinned host memory), the
-other arithmetic modes, full-configuration parity evidence against the CPU oracle, the CPU baseline in two thread
-settings, and the secondary workloads of BASELINE.json (configs[2] SenseVoiceSmall 128 x 10 s, configs[4] streaming).
+A plain run does only what the headline figure needs: set up, calibrate the output layer, warm up, time K steps, write the
+last step's outputs if --dump-outputs DIR is given (DIR/<name>.npy, float64: token counts and token ids per clip, what
+Paraformer.collect returns to a caller), print the line. Everything else runs with --full only: the instrumented pass
+behind `roofline` / `kernels`, the clock / power telemetry of the timed region, and (N = 1 only) beside `value` the
+PCIe-inclusive rate (waveforms start in pinned host memory), the other arithmetic modes, full-configuration parity
+evidence against the CPU oracle, the CPU baseline in two thread settings, and the secondary workloads of BASELINE.json
+(configs[2] SenseVoiceSmall 128 x 10 s, configs[4] streaming).
 
 Multi-GPU (utterance-level data parallelism, weak scaling): one process per GPU, rank 0 builds the weights and
 broadcasts ONE packed arena over RCCL, every rank decodes its own 64 clips, hypotheses are gathered on rank 0
 inside the timed region. No collective touches the data path.
 
-Contract: python bench.py --gpus N --steps K --warmup W   (N>1: either under torch.distributed.run with N ranks, or bare --
-the script then re-executes itself as N ranks, funasr_amd.dp.ensure_ranks; a world size other than N is an error)
-prints ONE JSON line on rank 0 (see README / DESIGN.md for the fields, incl. `roofline` and `cpu_baseline`).
+Contract: python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]   (N>1: either under
+torch.distributed.run with N ranks, or bare -- the script then re-executes itself as N ranks, funasr_amd.dp.ensure_ranks; a
+world size other than N is an error) prints ONE JSON line on rank 0 (see README / DESIGN.md for the fields, incl. `roofline`
+and `cpu_baseline`, which only --full fills).
 """
 from __future__ import annotations
 
@@ -88,6 +93,11 @@ def parse():
                     "falls back to the arena if any rank fails). The arena is the default because no multi-GPU box has ever run either "
                     "route (DESIGN 6) and a first contact that hangs inside a never-exercised communicator would lose the whole line")
     ap.add_argument("--cpu-threads", type=int, default=0, help="cap on host threads for the CPU baseline (0 = all usable)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline figure: the instrumented pass (`roofline`, "
+                    "`kernels`), telemetry, and at N = 1 the A/B loops, the secondary workloads, the other modes and the CPU baseline "
+                    "(the --no-* switches above select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step computed "
+                    "(rank 0: token counts and token ids per clip) as DIR/<name>.npy in float64")
     return ap.parse_args()
 
 
@@ -341,6 +351,56 @@ def read_prof_tags(lib, steps, peak_tflops):
     return rows
 
 
+def kernel_figures(lib, steps, precision):
+    """`roofline` and `kernels` of the line from the counters of the instrumented pass (pf_prof_*) over `steps` steps."""
+    prof = read_prof(lib, steps)
+    if precision in PRODUCTS:
+        # dominant kernel: the split-operand GEMM. `achieved` = algorithmic (fp32-equivalent) 2MNK flops per second; the
+        # kernel executes PRODUCTS 16-bit MFMA flops per algorithmic flop, so its ceiling is the dense 16-bit peak / PRODUCTS
+        gemm = prof["gemm_split"]
+        # f16x2: the tile kernel and its full-row form (gemm_f16x2_row_kernel: linear_out / w_2 with the fused LayerNorm)
+        kname = "gemm_f16x2_" if precision == "f16x2" else "gemm_split3_kernel"
+        peak = PEAK_16BIT_MFMA_TFLOPS / PRODUCTS[precision]
+    else:
+        gemm, kname = prof["gemm_f32_mfma"], "gemm_f32_mfma_kernel"
+        peak = PEAK_16BIT_MFMA_TFLOPS if precision == "bf16" else PEAK_F32_MFMA_TFLOPS
+    roofline = assemble_roofline(gemm, kname, peak, sum(v["ms_per_step"] for v in prof.values()), pmc_traffic(kname), PRODUCTS.get(precision))
+    roofline["measured_in"] = ("instrumented pass on ONE stream (hipEvent pairs on the launch stream); share_of_step = this family's share of the "
+                               "instrumented kernel time of a step")
+    kernels = {k: dict(ms_per_step=round(v["ms_per_step"], 3), launches=v["launches_per_step"]) for k, v in prof.items()}
+    for nm in ("gemm_f32_mfma", "gemm_split", "attention"):
+        if prof[nm]["ms_per_step"] > 0:
+            kernels[nm]["tflops"] = round(prof[nm]["work_per_step"] / (prof[nm]["ms_per_step"] * 1e-3) / 1e12, 2)
+    for nm in ("fsmn", "layernorm", "fbank"):
+        if prof[nm]["ms_per_step"] > 0:
+            kernels[nm]["GBps"] = round(prof[nm]["work_per_step"] / (prof[nm]["ms_per_step"] * 1e-3) / 1e9, 1)
+    inst = sum(v["ms_per_step"] for v in prof.values())
+    kernels["by_call_site"] = read_prof_tags(lib, steps, peak)[:8]
+    kernels["instrumented_sum_ms"] = round(inst, 2)
+    kernels["non_gemm_non_attention_ms"] = round(inst - prof["gemm_f32_mfma"]["ms_per_step"] - prof["gemm_split"]["ms_per_step"]
+                                                 - prof["attention"]["ms_per_step"], 2)
+    return roofline, kernels
+
+
+def dump_outputs(res, out_dir) -> list:
+    """--dump-outputs: the result of the timed path's last step as a caller receives it (Paraformer.collect) -- the token count
+    per clip and the token ids per clip, raw (as the arg-max produced them) and without <s> / </s> / <blank>; rows of ids are
+    right-padded with -1. float64 holds every id exactly. Returns the names written."""
+    import numpy as np
+
+    def padded(rows):
+        a = np.full((len(rows), max((len(r) for r in rows), default=0)), -1.0, dtype=np.float64)
+        for i, r in enumerate(rows):
+            a[i, :len(r)] = r
+        return a
+
+    arrays = {"token_num": np.asarray(res["token_num"], dtype=np.float64), "raw_ids": padded(res["raw_ids"]), "ids": padded(res["ids"])}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return sorted(arrays)
+
+
 def main():
     args = parse()
     from funasr_amd.dp import ensure_ranks
@@ -467,7 +527,7 @@ def main():
     confident, conf_stats = None, None
     if not args.random_output_layer:
         feats0, flens0 = frontend(wav, lens)
-        if rank == 0 and not args.no_cpu_baseline:
+        if args.full and rank == 0 and not args.no_cpu_baseline:
             gpu_random = model.recognize_features(feats0, flens0)["raw_ids"]
         confident, conf_stats = synth.make_paraformer_confident(model, feats0, flens0)
         del feats0
@@ -479,7 +539,7 @@ def main():
 
     # ------------------------------------------------------------------------------- the timed region (no instrumentation)
     sampler = None
-    if rank == 0:                                      # host thread polling librocm_smi64 every 20 ms: clock + socket power
+    if args.full and rank == 0:                        # host thread polling librocm_smi64 every 20 ms: clock + socket power
         try:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             from gpu_telemetry import Sampler
@@ -509,49 +569,31 @@ def main():
     audio_s = world * B * args.seconds * args.steps
     value = audio_s / dt
 
-    # ---- per-kernel numbers: the same steps again with a hipEvent pair around every launch of the dominant kernels, on the
-    #      launch stream (the events cost ~5 ms per step, which is why this pass is not the timed one). Every rank runs it
+    if args.dump_outputs and rank == 0:
+        names = dump_outputs(res, args.dump_outputs)
+        trace(f"outputs of the last timed step written: {', '.join(names)} under {args.dump_outputs}")
+
+    # ---- per-kernel numbers (--full): the same steps again with a hipEvent pair around every launch of the dominant kernels, on
+    #      the launch stream (the events cost ~5 ms per step, which is why this pass is not the timed one). Every rank runs it
     #      (the steps contain the hypothesis gather); only rank 0's numbers are reported
     #      ONE stream here even when the timed loop runs the decoder on a second stream: a kernel's duration beside another stream's
     #      kernels is not the kernel's (w_1 reads 261 us instead of 211 with the decoder next to it) -- the roofline fraction is quoted
     #      for the kernel running alone, as in every earlier round, and tools/profile.sh runs rocprofv3 on the same one-stream loop
-    torch.cuda.synchronize()
-    lib.pf_prof_reset()
-    lib.pf_prof_enable(1)
-    run_steps(args.steps, stream=None)
-    sync()
-    lib.pf_prof_enable(0)
+    if args.full:
+        torch.cuda.synchronize()
+        lib.pf_prof_reset()
+        lib.pf_prof_enable(1)
+        run_steps(args.steps, stream=None)
+        sync()
+        lib.pf_prof_enable(0)
     if rank != 0:
         if world > 1:
             dist.destroy_process_group()
         return
-    prof = read_prof(lib, args.steps)
-    if args.precision in PRODUCTS:
-        # dominant kernel: the split-operand GEMM. `achieved` = algorithmic (fp32-equivalent) 2MNK flops per second; the
-        # kernel executes PRODUCTS 16-bit MFMA flops per algorithmic flop, so its ceiling is the dense 16-bit peak / PRODUCTS
-        gemm = prof["gemm_split"]
-        # f16x2: the tile kernel and its full-row form (gemm_f16x2_row_kernel: linear_out / w_2 with the fused LayerNorm)
-        kname = "gemm_f16x2_" if args.precision == "f16x2" else "gemm_split3_kernel"
-        peak = PEAK_16BIT_MFMA_TFLOPS / PRODUCTS[args.precision]
-    else:
-        gemm, kname = prof["gemm_f32_mfma"], "gemm_f32_mfma_kernel"
-        peak = PEAK_16BIT_MFMA_TFLOPS if args.precision == "bf16" else PEAK_F32_MFMA_TFLOPS
-    roofline = assemble_roofline(gemm, kname, peak, sum(v["ms_per_step"] for v in prof.values()), pmc_traffic(kname), PRODUCTS.get(args.precision))
-    roofline["measured_in"] = ("instrumented pass on ONE stream (hipEvent pairs on the launch stream); share_of_step = this family's share of the "
-                               "instrumented kernel time of a step")
-    kernels = {k: dict(ms_per_step=round(v["ms_per_step"], 3), launches=v["launches_per_step"]) for k, v in prof.items()}
-    for nm in ("gemm_f32_mfma", "gemm_split", "attention"):
-        if prof[nm]["ms_per_step"] > 0:
-            kernels[nm]["tflops"] = round(prof[nm]["work_per_step"] / (prof[nm]["ms_per_step"] * 1e-3) / 1e12, 2)
-    for nm in ("fsmn", "layernorm", "fbank"):
-        if prof[nm]["ms_per_step"] > 0:
-            kernels[nm]["GBps"] = round(prof[nm]["work_per_step"] / (prof[nm]["ms_per_step"] * 1e-3) / 1e9, 1)
-    inst = sum(v["ms_per_step"] for v in prof.values())
-    kernels["by_call_site"] = read_prof_tags(lib, args.steps, peak)[:8]
-    kernels["instrumented_sum_ms"] = round(inst, 2)
-    kernels["non_gemm_non_attention_ms"] = round(inst - prof["gemm_f32_mfma"]["ms_per_step"] - prof["gemm_split"]["ms_per_step"]
-                                                 - prof["attention"]["ms_per_step"], 2)
-    trace("instrumented pass done")
+    roofline, kernels = None, None
+    if args.full:
+        roofline, kernels = kernel_figures(lib, args.steps, args.precision)
+        trace("instrumented pass done")
 
     line = assemble_line(value=value, dt=dt, steps=args.steps, warmup=args.warmup, world=world, dtype=MODE_DTYPE[args.precision], B=B,
                          seconds=args.seconds, token_num=res["token_num"], arena_bytes=arena_bytes, n_pad=N_PAD, per_rank_ms=per_rank_ms,
@@ -559,12 +601,13 @@ def main():
                          kernels=kernels, telemetry=telemetry,
                          output_layer=("random-init" if confident is None else
                                        {"kind": "confident (synth.confident_output_layer, calibrated on the batch)", **conf_stats}))
-    if world > 1:
+    if world > 1 or not args.full:
         print(json.dumps(line), flush=True)
-        dist.destroy_process_group()
+        if world > 1:
+            dist.destroy_process_group()
         return
 
-    # ------------------------------------------------------------------- everything below: N = 1 only, outside the timed region
+    # ------------------------------------------------------------------- everything below: --full, N = 1 only, outside the timed region
     line["hbm_copy_probe"] = hbm_copy_probe(device)
     if interleave:
         # A/B in the same process: round 5's loop (the host's wait for the CIF count between a batch's encoder and its decoder)

@@ -8,6 +8,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -59,6 +61,53 @@ def test_line_assembly_schema_on_synthetic_inputs():
     assert abs(live["frac_of_power_limited_peak"] - roof["achieved"] / 550.0) < 1e-3 and live["frac_of_power_limited_peak"] > roof["frac"]
     rec = b.apply_power_limited_peak(dict(roof), {"TFLOPs": None, "recorded_TFLOPs": 1647.0, "source": "NOT measured in this run; recorded: ..."}, 3)
     assert rec["frac_of_power_limited_peak"] is None and rec["power_limited_peak"] is None and rec["power_limited_peak_recorded"] == 549.0
+
+
+def test_plain_run_options_and_the_output_dump(tmp_path, monkeypatch):
+    """--full is off by default (a plain run sets up, warms up, times the steps and prints the line) and --dump-outputs writes the last
+    step's result as a caller receives it (Paraformer.collect: token counts, raw and filtered ids) in float64, ids right-padded with -1"""
+    import numpy as np
+    b = _import_bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = b.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 3 and a.warmup == 1
+    out = str(tmp_path / "out")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", out])
+    a = b.parse()
+    assert a.full is True and a.dump_outputs == out
+    res = {"token_num": [3, 0, 2], "raw_ids": [[1, 7, 2], [], [8403, 5]], "ids": [[7], [], [8403, 5]]}
+    names = b.dump_outputs(res, out)
+    assert names == ["ids", "raw_ids", "token_num"] and sorted(os.listdir(out)) == [n + ".npy" for n in names]
+    got = {n: np.load(os.path.join(out, n + ".npy")) for n in names}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert got["token_num"].tolist() == [3.0, 0.0, 2.0]
+    assert got["raw_ids"].tolist() == [[1, 7, 2], [-1, -1, -1], [8403, 5, -1]]
+    assert got["ids"].tolist() == [[7, -1], [-1, -1], [8403, 5]]
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(900)
+def test_plain_run_times_the_steps_asked_for_and_dumps_the_last_one(cuda, tmp_path):
+    """a plain run on a small batch: ONE line with the headline fields, `steps` / `warmup` as asked, `value` = clips x seconds / ms_per_step,
+    none of the --full figures, and the last timed step's token counts and ids under --dump-outputs"""
+    import numpy as np
+    out = str(tmp_path / "out")
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4", "--seconds", "5",
+                        "--dump-outputs", out], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["unit"] == "audio-s/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - 4 * 5.0 / (d["ms_per_step"] * 1e-3)) / d["value"] < 2e-3
+    assert d["roofline"] is None and d["kernels"] is None and "cpu_baseline" not in d and "pcie_inclusive" not in d
+    tok = np.load(os.path.join(out, "token_num.npy"))
+    raw = np.load(os.path.join(out, "raw_ids.npy"))
+    assert tok.dtype == raw.dtype == np.float64 and tok.shape == (4,) and raw.shape[0] == 4
+    assert abs(tok.mean() - d["config"]["tokens_per_clip"]) < 0.051 and tok.min() >= 1      # the line's own count is of the same step
+    assert [int((row >= 0).sum()) for row in raw] == [int(t) for t in tok]
 
 
 def test_committed_line_sanity_of_the_recorded_artefact():

@@ -65,7 +65,7 @@ def test_sweep_two_ranks_sharing_one_gpu_without_serialising(cuda, tmp_path):
 
 @pytest.mark.timeout(900)
 def test_bench_two_ranks_prints_one_whole_job_line(cuda):
-    out = _run(_torchrun(2, ["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--dist-backend", "gloo"]), 600)
+    out = _run(_torchrun(2, ["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--dist-backend", "gloo", "--full"]), 600)
     lines = [l for l in out.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out[-2000:]                       # rank 0 only
     d = json.loads(lines[0])

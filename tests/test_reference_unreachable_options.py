@@ -9,9 +9,10 @@ import torch
 
 from oracle import ref_import
 
-pytestmark = pytest.mark.skipif(not ref_import.available(), reason="reference checkout not present (GPU box)")
+needs_reference = pytest.mark.skipif(not ref_import.available(), reason="reference checkout not present (GPU box)")
 
 
+@needs_reference
 def test_reference_cnn_attn_upsampler_cannot_run_with_a_mask():
     ref_import.install()
     from funasr.models.bicif_paraformer.cif_predictor import CifPredictorV3
@@ -32,6 +33,7 @@ def test_reference_cnn_attn_upsampler_cannot_run_with_a_mask():
         assert ok.get_upsample_timestamp(hidden, mask, torch.tensor([5, 4]))[2].shape == (2, 60)
 
 
+@needs_reference
 def test_reference_mean_bias_encoder_has_no_inference_path():
     """read off the reference source (building the whole ContextualParaformer needs its full config): the `mean` branch of
     __init__ creates only `bias_embed`, and both hotword branches of cal_decoder_with_predictor call `self.bias_encoder`"""

@@ -5,9 +5,9 @@ cd "$(dirname "$0")/.." || exit 1
 O=gpurun_out/r06a
 mkdir -p $O
 export TMPDIR=/tmp
-( timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "rc=$?" >> $O/bench.err )
+( timeout 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "rc=$?" >> $O/bench.err )
 tail -n 5 $O/bench.err; cut -c1-400 $O/bench.json
-( timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-interleave --no-cpu-baseline --no-secondary --no-bf16 > $O/bench_sequential.json 2> $O/bench_sequential.err; echo "rc=$?" >> $O/bench_sequential.err )
+( timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-interleave --no-cpu-baseline --no-secondary --no-bf16 > $O/bench_sequential.json 2> $O/bench_sequential.err; echo "rc=$?" >> $O/bench_sequential.err )
 cut -c1-200 $O/bench_sequential.json
 ( timeout 600 python -m pytest tests/test_kernels_gpu.py tests/test_parity_gpu.py tests/test_abi.py -x -q -m gpu -k "conv1d or two_phase or one_call or abi or predictor or pipeline" > $O/new_tests.log 2>&1; echo "rc=$?" >> $O/new_tests.log )
 tail -n 5 $O/new_tests.log

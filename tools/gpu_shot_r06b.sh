@@ -11,7 +11,7 @@ tail -n 4 $O/ps_parity.jsonl; tail -n 3 $O/ps_parity.err
 cat $O/ps_time.jsonl; tail -n 2 $O/ps_time.err
 for opt in "" "--enc-option gemm_tile=10" "--enc-option gemm_tile=10 --enc-option w2_tile=10" "--enc-option w2_tile=10"; do
   tag=$(echo "$opt" | tr -c 'a-z0-9_=' '_')
-  ( timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-bf16 $opt > $O/bench_$tag.json 2> $O/bench_$tag.err; echo "rc=$?" >> $O/bench_$tag.err )
+  ( timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-bf16 $opt > $O/bench_$tag.json 2> $O/bench_$tag.err; echo "rc=$?" >> $O/bench_$tag.err )
   echo "== $opt"; python - <<PY
 import json
 try:

@@ -5,7 +5,7 @@ O=gpurun_out/r06i
 mkdir -p $O
 export TMPDIR=/tmp
 for mode in 0 1 2; do
-  ( PF_QKV_PS=$mode timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-bf16 > $O/bench_qkvps$mode.json 2> $O/bench_qkvps$mode.err; echo "rc=$?" >> $O/bench_qkvps$mode.err )
+  ( PF_QKV_PS=$mode timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-bf16 > $O/bench_qkvps$mode.json 2> $O/bench_qkvps$mode.err; echo "rc=$?" >> $O/bench_qkvps$mode.err )
   python - <<PY
 import json
 try:
@@ -20,7 +20,7 @@ for mode in 0 1 2; do
   echo "sensevoice PF_QKV_PS=$mode"; tail -n 3 $O/sv_qkvps$mode.json | cut -c1-600
 done
 for opt in "gemm_tile=10" "w2_tile=10"; do
-  ( timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-bf16 --enc-option $opt > $O/bench_$opt.json 2> $O/bench_$opt.err; echo "rc=$?" >> $O/bench_$opt.err )
+  ( timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-bf16 --enc-option $opt > $O/bench_$opt.json 2> $O/bench_$opt.err; echo "rc=$?" >> $O/bench_$opt.err )
   python - <<PY
 import json
 try:

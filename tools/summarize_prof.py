@@ -52,7 +52,7 @@ def pmc_table(root, sub, counter):
 
 def main():
     root, tag = sys.argv[1], sys.argv[2]
-    cmd = " ".join(sys.argv[3:]) or "python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --no-bf16"
+    cmd = " ".join(sys.argv[3:]) or "python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --no-bf16"
     print(f"# rocprofv3 summary `{tag}`  ({cmd})\n")
     rows = stats_table(root)
     print("## kernel time (rocprofv3 --kernel-trace --stats)\n")
@@ -121,7 +121,7 @@ def main():
     try:
         with open(out, "w") as f:
             json.dump(dict(tag=tag, note="FETCH_SIZE KiB x1024 x2 (gfx950 under-count of wide reads), WRITE_SIZE KiB x1024; "
-                                        "separate rocprofv3 --pmc passes of `bench.py --steps 3 --warmup 1 --no-cpu-baseline`",
+                                        "separate rocprofv3 --pmc passes of `bench.py --full --steps 3 --warmup 1 --no-cpu-baseline`",
                            kernels=traffic), f, indent=1)
     except OSError:
         pass
