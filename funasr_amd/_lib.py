@@ -77,6 +77,11 @@ class pf_vad_options(C.Structure):
                                            "fe_prior_thres")]
 
 
+class pf_campplus_config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("feat_dim", "embedding_size", "growth_rate", "bn_size", "init_channels", "m_channels")] + \
+               [("bn_eps", C.c_float)]
+
+
 class pf_stream_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_streams", "chunk_left", "chunk_cur", "chunk_right", "enc_look_back",
                                           "dec_look_back", "max_frames", "max_tokens", "use_graph")]
@@ -150,6 +155,13 @@ SIGNATURES = {
     "pf_vad_decision_set_thresholds": (None, [_vp, C.c_double, C.c_double]),
     "pf_vad_decision_state": (C.c_int, [_vp]),
     "pf_vad_decision_push": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32]),
+    "pf_campplus_create": (_vp, [C.POINTER(pf_campplus_config)]),
+    "pf_campplus_destroy": (None, [_vp]),
+    "pf_campplus_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),
+    "pf_campplus_missing": (C.c_int, [_vp]),
+    "pf_campplus_set_max_batch": (C.c_int, [_vp, _i32]),
+    "pf_campplus_forward": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
+    "pf_campplus_embed_chunks": (C.c_int, [_vp, _vp, _i64, C.POINTER(C.c_int64), _pi32, _i32, _i32, _vp, _vp]),
     "pf_ctc_create": (_vp, [_i32, _i32]),
     "pf_ctc_destroy": (None, [_vp]),
     "pf_ctc_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),

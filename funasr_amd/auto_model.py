@@ -18,7 +18,8 @@ segments; the segments are sorted by length, packed into batches under the refer
 `batch_size_threshold_s` policy, decoded by the HIP path, put back in order and merged (texts joined, per-token
 timestamps shifted by the segment start); with a `punc_model` (CT-Transformer directory or object) the joined text is
 punctuated once per recording (results that carry `words` keep their spelling, funasr_amd/punc_align.py) and
-`sentence_timestamp` cuts it into sentence records. The speaker branch raises. `vad_model` may also be a local FSMN-VAD
+`sentence_timestamp` cuts it into sentence records. With `spk_model` (a CAM++ directory or module) every sentence record
+carries a `spk` label (funasr_amd/speaker.py). `vad_model` may also be a local FSMN-VAD
 model directory: the network runs on the GPU (funasr_amd/fsmn_vad.py), its decision logic on the host
 (funasr_amd/vad_decision.py). `generate` hands a requested text-level hotword correction to the reference's own module (`_text_hotword_step`).
 
@@ -34,6 +35,8 @@ import os
 import random
 import string
 import time
+
+import numpy as np
 from typing import Any, Dict, List, Tuple
 
 import torch
@@ -217,8 +220,20 @@ def _text_hotword_step(cfg):
 
 class AutoModel:
     def __init__(self, **kwargs):
-        if kwargs.get("spk_model") is not None:
-            raise NotImplementedError("spk_model: the speaker pipeline is outside the HIP hot path")
+        spk_model = kwargs.pop("spk_model", None)
+        spk_kwargs = dict(kwargs.pop("spk_kwargs", None) or {})
+        self.cb_kwargs = dict(spk_kwargs.pop("cb_kwargs", None) or {})
+        self.spk_mode = kwargs.pop("spk_mode", "punc_segment")
+        if isinstance(spk_model, str):                                  # a local CAM++ model directory (:489-516)
+            if not os.path.isdir(spk_model):
+                raise NotImplementedError(f"spk_model={spk_model!r}: only a local CAM++ model directory or a module object is "
+                                          "accepted (hub names need a download)")
+            sk = dict(spk_kwargs, model=spk_model)
+            sk.setdefault("device", kwargs.get("device", "cuda"))
+            spk_model, spk_kwargs = self.build_model(**sk)
+        if self.spk_mode not in ("default", "vad_segment", "punc_segment"):
+            logging.error("spk_mode should be one of default, vad_segment and punc_segment.")
+        self.spk_model, self.spk_kwargs = spk_model, spk_kwargs
         punc_model = kwargs.pop("punc_model", None)
         self.punc_kwargs = dict(kwargs.pop("punc_kwargs", None) or {})
         if isinstance(punc_model, str):                                  # CT-Transformer model directory (:478-490)
@@ -346,6 +361,9 @@ class AutoModel:
                         result["raw_text"] = copy.copy(result["text"])
                     result["text"] = punc_res[0]["text"]
             return apply_postprocess_hotwords_to_results(results, cfg)      # text-level hotword correction (:742,:748)
+        if getattr(self, "spk_model", None) is not None and "output_timestamp" not in cfg:     # :871-873
+            cfg["output_timestamp"] = True
+            cfg["return_time_stamps"] = True
         return apply_postprocess_hotwords_to_results(self.inference_with_vad(input, input_len=input_len, **cfg), cfg)
 
     def inference(self, input, input_len=None, model=None, kwargs=None, key=None, progress_callback=None, batch_bounds=None, **cfg):
@@ -580,6 +598,63 @@ class AutoModel:
             flush()
         return done
 
+    def _speaker_sentences(self, speech, segments, restored, merged, kwargs, punc_res, punc_array, stamps, stamp_text,
+                           surface_sentences, return_raw_text) -> List[dict]:
+        """the speaker branch for one recording: 1.5-s chunks of every VAD segment (sv_chunk), cut from the recording already
+        in GPU memory and embedded in one library call, clustered on the host, turned into speaker turns and distributed over the
+        sentence list. The vad_segment fallback (no punctuation, no timestamps) is decided per call: unlike the reference,
+        self.spk_mode is not overwritten."""
+        from . import speaker
+        fs = 16000
+        starts, valid, chunks = [], [], []
+        for beg, end in segments:                                    # segment order = start order (:1023-1027, :1130)
+            s0 = int(beg * 16)
+            n = max(min(int(end * 16), len(speech)) - s0, 0)
+            for st, ed in speaker.sv_chunk_bounds(n, fs):
+                starts.append(s0 + st)
+                valid.append(ed - st)
+                chunks.append([st / fs + beg / 1000.0, ed / fs + beg / 1000.0])
+        if not chunks:
+            return []
+        size = int(speaker.CHUNK_S * fs)
+        if hasattr(self.spk_model, "embed_chunks") and speech.is_cuda:
+            emb = self.spk_model.embed_chunks(speech, starts, size, valid)
+        else:
+            pieces = []
+            for s, v in zip(starts, valid):
+                w = np.zeros(size, dtype=np.float32)
+                w[:v] = speech[s:s + v].detach().cpu().numpy()
+                pieces.append(w)
+            emb = self.spk_model.inference(pieces, device=self.spk_kwargs.get("device", "cuda"))[0][0]["spk_embedding"]
+        emb_np = emb.detach().cpu().numpy()
+        labels = speaker.ClusterBackend(**self.cb_kwargs)(emb_np, oracle_num=kwargs.get("preset_spk_num", None))
+        if kwargs.get("return_spk_center", False):
+            turns, centers = speaker.postprocess(chunks, None, labels, emb_np, return_spk_center=True)
+            merged["spk_embedding_center"] = centers
+        else:
+            turns = speaker.postprocess(chunks, None, labels, emb_np)
+        mode = self.spk_mode
+        if mode == "punc_segment" and (punc_res is None or "timestamp" not in merged or punc_array is None):
+            logging.warning("no punctuation or no timestamps: speaker diarization falls back to vad_segment for this call.")
+            mode = "vad_segment"
+        if mode == "punc_segment" and surface_sentences is not None:
+            sentences = surface_sentences
+        elif mode == "punc_segment":
+            from .timestamps import timestamp_sentence
+            sentences = timestamp_sentence(punc_array, stamps, stamp_text, return_raw_text=return_raw_text,
+                                           english=kwargs.get("en_post_proc", False))
+        else:
+            sentences = []
+            for rest, seg in zip(restored, segments):
+                if "timestamp" in rest:
+                    ts = rest["timestamp"]
+                elif "timestamps" in rest:
+                    ts = [[int(t["start_time"] * 1000), int(t["end_time"] * 1000)] for t in rest["timestamps"]]
+                else:
+                    ts = []
+                sentences.append({"start": seg[0], "end": seg[1], "sentence": rest.get("text", ""), "timestamp": ts})
+        return speaker.distribute_spk(sentences, turns)
+
     def inference_with_vad(self, input, input_len=None, **cfg):
         """VAD -> length-sorted dynamic batches -> ASR -> merge -> punctuation -> sentence records
         (funasr/auto/auto_model.py:852-1254 without the speaker branch). Returns one dict per recording: key, text,
@@ -614,11 +689,13 @@ class AutoModel:
             if n == 0:
                 out.append({"key": key, "text": "", "timestamp": []})
                 continue
+            speech = None
             if i in across:
                 order, decoded = list(range(n)), across[i]
             else:
-                speech = load_audio_list([data_list[i]], fs=fs, audio_fs=kwargs.get("fs", 16000))[0]
-                decoded = self._decode_one_recording(self._recording_on_device(speech, kwargs, fs), segments, kwargs, cfg, budget, threshold_ms)
+                speech = self._recording_on_device(load_audio_list([data_list[i]], fs=fs, audio_fs=kwargs.get("fs", 16000))[0],
+                                                   kwargs, fs)
+                decoded = self._decode_one_recording(speech, segments, kwargs, cfg, budget, threshold_ms)
                 order = sorted(range(n), key=lambda j: segments[j][1] - segments[j][0])   # stable, ascending duration
             if len(decoded) != n:
                 out.append({"key": key, "text": "", "timestamp": []})
@@ -694,7 +771,15 @@ class AutoModel:
                 if word_text is not None and punc_array is not None:
                     surface_sentences = punc_align.timestamp_sentences_from_surface(punc_text, stamps, punc_array, punc_model,
                                                                                     return_raw_text=return_raw_text)
-            if kwargs.get("sentence_timestamp", False):                                   # :1198-1234
+            spk_model = getattr(self, "spk_model", None)
+            if spk_model is not None and kwargs.get("return_spk_res", True):                 # :1122-1196
+                if speech is None:
+                    speech = self._recording_on_device(load_audio_list([data_list[i]], fs=fs, audio_fs=kwargs.get("fs", 16000))[0],
+                                                       kwargs, fs)
+                merged["sentence_info"] = self._speaker_sentences(
+                    speech, segments, restored, merged, kwargs, punc_res, punc_array, stamps, stamp_text, surface_sentences,
+                    return_raw_text)
+            elif kwargs.get("sentence_timestamp", False):                                 # :1198-1234
                 from .timestamps import timestamp_sentence
                 from .vad_utils import vad_segment_sentences
                 if not len(merged["text"].strip()):

@@ -258,3 +258,31 @@ def make_paraformer_confident(model, feats: torch.Tensor, flens, margin: float =
         lay.bias.copy_(b.to(lay.bias.device))
     model.decoder.mark_dirty()
     return {"decoder.output_layer.weight": W.cpu(), "decoder.output_layer.bias": b.cpu()}, stats
+
+
+def campplus_state_dict(seed: int = 0, embedding_size: int = 192) -> Dict[str, torch.Tensor]:
+    """A CAM++ state dict in the reference's layout (funasr/models/campplus/model.py; 937 keys) with He-scaled conv weights and
+    NON-trivial BatchNorm statistics (weight near 1, bias / running_mean off zero, running_var in [0.5, 2]), so that folding a
+    BatchNorm into the conv before it is exercised and every layer still sees activations of order one."""
+    from .campplus import CAMPPlus
+
+    g = torch.Generator().manual_seed(seed)
+    shapes = {k: tuple(v.shape) for k, v in CAMPPlus(embedding_size=embedding_size).state_dict().items()}
+    sd = {}
+    for k, shp in shapes.items():
+        if k.endswith("num_batches_tracked"):
+            sd[k] = torch.tensor(0, dtype=torch.long)
+        elif k.endswith("running_mean"):
+            sd[k] = 0.2 * torch.randn(shp, generator=g)
+        elif k.endswith("running_var"):
+            sd[k] = 0.5 + 1.5 * torch.rand(shp, generator=g)
+        elif ".bn" in k or "batchnorm" in k or "shortcut.1" in k:
+            sd[k] = (1.0 + 0.2 * torch.randn(shp, generator=g)) if k.endswith("weight") else 0.1 * torch.randn(shp, generator=g)
+        elif k.endswith("bias"):
+            sd[k] = 0.1 * torch.randn(shp, generator=g)
+        else:
+            fan_in = 1
+            for d in shp[1:]:
+                fan_in *= d
+            sd[k] = torch.randn(shp, generator=g) * (2.0 / fan_in) ** 0.5
+    return sd

@@ -25,6 +25,7 @@
  *   pf_stream     <-> ParaformerStreaming chunk step         funasr/models/paraformer_streaming/model.py
  *   pf_vad, pf_vad_decision <-> FsmnVADStreaming (network / state machine)   funasr/models/fsmn_vad_streaming/{encoder,model}.py
  *   pf_k_lstm     <-> torch.nn.LSTM layer (hotword encoder of SeACo, seaco_paraformer/model.py:388-424)
+ *   pf_campplus   <-> CAMPPlus.forward (speaker embedding)  funasr/models/campplus/model.py, components.py
  *
  * The handle style (opaque pointer, int return codes, library-owned scratch) follows the reference's own C
  * API for the same path, runtime/onnxruntime/include/funasrruntime.h:21-24,58-73. Tensor names accepted by
@@ -387,6 +388,36 @@ int pf_vad_decision_state(const pf_vad_decision* d);   /* 1 start point not dete
  * `capacity`; with streaming_events a started segment is [beg, -1] and closed later by [-1, end]); -1 on error. */
 int pf_vad_decision_push(pf_vad_decision* d, const float* sil_scores, const float* decibels, int32_t n_frames,
                          int32_t is_final, int32_t streaming_events, int32_t* segments_out, int32_t capacity);
+
+/* ---- CAM++ speaker embedding (funasr/models/campplus/model.py CAMPPlus.forward, output_level "segment",
+ * config_str "batchnorm-relu"). Tensor names are the reference's state_dict keys: "head.conv1.weight", "head.bn1.running_mean",
+ * "head.layer1.0.shortcut.0.weight", "xvector.tdnn.linear.weight", "xvector.block1.tdnnd1.cam_layer.linear1.bias",
+ * "xvector.transit1.nonlinear.batchnorm.weight", "xvector.dense.nonlinear.batchnorm.running_var", ... (every parameter and
+ * BatchNorm running statistic; num_batches_tracked is not taken). BatchNorms that follow a conv are folded into it at the
+ * first forward after a set_tensor. Only the published shape is built: feat_dim 80, embedding 192, growth 32, bn_size 4,
+ * init_channels 128, m_channels 32. Activations live in a handle-owned workspace (see pf_campplus_set_max_batch). */
+typedef struct pf_campplus pf_campplus;
+typedef struct pf_campplus_config {
+    int32_t feat_dim, embedding_size, growth_rate, bn_size, init_channels, m_channels;
+    float bn_eps;             /* 1e-5 (torch BatchNorm default) */
+} pf_campplus_config;
+pf_campplus* pf_campplus_create(const pf_campplus_config* cfg);
+void pf_campplus_destroy(pf_campplus* h);
+int pf_campplus_set_tensor(pf_campplus* h, const char* name, const float* data, int64_t numel);
+int pf_campplus_missing(const pf_campplus* h);
+/* chunks per launch sequence (default 256); never changes a result bit. The workspace grows with chunks x frames (about 31 KB per
+ * input frame: the head's three 80 x 32 planes): this bounds it for the fixed 1.5-s chunks of embed_chunks, while ONE long
+ * utterance through pf_campplus_forward needs workspace for its whole length (about 11 GB per hour of audio). */
+int pf_campplus_set_max_batch(pf_campplus* h, int32_t max_chunks);
+/* feats_dev [B, T, feat_dim] (already mean-normalised, as extract_feature gives them) -> emb_dev [B, embedding_size].
+ * T must give at least 2 frames after the stride-2 TDNN (T >= 3). No sync. */
+int pf_campplus_forward(pf_campplus* h, const float* feats_dev, int32_t B, int32_t T, float* emb_dev, void* stream);
+/* N chunks of chunk_len samples cut from one device waveform wav_dev [n_samples]: chunk i = samples
+ * [starts_host[i], starts_host[i] + valid_host[i]) followed by zeros up to chunk_len (valid_host NULL: chunk_len samples; samples
+ * past the waveform read as zero) -> kaldi fbank (80 bins, povey window, no 2^15 scaling, dither 0, snip_edges) -> minus the
+ * chunk's time mean -> the network -> emb_dev [N, embedding_size]. Every chunk's embedding is bitwise independent of N. No sync. */
+int pf_campplus_embed_chunks(pf_campplus* h, const float* wav_dev, int64_t n_samples, const int64_t* starts_host,
+                             const int32_t* valid_host, int32_t N, int32_t chunk_len, float* emb_dev, void* stream);
 
 typedef struct pf_ctc pf_ctc;
 pf_ctc* pf_ctc_create(int32_t d_model, int32_t vocab_size);
