@@ -82,6 +82,14 @@ class pf_campplus_config(C.Structure):
                [("bn_eps", C.c_float)]
 
 
+class pf_emotion2vec_config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("embed_dim", "num_heads", "ffn_dim", "prenet_depth", "depth", "num_extra_tokens",
+                                          "num_alibi_heads", "alibi_scale_layers", "alibi_scale_heads", "n_conv")] + \
+               [("conv_kernel", C.c_int32 * 8), ("conv_stride", C.c_int32 * 8)] + \
+               [(n, C.c_int32) for n in ("conv_pos_depth", "conv_pos_kernel", "conv_pos_groups", "vocab_size", "normalize", "precision")] + \
+               [("norm_eps", C.c_float)]
+
+
 class pf_stream_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_streams", "chunk_left", "chunk_cur", "chunk_right", "enc_look_back",
                                           "dec_look_back", "max_frames", "max_tokens", "use_graph")]
@@ -162,6 +170,14 @@ SIGNATURES = {
     "pf_campplus_set_max_batch": (C.c_int, [_vp, _i32]),
     "pf_campplus_forward": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "pf_campplus_embed_chunks": (C.c_int, [_vp, _vp, _i64, C.POINTER(C.c_int64), _pi32, _i32, _i32, _vp, _vp]),
+    "pf_emotion2vec_create": (_vp, [C.POINTER(pf_emotion2vec_config)]),
+    "pf_emotion2vec_destroy": (None, [_vp]),
+    "pf_emotion2vec_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),
+    "pf_emotion2vec_missing": (C.c_int, [_vp]),
+    "pf_emotion2vec_set_label_mask": (C.c_int, [_vp, _pi32, _i32]),
+    "pf_emotion2vec_set_max_samples": (C.c_int, [_vp, _i64]),
+    "pf_emotion2vec_num_frames": (_i32, [_vp, _i64]),
+    "pf_emotion2vec_forward": (C.c_int, [_vp, _vp, C.POINTER(C.c_int64), _i32, _vp, _vp, _vp, _vp]),
     "pf_ctc_create": (_vp, [_i32, _i32]),
     "pf_ctc_destroy": (None, [_vp]),
     "pf_ctc_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),

@@ -10,8 +10,8 @@ Mirrors the dispatch half of funasr/auto/auto_model.py that sits on the hot path
     lists of paths / arrays / tensors, raw PCM bytes), the batch loop calling
     `model.inference(data_in=..., key=..., tokenizer=..., frontend=..., **kwargs)` under `torch.no_grad()` (:812-814),
     RTF bookkeeping from `meta_data["batch_data_time"]` (:823-833).
-Model directory format (funasr/download/download_model_from_hub.py:80-97): `config.yaml`, `model.pt`, `tokens.json`,
-`am.mvn`. No hub download (no network): `model` must be a local directory.
+Model directory format (funasr/download/download_model_from_hub.py:80-97): `config.yaml`, `model.pt`, `tokens.json` (or
+`tokens.txt`; `tokens.json` wins), `am.mvn`. No hub download (no network): `model` must be a local directory.
 `inference_with_vad` (:852-1254), ASR half: a VAD model -- any object that follows the FunASR model contract and returns
 `[{"key", "value": [[beg_ms, end_ms], ...]}]`, e.g. the reference's own FsmnVADStreaming -- cuts each recording into
 segments; the segments are sorted by length, packed into batches under the reference's `batch_size_s` /
@@ -44,6 +44,7 @@ import torch
 from . import bicif_paraformer as _bicif_paraformer  # noqa: F401  (registers BiCifParaformer / CifPredictorV3)
 from . import contextual_paraformer as _contextual_paraformer  # noqa: F401  (registers ContextualParaformer + its decoder)
 from . import ct_transformer as _ct_transformer  # noqa: F401  (registers CTTransformer)
+from . import emotion2vec as _emotion2vec  # noqa: F401  (registers Emotion2vec)
 from . import fsmn_vad as _fsmn_vad  # noqa: F401  (registers FSMN / FsmnVADStreaming)
 from . import paraformer as _paraformer  # noqa: F401  (registers the model classes)
 from . import paraformer_streaming as _paraformer_streaming  # noqa: F401  (WavFrontendOnline)
@@ -150,8 +151,13 @@ def load_model_dir(model_dir: str) -> dict:
     init_param = init_param or pt
     if init_param:
         kwargs["init_param"] = init_param
-    tokens = resolve("tokenizer_conf.token_list", "tokens.json") if "tokenizer_conf" not in metas else None
-    tokens = tokens or (os.path.join(model_dir, "tokens.json") if os.path.exists(os.path.join(model_dir, "tokens.json")) else None)
+    tokens = None
+    if "tokenizer_conf" not in metas and "tokenizer_conf.token_list" in metas:
+        tokens = resolve("tokenizer_conf.token_list", None)
+    # download_model_from_hub.py:87-90: tokens.txt (emotion2vec's label list), then tokens.json, which wins when both exist
+    for name in ("tokens.json", "tokens.txt"):
+        if not tokens and os.path.exists(os.path.join(model_dir, name)):
+            tokens = os.path.join(model_dir, name)
     if tokens:
         kwargs.setdefault("tokenizer_conf", {})
         kwargs["tokenizer_conf"] = dict(kwargs["tokenizer_conf"] or {}, token_list=tokens)

@@ -286,3 +286,44 @@ def campplus_state_dict(seed: int = 0, embedding_size: int = 192) -> Dict[str, t
                 fan_in *= d
             sd[k] = torch.randn(shp, generator=g) * (2.0 / fan_in) ** 0.5
     return sd
+
+
+def emotion2vec_conf(embed_dim: int = 256, num_heads: int = 4, prenet_depth: int = 1, depth: int = 2, num_alibi_heads: int = None,
+                     per_head: bool = True) -> dict:
+    """an emotion2vec model_conf (template.yaml's layout) at a chosen size; the conv encoder is the real 512-channel stack"""
+    return {"embed_dim": embed_dim, "num_heads": num_heads, "depth": depth, "mlp_ratio": 4.0, "norm_eps": 1e-05, "norm_affine": True,
+            "layer_norm_first": False, "normalize": True, "extractor_mode": "layer_norm",
+            "encoder_dropout": 0.0, "post_mlp_drop": 0.0, "attention_dropout": 0.0, "activation_dropout": 0.0, "dropout_input": 0.0,
+            "layerdrop": 0.0, "start_drop_path_rate": 0.0, "end_drop_path_rate": 0.0, "end_of_block_targets": False,
+            "modalities": {"audio": {"prenet_depth": prenet_depth, "num_extra_tokens": 10, "init_extra_token_zero": True,
+                                     "use_alibi_encoder": True, "alibi_scale": 1.0, "learned_alibi": False, "learned_alibi_scale": True,
+                                     "learned_alibi_scale_per_head": per_head, "learned_alibi_scale_per_layer": False,
+                                     "num_alibi_heads": num_alibi_heads or num_heads, "model_depth": depth, "extractor_mode": "layer_norm",
+                                     "feature_encoder_spec": "[(512, 10, 5)] + [(512, 3, 2)] * 4 + [(512,2,2)] + [(512,2,2)]",
+                                     "conv_pos_width": 95, "conv_pos_groups": 16, "conv_pos_depth": 5, "conv_pos_pre_ln": False,
+                                     "prenet_layerdrop": 0.0, "prenet_dropout": 0.0, "start_drop_path_rate": 0.0,
+                                     "end_drop_path_rate": 0.0, "local_grad_mult": 1.0, "decoder": None}}}
+
+
+def emotion2vec_state_dict(seed: int, model) -> Dict[str, torch.Tensor]:
+    """synthetic weights in the layout of `model` (an Emotion2vec module): fan-in scaled convs / linears, LayerNorms near
+    identity, random extra tokens, per-head ALiBi scales around 1 with one negative entry (clamped to 0 by the model)"""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for k, v in model.state_dict().items():
+        shp = tuple(v.shape)
+        if k.endswith("alibi_scale"):
+            t = 0.5 + torch.rand(shp, generator=g)
+            t.view(-1)[min(1, t.numel() - 1)] = -0.3
+            sd[k] = t
+        elif k.endswith("extra_tokens"):
+            sd[k] = torch.randn(shp, generator=g)
+        elif len(shp) == 1:
+            is_ln = any(s in k for s in ("norm", ".2.1.", "project_features.1."))
+            sd[k] = (1.0 + 0.2 * torch.randn(shp, generator=g)) if (is_ln and k.endswith("weight")) else 0.1 * torch.randn(shp, generator=g)
+        else:
+            fan_in = 1
+            for d in shp[1:]:
+                fan_in *= d
+            sd[k] = torch.randn(shp, generator=g) * (1.0 / fan_in) ** 0.5
+    return sd

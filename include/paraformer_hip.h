@@ -419,6 +419,45 @@ int pf_campplus_forward(pf_campplus* h, const float* feats_dev, int32_t B, int32
 int pf_campplus_embed_chunks(pf_campplus* h, const float* wav_dev, int64_t n_samples, const int64_t* starts_host,
                              const int32_t* valid_host, int32_t N, int32_t chunk_len, float* emb_dev, void* stream);
 
+/* ---- emotion2vec (funasr/models/emotion2vec/model.py Emotion2vec.extract_features + the inference head): waveform norm, the
+ * 512-channel conv encoder (extractor_mode "layer_norm"), project_features, the grouped positional conv, extra tokens, context
+ * LayerNorm, prenet_depth + depth post-LN ALiBi blocks (head dim 64), then the mean over frames, proj and softmax. Tensor names
+ * are the reference's state_dict keys: "modality_encoders.AUDIO.local_encoder.conv_layers.0.0.weight",
+ * "modality_encoders.AUDIO.relative_positional_encoder.1.0.weight", "modality_encoders.AUDIO.context_encoder.blocks.0.attn.qkv.weight",
+ * "blocks.0.mlp.fc2.bias", "proj.weight" (vocab_size > 0), ... (the training-only decoder.* keys are not taken).
+ * precision 0: every GEMM on the exact-f32 MFMA; 3: on the fp16 MFMA with two-plane operands (fp32-class results; plane
+ * exponents from a-priori bounds of the weights only). Attention, convs and LayerNorms are fp32 in both. Every utterance's
+ * results are bitwise the same alone or in any batch. */
+typedef struct pf_emotion2vec pf_emotion2vec;
+typedef struct pf_emotion2vec_config {
+    int32_t embed_dim, num_heads, ffn_dim, prenet_depth, depth;
+    int32_t num_extra_tokens, num_alibi_heads;
+    int32_t alibi_scale_layers;   /* rows of alibi_scale: 1, or prenet_depth + depth (learned_alibi_scale_per_layer) */
+    int32_t alibi_scale_heads;    /* 1, or num_alibi_heads (learned_alibi_scale_per_head) */
+    int32_t n_conv, conv_kernel[8], conv_stride[8];    /* the conv encoder: 512 channels per layer */
+    int32_t conv_pos_depth, conv_pos_kernel, conv_pos_groups;
+    int32_t vocab_size;           /* 0: no proj (features only) */
+    int32_t normalize;            /* F.layer_norm over the whole waveform first */
+    int32_t precision;            /* 0 fp32, 3 f16x2 */
+    float norm_eps;
+} pf_emotion2vec_config;
+pf_emotion2vec* pf_emotion2vec_create(const pf_emotion2vec_config* cfg);
+void pf_emotion2vec_destroy(pf_emotion2vec* h);
+int pf_emotion2vec_set_tensor(pf_emotion2vec* h, const char* name, const float* data, int64_t numel);
+int pf_emotion2vec_missing(const pf_emotion2vec* h);
+/* classes whose label starts with "unuse" (mask_host[c] != 0) get -inf before the softmax; default none masked */
+int pf_emotion2vec_set_label_mask(pf_emotion2vec* h, const int32_t* mask_host, int32_t n);
+/* samples per launch sequence (default 8 M, about 7 GB of workspace): larger batches run as sub-batches of whole utterances;
+ * never changes a result bit */
+int pf_emotion2vec_set_max_samples(pf_emotion2vec* h, int64_t max_samples);
+/* frames of an utterance of n samples (0 if it is too short for one frame) */
+int32_t pf_emotion2vec_num_frames(const pf_emotion2vec* h, int64_t n_samples);
+/* wav_dev: B utterances back to back (lens_host[b] samples each) -> optional outputs: feats_dev [sum of frames, D] (each
+ * utterance's frames after the extra tokens, back to back), pooled_dev [B, D] (their mean), probs_dev [B, vocab_size].
+ * Returns nonzero (pf_last_error) when an utterance is too short for one frame (400 samples for the published encoder). No sync. */
+int pf_emotion2vec_forward(pf_emotion2vec* h, const float* wav_dev, const int64_t* lens_host, int32_t B, float* feats_dev,
+                           float* pooled_dev, float* probs_dev, void* stream);
+
 typedef struct pf_ctc pf_ctc;
 pf_ctc* pf_ctc_create(int32_t d_model, int32_t vocab_size);
 void pf_ctc_destroy(pf_ctc* c);
