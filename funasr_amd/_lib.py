@@ -90,6 +90,15 @@ class pf_emotion2vec_config(C.Structure):
                [("norm_eps", C.c_float)]
 
 
+class pf_conformer_config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("input_dim", "d_model", "n_heads", "ffn_dim", "n_blocks", "kernel_size", "macaron", "legacy",
+                                          "precision")] + [("ln_eps", C.c_float)]
+
+
+class pf_tdecoder_config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("vocab_size", "d_model", "n_heads", "ffn_dim", "n_blocks")] + [("ln_eps", C.c_float)]
+
+
 class pf_stream_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_streams", "chunk_left", "chunk_cur", "chunk_right", "enc_look_back",
                                           "dec_look_back", "max_frames", "max_tokens", "use_graph")]
@@ -178,6 +187,22 @@ SIGNATURES = {
     "pf_emotion2vec_set_max_samples": (C.c_int, [_vp, _i64]),
     "pf_emotion2vec_num_frames": (_i32, [_vp, _i64]),
     "pf_emotion2vec_forward": (C.c_int, [_vp, _vp, C.POINTER(C.c_int64), _i32, _vp, _vp, _vp, _vp]),
+    "pf_conformer_create": (_vp, [C.POINTER(pf_conformer_config)]),
+    "pf_conformer_destroy": (None, [_vp]),
+    "pf_conformer_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),
+    "pf_conformer_missing": (C.c_int, [_vp]),
+    "pf_conformer_set_precision": (C.c_int, [_vp, _i32]),
+    "pf_conformer_num_frames": (_i32, [_vp, _i32, _i32]),
+    "pf_conformer_forward": (C.c_int, [_vp, _vp, _pi32, _i32, _i32, _vp, _pi32, _vp]),
+    "pf_tdecoder_create": (_vp, [C.POINTER(pf_tdecoder_config)]),
+    "pf_tdecoder_destroy": (None, [_vp]),
+    "pf_tdecoder_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),
+    "pf_tdecoder_missing": (C.c_int, [_vp]),
+    "pf_tdecoder_begin": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "pf_tdecoder_step": (C.c_int, [_vp, _pi32, _i32, _i32, _vp, _vp]),
+    "pf_tdecoder_reorder": (C.c_int, [_vp, _pi32, _i32, _vp]),
+    "pf_k_relpos_attention": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "pf_k_conformer_glu_dw": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "pf_ctc_create": (_vp, [_i32, _i32]),
     "pf_ctc_destroy": (None, [_vp]),
     "pf_ctc_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),

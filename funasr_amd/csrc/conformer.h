@@ -1,0 +1,52 @@
+// Kernel launchers of the Conformer encoder and the Transformer decoder step (conformer.hip, attention_relpos.hip; driven by
+// engine_conformer.hip). Activations are rows of a [B * T, D] buffer (T = the BATCH's encoder length: the reference computes every
+// row of the zero-padded batch and so does this path). Every kernel computes a row in a fixed order and without atomics.
+#pragma once
+#include "common.h"
+
+namespace pf {
+
+// Conv2d(1 -> C, 3 x 3, stride 2) + ReLU of Conv2dSubsampling, written channels-last into TWO buffers so that the second conv
+// becomes three plain GEMMs over overlapping strided views: conv0's even time rows go to `even` and its odd rows to `odd`, both
+// [B][NE][FP][C] with FP = 2 * (F2 + 1) frequency columns (F1 = (F - 1) / 2 of them computed, the rest zero) and NE = T2 + 1 time
+// rows (rows past conv0's T1 are zero). feats [B, Tin, F].
+int launch_cf_conv0(const float* feats, int B, int Tin, int F, const float* w, const float* bias, int C, int T1, int F1, int NE,
+                    int FP, float* even, float* odd, hipStream_t stream);
+
+// in place over n floats: mode 0 = ReLU, 1 = Swish (x * sigmoid(x)); n % 4 == 0
+int launch_cf_act(float* x, size_t n, int mode, hipStream_t stream);
+
+// y[b * T + t] = x[b * NE + t] * scale for t < T (the embed linear's rows without the waste row per sequence, times sqrt(D))
+int launch_cf_scale_rows(const float* x, int NE, float* y, int B, int T, int D, float scale, hipStream_t stream);
+
+// The Conformer convolution module between its two pointwise convs: g [B * T, 2 D] (value | gate) -> GLU -> depthwise Conv1d over
+// time (taps odd <= 31, zero padding at the edges of each sequence's T rows) + bias -> eval-mode BatchNorm as y * bn_scale +
+// bn_shift -> Swish -> y [B * T, D]. dw [D][taps]. D % 64 == 0.
+int launch_cf_glu_dw(const float* g, const float* dw, const float* dw_bias, const float* bn_scale, const float* bn_shift, int B,
+                     int T, int D, int taps, float* y, hipStream_t stream);
+
+// Relative-position self-attention (Transformer-XL style), head dim 64, flash-style: no [T, T] tensor reaches memory.
+// qkv [B * T, 3 D] (q | k | v, head h at column 64 h of each); P [nP, D] = linear_pos(pos_emb); u, v [H, 64] = pos_bias_u / _v.
+// score(i, j) = ((q_i + u) . k_j + bd(i, j)) / 8, keys j >= klens[b] masked (klens[b] == 0: zero rows), with qv_i = q_i + v and
+//   legacy == 0 (nP = 2 T - 1): bd(i, j) = qv_i . P[T - 1 - i + j]
+//   legacy == 1 (nP = T):       bd(i, j) = qv_i . P[T - 1 - i + j] for j <= i, 0 for j == i + 1, qv_{i + 1} . P[j - i - 2] for j >= i + 2
+// (the reference's rel_shift of a [T, T] matrix wraps the next row into the upper triangle). q . k, the band products and p . v run
+// on the matrix cores in exact fp32 (v_mfma_f32_32x32x2_f32); fp32 online softmax -> out [B * T, D].
+int launch_cf_relpos_attention(const float* qkv, const float* P, const float* u, const float* v, const int* klens, int B, int T,
+                               int H, int legacy, float* out, hipStream_t stream);
+
+// ---- Transformer decoder step
+// x[r] = table[ids[r]] * scale + pe[pos] (r < n; ids on the device)
+int launch_td_embed(const float* table, const int* ids, const float* pe_row, float scale, float* x, int n, int D, hipStream_t stream);
+
+// few-query attention, head dim 64: query r (q [n, D], head h at column 64 h) over nk keys K / V rows of `ldkv` floats, the
+// rows of query r starting at K + r * seq_stride (seq_stride 0: every query reads the same memory). softmax(q . k / 8) v -> out [n, D].
+int launch_td_attention(const float* q, const float* K, const float* V, int ldkv, size_t seq_stride, int nk, int n, int H, float* out,
+                        hipStream_t stream);
+
+// cache reorder: dst[l][k][0 .. len) = src[l][parents[k]][0 .. len) for every layer l < L and k < n; a slot is `slot_floats` wide,
+// a layer `layer_floats`, a position `row_floats`
+int launch_td_reorder(const float* src, float* dst, const int* parents, int n, int L, size_t layer_floats, size_t slot_floats,
+                      int len, int row_floats, hipStream_t stream);
+
+}  // namespace pf

@@ -1,0 +1,535 @@
+// C-ABI layer, Conformer ASR: pf_conformer_* (the encoder) and pf_tdecoder_* (the autoregressive Transformer decoder step);
+// kernels in conformer.hip and attention_relpos.hip, GEMMs through the shared launchers.
+//
+// Encoder forward over the zero-padded batch [B, Tin, F] (the reference runs Conv2dSubsampling and the convolution module over
+// the padded tensor without masking, so every row of the batch is computed and a clip's frames depend on the batch's length):
+//   conv0 + ReLU into the even / odd time-row buffers -> conv1 as THREE accumulating GEMMs over overlapping strided views
+//   (element r = t (F2 + 1) + f of the output reads the contiguous 3 C floats at 2 C r of even[t], odd[t], even[t + 1]: lda = 2 C,
+//   K = 3 C, no im2col; one output column in F2 + 1 is waste) + ReLU -> the output linear over rows of (F2 + 1) C floats (weight
+//   permuted, zero for the waste column) -> x sqrt(D) into [B T, D] rows -> blocks: [macaron FFN] -> LayerNorm, q / k / v and
+//   linear_pos GEMMs, relative-position attention, linear_out (+ residual) -> LayerNorm, pointwise-1, GLU + depthwise + BatchNorm
+//   + Swish, pointwise-2 (+ residual) -> FFN -> norm_final; after_norm.
+// ff_scale = 0.5 of the macaron pair is folded into w_2 and its bias at load (an exact scaling), so the residual rides in the GEMM.
+// precision 3 (f16x2): the block GEMMs take two-plane fp16 operands with exponents from a-priori bounds of the weights (LayerNorm
+// outputs: sqrt(D) max|gamma| + max|beta|; hidden / value / conv-module rows: row-L1 bounds). The subsampling GEMMs (their input is
+// the caller's features, for which no bound exists) and linear_pos stay exact-fp32 MFMA GEMMs in both modes.
+//
+// Decoder: begin() computes the cross-attention K / V of every layer once per utterance; step() runs all running hypotheses of a
+// beam through the layers (M = n_hyp rows: the small-M weight-streaming GEMMs, fp32 in both modes), appending each layer's
+// self-attention K / V at `pos` of the hypothesis' slot; reorder() gathers the surviving hypotheses' parent slots on the device.
+#include <algorithm>
+#include <cmath>
+
+#include "engine_internal.h"
+#include "conformer.h"
+
+using namespace pf;
+
+namespace {
+
+struct CfBlockX { int e_ffm_in = 0, e_ffm_h = 0, e_mha_in = 0, e_att = 0, e_conv_in = 0, e_cm = 0, e_ff_in = 0, e_ff_h = 0; };
+
+struct Cf {
+    pf_conformer_config cfg;
+    TensorTable tt;
+    unsigned long long prepared = ~0ull;
+    std::vector<CfBlockX> bx;
+    DevBuf bn, even, odd, ya, yb, lin, xa, xb, xn, qkv, P, att, hid, planes, klens;
+
+    int C() const { return cfg.d_model; }
+    int F1() const { return (cfg.input_dim - 3) / 2 + 1; }
+    int F2() const { return (F1() - 3) / 2 + 1; }
+    int pos_rows() const { return cfg.legacy ? 5000 : 9999; }
+    static int sub(int L, int n) { const int m = std::min(L, n - 2); return m <= 0 ? 0 : (m + 1) / 2; }
+    // encoder frames of a length-L clip inside a batch padded to n frames (the mask rule x_mask[:, :, :-2:2][:, :, :-2:2])
+    static int out_len(int L, int n) { const int n1 = sub(n, n); return sub(sub(L, n), n1); }
+    std::vector<float> host(const std::string& name) {
+        const Tensor& t = tt.t.at(name);
+        std::vector<float> v((size_t)t.numel);
+        if (hipMemcpy(v.data(), t.d, sizeof(float) * v.size(), hipMemcpyDeviceToHost) != hipSuccess) v.clear();
+        return v;
+    }
+    int derived(const std::string& name, const std::vector<float>& v) {
+        if (!tt.t.count(name) && tt.add(name, (int64_t)v.size())) return -2;
+        return tt.set(name.c_str(), v.data(), (int64_t)v.size());
+    }
+    float ln_bound(const std::string& p) {
+        std::vector<float> g = host(p + "weight"), b = host(p + "bias");
+        float mg = 0.f, mb = 0.f;
+        for (float v : g) mg = fmaxf(mg, fabsf(v));
+        for (float v : b) mb = fmaxf(mb, fabsf(v));
+        return sqrtf((float)cfg.d_model) * mg + mb;
+    }
+    int prepare(hipStream_t s);
+};
+
+std::string blk(int i) { return "encoders." + std::to_string(i) + "."; }
+
+int Cf::prepare(hipStream_t s) {
+    const int C = cfg.d_model, D = cfg.d_model, f2 = F2(), NB = cfg.n_blocks, K = cfg.kernel_size, FF = cfg.ffn_dim;
+    {   // conv1 [C, C, 3, 3] -> per time tap dt the [C, 3 C] matrix W_dt[co][df C + ci]
+        std::vector<float> w = host("embed.conv.2.weight");
+        if (w.empty()) { set_error("conformer: weight copy failed"); return -2; }
+        for (int dt = 0; dt < 3; ++dt) {
+            std::vector<float> m((size_t)C * 3 * C);
+            for (int co = 0; co < C; ++co)
+                for (int df = 0; df < 3; ++df)
+                    for (int ci = 0; ci < C; ++ci) m[((size_t)co * 3 + df) * C + ci] = w[(((size_t)co * C + ci) * 3 + dt) * 3 + df];
+            if (derived("#conv1.tap" + std::to_string(dt), m)) return -2;
+        }
+        // output linear [D, C F2] (feature c F2 + f) -> [D, (F2 + 1) C] (feature f C + c, zero for the waste column)
+        std::vector<float> l = host("embed.out.0.weight");
+        std::vector<float> m((size_t)D * (f2 + 1) * C, 0.f);
+        for (int d = 0; d < D; ++d)
+            for (int c = 0; c < C; ++c)
+                for (int f = 0; f < f2; ++f) m[((size_t)d * (f2 + 1) + f) * C + c] = l[((size_t)d * C + c) * f2 + f];
+        if (derived("#embed.out", m)) return -2;
+    }
+    std::vector<float> bnv((size_t)NB * 2 * D);
+    bx.assign(NB, CfBlockX());
+    if (cfg.precision == 3) tt.drop_bf16();
+    for (int i = 0; i < NB; ++i) {
+        const std::string p = blk(i);
+        std::vector<float> g = host(p + "conv_module.norm.weight"), b = host(p + "conv_module.norm.bias"),
+                           mu = host(p + "conv_module.norm.running_mean"), var = host(p + "conv_module.norm.running_var");
+        if (g.empty() || b.empty() || mu.empty() || var.empty()) { set_error("conformer: weight copy failed"); return -2; }
+        for (int c = 0; c < D; ++c) {
+            const double sc = (double)g[c] / std::sqrt((double)var[c] + 1e-5);
+            bnv[((size_t)i * 2) * D + c] = (float)sc;
+            bnv[((size_t)i * 2 + 1) * D + c] = (float)((double)b[c] - (double)mu[c] * sc);
+        }
+        for (const char* ff : {"feed_forward.", "feed_forward_macaron."}) {
+            if (!cfg.macaron) break;
+            std::vector<float> w = host(p + ff + "w_2.weight"), bb = host(p + ff + "w_2.bias");
+            for (float& v : w) v *= 0.5f;
+            for (float& v : bb) v *= 0.5f;
+            if (derived(p + ff + "w_2.weight#half", w) || derived(p + ff + "w_2.bias#half", bb)) return -2;
+        }
+        if (cfg.precision != 3) continue;
+        CfBlockX& x = bx[i];
+        float hb = 0.f;
+        auto ffn = [&](const std::string& f, const std::string& norm, int* e_in, int* e_h) {
+            const float nb = ln_bound(p + norm);
+            *e_in = exp_for_bound(nb);
+            if (TensorTable::dev_linear_bound(tt.get(p + f + "w_1.weight"), FF, D, D, tt.get(p + f + "w_1.bias"), nb, &hb, s)) return -2;
+            *e_h = exp_for_bound(hb);
+            return 0;
+        };
+        if (cfg.macaron && ffn("feed_forward_macaron.", "norm_ff_macaron.", &x.e_ffm_in, &x.e_ffm_h)) return -2;
+        if (ffn("feed_forward.", "norm_ff.", &x.e_ff_in, &x.e_ff_h)) return -2;
+        const float mb = ln_bound(p + "norm_mha.");
+        x.e_mha_in = exp_for_bound(mb);
+        if (TensorTable::dev_linear_bound(tt.get(p + "self_attn.linear_v.weight"), D, D, D, tt.get(p + "self_attn.linear_v.bias"), mb, &hb, s))
+            return -2;
+        x.e_att = exp_for_bound(hb);
+        const float cb = ln_bound(p + "norm_conv.");
+        x.e_conv_in = exp_for_bound(cb);
+        if (TensorTable::dev_linear_bound(tt.get(p + "conv_module.pointwise_conv1.weight"), D, D, D,
+                                          tt.get(p + "conv_module.pointwise_conv1.bias"), cb, &hb, s))
+            return -2;
+        std::vector<float> dw = host(p + "conv_module.depthwise_conv.weight"), db = host(p + "conv_module.depthwise_conv.bias");
+        float zb = 0.f;
+        for (int c = 0; c < D; ++c) {
+            float l1 = 0.f;
+            for (int k = 0; k < K; ++k) l1 += fabsf(dw[(size_t)c * K + k]);
+            zb = fmaxf(zb, (hb * l1 + fabsf(db[c])) * fabsf(bnv[((size_t)i * 2) * D + c]) + fabsf(bnv[((size_t)i * 2 + 1) * D + c]));
+        }
+        x.e_cm = exp_for_bound(zb);
+    }
+    if (NB > 0) {
+        if (bn.ensure(sizeof(float) * bnv.size())) return -2;
+        PF_HIP_TRY(hipMemcpy(bn.p, bnv.data(), sizeof(float) * bnv.size(), hipMemcpyHostToDevice));
+    }
+    prepared = tt.version;
+    return 0;
+}
+
+// C[M, N] = A[M, K] (row stride lda) W^T + bias (+ R1) (ReLU before the addend); x2: two-plane fp16 operands with A's exponent e_a
+int cf_gemm(Cf* h, bool x2, const float* A, int lda, int M, int K, const std::string& wname, int N, const float* bias, const float* R1,
+            float* C, int ldc, int e_a, int relu, hipStream_t s) {
+    if (!x2) {
+        GemmArgs g{};
+        g.A = A; g.lda = lda; g.W = h->tt.get(wname); g.ldw = K; g.bias = bias; g.relu = relu;
+        g.R1 = R1; g.ldr1 = N; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
+        return launch_gemm_f32(g, s);
+    }
+    const size_t plane = (size_t)M * K;
+    if (h->planes.ensure(sizeof(unsigned short) * 2 * plane)) return -2;
+    unsigned short* P = h->planes.as<unsigned short>();
+    int rc;
+    if ((rc = launch_split2(A, lda, P, K, plane, M, K, pow2f(e_a), s))) return rc;
+    int ew = 0;
+    const unsigned short* W2 = h->tt.get_split2(wname, N, K, &ew, s);
+    if (!W2) return -2;
+    Gemm2Args g{};
+    g.A = P; g.lda = K; g.a_plane = plane;
+    g.W = W2; g.ldw = K; g.w_plane = (size_t)N * K;
+    g.oscale = pow2f(-(e_a + ew));
+    g.bias = bias; g.relu = relu; g.R1 = R1; g.ldr1 = N; g.C = C; g.ldc = ldc;
+    g.M = M; g.N = N; g.K = K;
+    return launch_gemm_f16x2(g, s);
+}
+
+int cf_forward(Cf* h, const float* feats, const int32_t* lens, int B, int Tin, float* out, int32_t* olens, hipStream_t s) {
+    const pf_conformer_config& c = h->cfg;
+    const int C = c.d_model, D = c.d_model, FF = c.ffn_dim, F = c.input_dim, f1 = h->F1(), f2 = h->F2(), FP = 2 * (f2 + 1);
+    const int T1 = (Tin - 3) / 2 + 1, T = (T1 - 3) / 2 + 1, NE = T + 1;
+    const bool x2 = c.precision == 3;
+    const float eps = c.ln_eps;
+    std::vector<int32_t> kl(B);
+    for (int b = 0; b < B; ++b) {
+        kl[b] = Cf::out_len(lens[b], Tin);
+        if (olens) olens[b] = kl[b];
+    }
+    const size_t M = (size_t)B * T, Mc = (size_t)B * NE * (f2 + 1), EO = (size_t)B * NE * FP * C, SL = (size_t)2 * FP * C;
+    const int nP = c.legacy ? T : 2 * T - 1;
+    if (h->even.ensure(sizeof(float) * (EO + SL)) || h->odd.ensure(sizeof(float) * (EO + SL)) || h->ya.ensure(sizeof(float) * Mc * C) ||
+        h->yb.ensure(sizeof(float) * Mc * C) || h->lin.ensure(sizeof(float) * (size_t)B * NE * D) || h->xa.ensure(sizeof(float) * M * D) ||
+        h->xb.ensure(sizeof(float) * M * D) || h->xn.ensure(sizeof(float) * M * D) || h->qkv.ensure(sizeof(float) * M * 3 * D) ||
+        h->P.ensure(sizeof(float) * (size_t)nP * D) || h->att.ensure(sizeof(float) * M * D) ||
+        h->hid.ensure(sizeof(float) * M * std::max(FF, 2 * D)) || h->klens.ensure(sizeof(int32_t) * B))
+        return -2;
+    if (upload_h2d(h->klens.p, kl.data(), sizeof(int32_t) * B, s)) return -2;
+    int rc;
+    float *even = h->even.as<float>(), *odd = h->odd.as<float>(), *ya = h->ya.as<float>(), *yb = h->yb.as<float>();
+    PF_HIP_TRY(hipMemsetAsync(even + EO, 0, sizeof(float) * SL, s));
+    PF_HIP_TRY(hipMemsetAsync(odd + EO, 0, sizeof(float) * SL, s));
+    if ((rc = launch_cf_conv0(feats, B, Tin, F, h->tt.get("embed.conv.0.weight"), h->tt.get("embed.conv.0.bias"), C, T1, f1, NE, FP, even,
+                              odd, s)))
+        return rc;
+    const float* cb = h->tt.get("embed.conv.2.bias");
+    if ((rc = cf_gemm(h, false, even, 2 * C, (int)Mc, 3 * C, "#conv1.tap0", C, cb, nullptr, ya, C, 0, 0, s))) return rc;
+    if ((rc = cf_gemm(h, false, odd, 2 * C, (int)Mc, 3 * C, "#conv1.tap1", C, nullptr, ya, yb, C, 0, 0, s))) return rc;
+    if ((rc = cf_gemm(h, false, even + (size_t)FP * C, 2 * C, (int)Mc, 3 * C, "#conv1.tap2", C, nullptr, yb, ya, C, 0, 0, s))) return rc;
+    if ((rc = launch_cf_act(ya, Mc * C, 0, s))) return rc;
+    if ((rc = cf_gemm(h, false, ya, (f2 + 1) * C, B * NE, (f2 + 1) * C, "#embed.out", D, h->tt.get("embed.out.0.bias"), nullptr,
+                      h->lin.as<float>(), D, 0, 0, s)))
+        return rc;
+    float* x = h->xa.as<float>();
+    float* y = h->xb.as<float>();
+    if ((rc = launch_cf_scale_rows(h->lin.as<float>(), NE, x, B, T, D, sqrtf((float)D), s))) return rc;
+    const float* pos = h->tt.get("pos_table") + (c.legacy ? (size_t)0 : (size_t)(5000 - T) * D);
+    float *xn = h->xn.as<float>(), *qkv = h->qkv.as<float>(), *Pm = h->P.as<float>(), *att = h->att.as<float>(), *hid = h->hid.as<float>();
+    const int Mi = (int)M;
+    auto ln = [&](const std::string& p, const float* in, float* o) {
+        return layernorm(in, D, h->tt.get(p + "weight"), h->tt.get(p + "bias"), o, D, Mi, D, D, eps, s);
+    };
+    for (int i = 0; i < c.n_blocks; ++i) {
+        const std::string p = blk(i);
+        const CfBlockX& e = h->bx[i];
+        const std::string half = c.macaron ? "#half" : "";
+        auto ffn = [&](const std::string& f, const std::string& norm, int e_in, int e_h) {
+            int r;
+            if ((r = ln(p + norm, x, xn))) return r;
+            if ((r = cf_gemm(h, x2, xn, D, Mi, D, p + f + "w_1.weight", FF, h->tt.get(p + f + "w_1.bias"), nullptr, hid, FF, e_in, 0, s))) return r;
+            if ((r = launch_cf_act(hid, M * FF, 1, s))) return r;
+            if ((r = cf_gemm(h, x2, hid, FF, Mi, FF, p + f + "w_2.weight" + half, D, h->tt.get(p + f + "w_2.bias" + half), x, y, D, e_h, 0, s)))
+                return r;
+            std::swap(x, y);
+            return 0;
+        };
+        if (c.macaron && (rc = ffn("feed_forward_macaron.", "norm_ff_macaron.", e.e_ffm_in, e.e_ffm_h))) return rc;
+        // relative-position self-attention
+        if ((rc = ln(p + "norm_mha.", x, xn))) return rc;
+        const char* names[3] = {"self_attn.linear_q.", "self_attn.linear_k.", "self_attn.linear_v."};
+        for (int j = 0; j < 3; ++j)
+            if ((rc = cf_gemm(h, x2, xn, D, Mi, D, p + names[j] + "weight", D, h->tt.get(p + names[j] + "bias"), nullptr, qkv + (size_t)j * D,
+                              3 * D, e.e_mha_in, 0, s)))
+                return rc;
+        if ((rc = cf_gemm(h, false, pos, D, nP, D, p + "self_attn.linear_pos.weight", D, nullptr, nullptr, Pm, D, 0, 0, s))) return rc;
+        if ((rc = launch_cf_relpos_attention(qkv, Pm, h->tt.get(p + "self_attn.pos_bias_u"), h->tt.get(p + "self_attn.pos_bias_v"),
+                                             h->klens.as<int>(), B, T, c.n_heads, c.legacy, att, s)))
+            return rc;
+        if ((rc = cf_gemm(h, x2, att, D, Mi, D, p + "self_attn.linear_out.weight", D, h->tt.get(p + "self_attn.linear_out.bias"), x, y, D,
+                          e.e_att, 0, s)))
+            return rc;
+        std::swap(x, y);
+        // convolution module
+        if ((rc = ln(p + "norm_conv.", x, xn))) return rc;
+        if ((rc = cf_gemm(h, x2, xn, D, Mi, D, p + "conv_module.pointwise_conv1.weight", 2 * D, h->tt.get(p + "conv_module.pointwise_conv1.bias"),
+                          nullptr, hid, 2 * D, e.e_conv_in, 0, s)))
+            return rc;
+        const float* bnp = h->bn.as<float>() + (size_t)i * 2 * D;
+        if ((rc = launch_cf_glu_dw(hid, h->tt.get(p + "conv_module.depthwise_conv.weight"), h->tt.get(p + "conv_module.depthwise_conv.bias"),
+                                   bnp, bnp + D, B, T, D, c.kernel_size, att, s)))
+            return rc;
+        if ((rc = cf_gemm(h, x2, att, D, Mi, D, p + "conv_module.pointwise_conv2.weight", D, h->tt.get(p + "conv_module.pointwise_conv2.bias"),
+                          x, y, D, e.e_cm, 0, s)))
+            return rc;
+        std::swap(x, y);
+        if ((rc = ffn("feed_forward.", "norm_ff.", e.e_ff_in, e.e_ff_h))) return rc;
+        if ((rc = ln(p + "norm_final.", x, y))) return rc;
+        std::swap(x, y);
+    }
+    return layernorm(x, D, h->tt.get("after_norm.weight"), h->tt.get("after_norm.bias"), out, D, Mi, D, D, eps, s);
+}
+
+// ================================================================================================ decoder
+struct Td {
+    pf_tdecoder_config cfg;
+    TensorTable tt;
+    DevBuf ckv, cache, x, y, xn, q, a, hid, logits, ids, par;
+    int T = 0, max_len = 0, max_hyp = 0, filled = 0, cur = 0;
+    size_t slot() const { return (size_t)max_len * 2 * cfg.d_model; }
+    size_t layer() const { return slot() * max_hyp; }
+    float* cache_of(int which, int l) { return cache.as<float>() + ((size_t)which * cfg.n_blocks + l) * layer(); }
+};
+
+std::string dl(int i) { return "decoders." + std::to_string(i) + "."; }
+
+}  // namespace
+
+extern "C" {
+
+pf_conformer* pf_conformer_create(const pf_conformer_config* cfg) {
+    if (!cfg) { set_error("conformer: null config"); return nullptr; }
+    if (check_device()) return nullptr;
+    const pf_conformer_config& c = *cfg;
+    const bool ok = c.input_dim >= 7 && c.input_dim <= 256 && c.d_model > 0 && c.d_model % 64 == 0 && c.d_model <= 2048 &&
+                    c.n_heads > 0 && c.d_model == 64 * c.n_heads && c.ffn_dim > 0 && c.ffn_dim % 32 == 0 && c.n_blocks >= 0 &&
+                    c.kernel_size % 2 == 1 && c.kernel_size >= 1 && c.kernel_size <= 31 && (c.macaron == 0 || c.macaron == 1) &&
+                    (c.legacy == 0 || c.legacy == 1) && (c.precision == 0 || c.precision == 3) && c.ln_eps > 0.f;
+    if (!ok) {
+        set_error("conformer: unsupported config (7 .. 256 input features, head dim 64, d_model % 64, ffn_dim % 32, odd kernel <= 31, "
+                  "precision 0 or 3)");
+        return nullptr;
+    }
+    std::unique_ptr<Cf> h(new Cf());
+    h->cfg = c;
+    const int D = c.d_model, C = c.d_model, FF = c.ffn_dim, K = c.kernel_size;
+    int rc = 0;
+    rc |= h->tt.add("embed.conv.0.weight", (int64_t)C * 9);
+    rc |= h->tt.add("embed.conv.0.bias", C);
+    rc |= h->tt.add("embed.conv.2.weight", (int64_t)C * C * 9);
+    rc |= h->tt.add("embed.conv.2.bias", C);
+    rc |= h->tt.add("embed.out.0.weight", (int64_t)D * C * h->F2());
+    rc |= h->tt.add("embed.out.0.bias", D);
+    rc |= h->tt.add("pos_table", (int64_t)h->pos_rows() * D);
+    auto lin = [&](const std::string& n, int o, int i, bool bias = true) {
+        rc |= h->tt.add(n + "weight", (int64_t)o * i);
+        if (bias) rc |= h->tt.add(n + "bias", o);
+    };
+    for (int i = 0; i < c.n_blocks; ++i) {
+        const std::string p = blk(i);
+        for (const char* n : {"linear_q.", "linear_k.", "linear_v.", "linear_out."}) lin(p + "self_attn." + n, D, D);
+        lin(p + "self_attn.linear_pos.", D, D, false);
+        rc |= h->tt.add(p + "self_attn.pos_bias_u", D);
+        rc |= h->tt.add(p + "self_attn.pos_bias_v", D);
+        lin(p + "feed_forward.w_1.", FF, D);
+        lin(p + "feed_forward.w_2.", D, FF);
+        if (c.macaron) {
+            lin(p + "feed_forward_macaron.w_1.", FF, D);
+            lin(p + "feed_forward_macaron.w_2.", D, FF);
+            lin(p + "norm_ff_macaron.", D, 1);
+        }
+        lin(p + "conv_module.pointwise_conv1.", 2 * D, D);
+        lin(p + "conv_module.depthwise_conv.", D, K);
+        lin(p + "conv_module.norm.", D, 1);
+        rc |= h->tt.add(p + "conv_module.norm.running_mean", D);
+        rc |= h->tt.add(p + "conv_module.norm.running_var", D);
+        lin(p + "conv_module.pointwise_conv2.", D, D);
+        for (const char* n : {"norm_ff.", "norm_mha.", "norm_conv.", "norm_final."}) lin(p + n, D, 1);
+    }
+    lin("after_norm.", D, 1);
+    if (rc) return nullptr;
+    return reinterpret_cast<pf_conformer*>(h.release());
+}
+void pf_conformer_destroy(pf_conformer* h) { delete reinterpret_cast<Cf*>(h); }
+int pf_conformer_set_tensor(pf_conformer* hh, const char* name, const float* data, int64_t numel) {
+    Cf* h = reinterpret_cast<Cf*>(hh);
+    PF_REQUIRE(h && name && data && name[0] != '#', "conformer_set_tensor: null");
+    return h->tt.set(name, data, numel);
+}
+int pf_conformer_missing(const pf_conformer* hh) {
+    const Cf* h = reinterpret_cast<const Cf*>(hh);
+    if (!h) return -1;
+    int n = 0;
+    for (auto& kv : h->tt.t) if (!kv.second.set && kv.first.find('#') == std::string::npos) ++n;
+    return n;
+}
+int pf_conformer_set_precision(pf_conformer* hh, int32_t precision) {
+    Cf* h = reinterpret_cast<Cf*>(hh);
+    PF_REQUIRE(h && (precision == 0 || precision == 3), "conformer_set_precision: 0 (fp32) or 3 (f16x2)");
+    if (h->cfg.precision != precision) { h->cfg.precision = precision; h->prepared = ~0ull; }
+    return 0;
+}
+int32_t pf_conformer_num_frames(const pf_conformer* hh, int32_t n_frames, int32_t padded_frames) {
+    if (!hh || padded_frames < 7 || n_frames > padded_frames) return -1;
+    return Cf::out_len(n_frames, padded_frames);
+}
+int pf_conformer_forward(pf_conformer* hh, const float* feats, const int32_t* lens_host, int32_t B, int32_t Tin, float* out,
+                         int32_t* out_lens_host, void* stream) {
+    Cf* h = reinterpret_cast<Cf*>(hh);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    PF_REQUIRE(h && feats && lens_host && out && B > 0, "conformer_forward: null/empty argument");
+    if (Tin < 7) { set_error("conformer: has " + std::to_string(Tin) + " frames and is too short for subsampling (it needs more than 7 frames)"); return -1; }
+    for (int b = 0; b < B; ++b) PF_REQUIRE(lens_host[b] >= 0 && lens_host[b] <= Tin, "conformer_forward: a length exceeds the padded length");
+    const int T = Cf::out_len(Tin, Tin);
+    if (T > 5000) { set_error("conformer: " + std::to_string(T) + " encoder frames; the positional tables hold 5000 (200 s)"); return -1; }
+    for (auto& kv : h->tt.t)
+        if (!kv.second.set && kv.first.find('#') == std::string::npos) { set_error("conformer: tensor not set: " + kv.first); return -3; }
+    int rc;
+    if (h->prepared != h->tt.version && (rc = h->prepare(s))) return rc;
+    return cf_forward(h, feats, lens_host, B, Tin, out, out_lens_host, s);
+}
+
+pf_tdecoder* pf_tdecoder_create(const pf_tdecoder_config* cfg) {
+    if (!cfg) { set_error("tdecoder: null config"); return nullptr; }
+    if (check_device()) return nullptr;
+    const pf_tdecoder_config& c = *cfg;
+    if (!(c.vocab_size > 0 && c.d_model > 0 && c.d_model % 64 == 0 && c.d_model <= 2048 && c.n_heads > 0 && c.d_model == 64 * c.n_heads &&
+          c.ffn_dim > 0 && c.ffn_dim % 32 == 0 && c.n_blocks > 0 && c.ln_eps > 0.f)) {
+        set_error("tdecoder: unsupported config (head dim 64, d_model % 64, ffn_dim % 32)");
+        return nullptr;
+    }
+    std::unique_ptr<Td> h(new Td());
+    h->cfg = c;
+    const int D = c.d_model, FF = c.ffn_dim, V = c.vocab_size;
+    int rc = 0;
+    auto lin = [&](const std::string& n, int o, int i) {
+        rc |= h->tt.add(n + "weight", (int64_t)o * i);
+        rc |= h->tt.add(n + "bias", o);
+    };
+    rc |= h->tt.add("embed.0.weight", (int64_t)V * D);
+    rc |= h->tt.add("pos_table", (int64_t)5000 * D);
+    for (int i = 0; i < c.n_blocks; ++i) {
+        const std::string p = dl(i);
+        for (const char* a : {"self_attn.", "src_attn."})
+            for (const char* n : {"linear_q.", "linear_k.", "linear_v.", "linear_out."}) lin(p + a + n, D, D);
+        lin(p + "feed_forward.w_1.", FF, D);
+        lin(p + "feed_forward.w_2.", D, FF);
+        for (const char* n : {"norm1.", "norm2.", "norm3."}) lin(p + n, D, 1);
+    }
+    lin("after_norm.", D, 1);
+    lin("output_layer.", V, D);
+    if (rc) return nullptr;
+    return reinterpret_cast<pf_tdecoder*>(h.release());
+}
+void pf_tdecoder_destroy(pf_tdecoder* h) { delete reinterpret_cast<Td*>(h); }
+int pf_tdecoder_set_tensor(pf_tdecoder* hh, const char* name, const float* data, int64_t numel) {
+    Td* h = reinterpret_cast<Td*>(hh);
+    PF_REQUIRE(h && name && data, "tdecoder_set_tensor: null");
+    return h->tt.set(name, data, numel);
+}
+int pf_tdecoder_missing(const pf_tdecoder* hh) {
+    const Td* h = reinterpret_cast<const Td*>(hh);
+    return h ? h->tt.missing() : -1;
+}
+int pf_tdecoder_begin(pf_tdecoder* hh, const float* memory, int32_t T, int32_t max_len, int32_t max_hyp, void* stream) {
+    Td* h = reinterpret_cast<Td*>(hh);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    PF_REQUIRE(h && memory && T > 0 && T <= 12000 && max_len > 0 && max_len <= 5000 && max_hyp > 0 && max_hyp <= 256,
+               "tdecoder_begin: 1 .. 12000 memory rows, 1 .. 5000 positions, 1 .. 256 hypotheses");
+    std::string first;
+    if (h->tt.missing(&first)) { set_error("tdecoder: tensor not set: " + first); return -3; }
+    const int D = h->cfg.d_model, L = h->cfg.n_blocks;
+    h->T = T; h->max_len = max_len; h->max_hyp = max_hyp; h->filled = 0; h->cur = 0;
+    const size_t n = (size_t)max_hyp;
+    if (h->ckv.ensure(sizeof(float) * (size_t)L * T * 2 * D) || h->cache.ensure(sizeof(float) * 2 * L * h->layer()) ||
+        h->x.ensure(sizeof(float) * n * D) || h->y.ensure(sizeof(float) * n * D) || h->xn.ensure(sizeof(float) * n * D) ||
+        h->q.ensure(sizeof(float) * n * D) || h->a.ensure(sizeof(float) * n * D) || h->hid.ensure(sizeof(float) * n * h->cfg.ffn_dim) ||
+        h->logits.ensure(sizeof(float) * n * h->cfg.vocab_size) || h->ids.ensure(sizeof(int32_t) * n) || h->par.ensure(sizeof(int32_t) * n))
+        return -2;
+    int rc;
+    for (int l = 0; l < L; ++l) {
+        const std::string p = dl(l) + "src_attn.";
+        float* kv = h->ckv.as<float>() + (size_t)l * T * 2 * D;
+        GemmArgs g{};
+        g.A = memory; g.lda = D; g.ldw = D; g.ldc = 2 * D; g.M = T; g.N = D; g.K = D;
+        g.W = h->tt.get(p + "linear_k.weight"); g.bias = h->tt.get(p + "linear_k.bias"); g.C = kv;
+        if ((rc = launch_gemm_f32(g, s))) return rc;
+        g.W = h->tt.get(p + "linear_v.weight"); g.bias = h->tt.get(p + "linear_v.bias"); g.C = kv + D;
+        if ((rc = launch_gemm_f32(g, s))) return rc;
+    }
+    return 0;
+}
+int pf_tdecoder_step(pf_tdecoder* hh, const int32_t* tokens_host, int32_t pos, int32_t n, float* logp, void* stream) {
+    Td* h = reinterpret_cast<Td*>(hh);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    PF_REQUIRE(h && tokens_host && logp && h->max_len > 0, "tdecoder_step: null argument or no begin()");
+    PF_REQUIRE(n > 0 && n <= h->max_hyp && pos >= 0 && pos < h->max_len && pos <= h->filled,
+               "tdecoder_step: n_hyp <= max_hyp, positions appended in order below max_len");
+    const pf_tdecoder_config& c = h->cfg;
+    const int D = c.d_model, FF = c.ffn_dim, V = c.vocab_size, H = c.n_heads, T = h->T;
+    for (int i = 0; i < n; ++i) PF_REQUIRE(tokens_host[i] >= 0 && tokens_host[i] < V, "tdecoder_step: token id outside the vocabulary");
+    if (upload_h2d(h->ids.p, tokens_host, sizeof(int32_t) * n, s)) return -2;
+    int rc;
+    StreamModeScope small_m;                         // every GEMM of the step has M = n_hyp rows: the weight-streaming kernel
+    float *x = h->x.as<float>(), *y = h->y.as<float>(), *xn = h->xn.as<float>(), *q = h->q.as<float>(), *a = h->a.as<float>(),
+          *hid = h->hid.as<float>();
+    if ((rc = launch_td_embed(h->tt.get("embed.0.weight"), h->ids.as<int>(), h->tt.get("pos_table") + (size_t)pos * D, sqrtf((float)D), x, n,
+                              D, s)))
+        return rc;
+    auto W = [&](const std::string& nme) { return h->tt.get(nme); };
+    const int ldslot = (int)h->slot();
+    for (int l = 0; l < c.n_blocks; ++l) {
+        const std::string p = dl(l);
+        float* cache = h->cache_of(h->cur, l);
+        if ((rc = layernorm(x, D, W(p + "norm1.weight"), W(p + "norm1.bias"), xn, D, n, D, D, c.ln_eps, s))) return rc;
+        if ((rc = gemm_simple(xn, D, W(p + "self_attn.linear_q.weight"), D, W(p + "self_attn.linear_q.bias"), q, D, n, D, D, 0, nullptr, 0,
+                              nullptr, 0, s)))
+            return rc;
+        if ((rc = gemm_simple(xn, D, W(p + "self_attn.linear_k.weight"), D, W(p + "self_attn.linear_k.bias"), cache + (size_t)pos * 2 * D, ldslot,
+                              n, D, D, 0, nullptr, 0, nullptr, 0, s)))
+            return rc;
+        if ((rc = gemm_simple(xn, D, W(p + "self_attn.linear_v.weight"), D, W(p + "self_attn.linear_v.bias"), cache + (size_t)pos * 2 * D + D,
+                              ldslot, n, D, D, 0, nullptr, 0, nullptr, 0, s)))
+            return rc;
+        if ((rc = launch_td_attention(q, cache, cache + D, 2 * D, h->slot(), pos + 1, n, H, a, s))) return rc;
+        if ((rc = gemm_simple(a, D, W(p + "self_attn.linear_out.weight"), D, W(p + "self_attn.linear_out.bias"), y, D, n, D, D, 0, x, D,
+                              nullptr, 0, s)))
+            return rc;
+        std::swap(x, y);
+        if ((rc = layernorm(x, D, W(p + "norm2.weight"), W(p + "norm2.bias"), xn, D, n, D, D, c.ln_eps, s))) return rc;
+        if ((rc = gemm_simple(xn, D, W(p + "src_attn.linear_q.weight"), D, W(p + "src_attn.linear_q.bias"), q, D, n, D, D, 0, nullptr, 0,
+                              nullptr, 0, s)))
+            return rc;
+        const float* kv = h->ckv.as<float>() + (size_t)l * T * 2 * D;
+        if ((rc = launch_td_attention(q, kv, kv + D, 2 * D, 0, T, n, H, a, s))) return rc;
+        if ((rc = gemm_simple(a, D, W(p + "src_attn.linear_out.weight"), D, W(p + "src_attn.linear_out.bias"), y, D, n, D, D, 0, x, D,
+                              nullptr, 0, s)))
+            return rc;
+        std::swap(x, y);
+        if ((rc = layernorm(x, D, W(p + "norm3.weight"), W(p + "norm3.bias"), xn, D, n, D, D, c.ln_eps, s))) return rc;
+        if ((rc = gemm_simple(xn, D, W(p + "feed_forward.w_1.weight"), D, W(p + "feed_forward.w_1.bias"), hid, FF, n, FF, D, 1, nullptr, 0,
+                              nullptr, 0, s)))
+            return rc;
+        if ((rc = gemm_simple(hid, FF, W(p + "feed_forward.w_2.weight"), FF, W(p + "feed_forward.w_2.bias"), y, D, n, D, FF, 0, x, D, nullptr,
+                              0, s)))
+            return rc;
+        std::swap(x, y);
+    }
+    if ((rc = layernorm(x, D, W("after_norm.weight"), W("after_norm.bias"), xn, D, n, D, D, c.ln_eps, s))) return rc;
+    if ((rc = gemm_simple(xn, D, W("output_layer.weight"), D, W("output_layer.bias"), h->logits.as<float>(), V, n, V, D, 0, nullptr, 0, nullptr,
+                          0, s)))
+        return rc;
+    if ((rc = launch_log_softmax(h->logits.as<float>(), V, logp, V, n, V, s))) return rc;
+    h->filled = std::max(h->filled, pos + 1);
+    return 0;
+}
+int pf_tdecoder_reorder(pf_tdecoder* hh, const int32_t* parents_host, int32_t n, void* stream) {
+    Td* h = reinterpret_cast<Td*>(hh);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    PF_REQUIRE(h && parents_host && h->max_len > 0 && n > 0 && n <= h->max_hyp, "tdecoder_reorder: null argument, no begin() or n_hyp > max_hyp");
+    for (int i = 0; i < n; ++i) PF_REQUIRE(parents_host[i] >= 0 && parents_host[i] < h->max_hyp, "tdecoder_reorder: parent slot out of range");
+    if (h->filled == 0) return 0;
+    if (upload_h2d(h->par.p, parents_host, sizeof(int32_t) * n, s)) return -2;
+    int rc;
+    if ((rc = launch_td_reorder(h->cache_of(h->cur, 0), h->cache_of(h->cur ^ 1, 0), h->par.as<int>(), n, h->cfg.n_blocks, h->layer(), h->slot(),
+                                h->filled, 2 * h->cfg.d_model, s)))
+        return rc;
+    h->cur ^= 1;
+    return 0;
+}
+
+// single-kernel hooks (tests)
+int pf_k_relpos_attention(const float* qkv, const float* P, const float* u, const float* v, const int32_t* klens_dev, int32_t B, int32_t T,
+                          int32_t H, int32_t legacy, float* out, void* stream) {
+    return launch_cf_relpos_attention(qkv, P, u, v, klens_dev, B, T, H, legacy, out, reinterpret_cast<hipStream_t>(stream));
+}
+int pf_k_conformer_glu_dw(const float* g, const float* dw, const float* dw_bias, const float* bn_scale, const float* bn_shift, int32_t B,
+                          int32_t T, int32_t D, int32_t taps, float* y, void* stream) {
+    return launch_cf_glu_dw(g, dw, dw_bias, bn_scale, bn_shift, B, T, D, taps, y, reinterpret_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

@@ -327,3 +327,53 @@ def emotion2vec_state_dict(seed: int, model) -> Dict[str, torch.Tensor]:
                 fan_in *= d
             sd[k] = torch.randn(shp, generator=g) * (1.0 / fan_in) ** 0.5
     return sd
+
+
+def conformer_conf(output_size: int = 128, attention_heads: int = 2, linear_units: int = 256, enc_blocks: int = 2, dec_blocks: int = 2,
+                   kernel: int = 15, macaron: bool = True, rel_pos_type: str = "legacy", vocab: int = 60, input_size: int = 80) -> dict:
+    """constructor arguments of a Conformer model (the layout of funasr/models/conformer/template.yaml) at a chosen size"""
+    enc = {"output_size": output_size, "attention_heads": attention_heads, "linear_units": linear_units, "num_blocks": enc_blocks,
+           "dropout_rate": 0.1, "positional_dropout_rate": 0.1, "attention_dropout_rate": 0.0, "input_layer": "conv2d",
+           "normalize_before": True, "pos_enc_layer_type": "rel_pos", "selfattention_layer_type": "rel_selfattn",
+           "activation_type": "swish", "macaron_style": macaron, "use_cnn_module": True, "cnn_module_kernel": kernel}
+    if rel_pos_type != "legacy":                       # the AISHELL yaml leaves it out: "legacy" is the constructor's default
+        enc["rel_pos_type"] = rel_pos_type
+    dec = {"attention_heads": attention_heads, "linear_units": linear_units, "num_blocks": dec_blocks, "dropout_rate": 0.1,
+           "positional_dropout_rate": 0.1, "self_attention_dropout_rate": 0.0, "src_attention_dropout_rate": 0.0}
+    return {"encoder": "ConformerEncoder", "encoder_conf": enc, "decoder": "TransformerDecoder", "decoder_conf": dec,
+            "ctc_weight": 0.3, "lsm_weight": 0.1, "length_normalized_loss": False, "input_size": input_size, "vocab_size": vocab}
+
+
+CONFORMER_AISHELL = dict(output_size=256, attention_heads=4, linear_units=2048, enc_blocks=12, dec_blocks=6, kernel=15, macaron=True,
+                         rel_pos_type="legacy", vocab=4234)
+
+
+def conformer_state_dict(seed: int, model) -> Dict[str, torch.Tensor]:
+    """synthetic weights in the layout of `model` (a Conformer module or the reference's): fan-in scaled convs / linears, LayerNorms
+    near identity, NON-trivial BatchNorm statistics (weight near 1, bias / running_mean off zero, running_var in [0.5, 2]),
+    relative-position biases of order 0.1, a token embedding of order 1 / sqrt(D)"""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for k, v in model.state_dict().items():
+        shp = tuple(v.shape)
+        if k.endswith("num_batches_tracked"):
+            sd[k] = torch.tensor(0, dtype=torch.long)
+        elif k.endswith("running_mean"):
+            sd[k] = 0.2 * torch.randn(shp, generator=g)
+        elif k.endswith("running_var"):
+            sd[k] = 0.5 + 1.5 * torch.rand(shp, generator=g)
+        elif k.endswith("pos_bias_u") or k.endswith("pos_bias_v"):
+            sd[k] = 0.1 * torch.randn(shp, generator=g)
+        elif k.endswith("embed.0.weight") and len(shp) == 2:
+            sd[k] = torch.randn(shp, generator=g) * (1.0 / shp[1]) ** 0.5
+        elif k.endswith("ctc_lo.weight") or k.endswith("output_layer.weight"):      # logits of order 4: few near-ties between classes
+            sd[k] = torch.randn(shp, generator=g) * 4.0 * (1.0 / shp[1]) ** 0.5
+        elif len(shp) == 1:
+            is_norm = "norm" in k
+            sd[k] = (1.0 + 0.2 * torch.randn(shp, generator=g)) if (is_norm and k.endswith("weight")) else 0.1 * torch.randn(shp, generator=g)
+        else:
+            fan_in = 1
+            for d in shp[1:]:
+                fan_in *= d
+            sd[k] = torch.randn(shp, generator=g) * (1.0 / fan_in) ** 0.5
+    return sd

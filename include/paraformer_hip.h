@@ -458,6 +458,68 @@ int32_t pf_emotion2vec_num_frames(const pf_emotion2vec* h, int64_t n_samples);
 int pf_emotion2vec_forward(pf_emotion2vec* h, const float* wav_dev, const int64_t* lens_host, int32_t B, float* feats_dev,
                            float* pooled_dev, float* probs_dev, void* stream);
 
+/* ---- Conformer encoder (funasr/models/conformer/encoder.py ConformerEncoder: Conv2dSubsampling, relative-position self-attention
+ * in its "legacy" and "latest" forms, macaron feed-forwards, the GLU / depthwise / BatchNorm / Swish convolution module; head dim 64,
+ * pre-LayerNorm). Tensor names are the reference's state_dict keys below `encoder.`: "embed.conv.0.weight", "embed.out.0.weight",
+ * "encoders.0.self_attn.linear_pos.weight", "encoders.0.self_attn.pos_bias_u", "encoders.0.conv_module.norm.running_mean",
+ * "encoders.0.norm_final.weight", "after_norm.bias", ... plus "pos_table": the positional table built on the host exactly as the
+ * reference builds it ([5000, D] for legacy: row m = position 4999 - m; [9999, D] for latest: row k = position 4999 - k).
+ * The forward takes the ZERO-PADDED feature batch and computes every row of it, as the reference does: a clip's frames and its
+ * output length depend on the batch's padded length (the mask rule x_mask[:, :, :-2:2][:, :, :-2:2]).
+ * precision 0: every GEMM on the exact-f32 MFMA; 3: the block GEMMs on the fp16 MFMA with two-plane operands (exponents from
+ * a-priori bounds of the weights only); the subsampling GEMMs, linear_pos, attention, convs and LayerNorms are fp32 in both. */
+typedef struct pf_conformer pf_conformer;
+typedef struct pf_conformer_config {
+    int32_t input_dim, d_model, n_heads, ffn_dim, n_blocks, kernel_size;
+    int32_t macaron;              /* 1: macaron pair of feed-forwards (ff_scale 0.5) */
+    int32_t legacy;               /* 1: LegacyRelPositionalEncoding / LegacyRelPositionMultiHeadedAttention (rel_pos_type "legacy") */
+    int32_t precision;            /* 0 fp32, 3 f16x2 */
+    float ln_eps;
+} pf_conformer_config;
+pf_conformer* pf_conformer_create(const pf_conformer_config* cfg);
+void pf_conformer_destroy(pf_conformer* h);
+int pf_conformer_set_tensor(pf_conformer* h, const char* name, const float* data, int64_t numel);
+int pf_conformer_missing(const pf_conformer* h);
+int pf_conformer_set_precision(pf_conformer* h, int32_t precision);
+/* encoder frames of a clip of n_frames features inside a batch padded to padded_frames (-1: padded_frames < 7 or n_frames > padded_frames) */
+int32_t pf_conformer_num_frames(const pf_conformer* h, int32_t n_frames, int32_t padded_frames);
+/* feats_dev [B, Tin, input_dim] zero-padded, lens_host[b] valid frames -> out_dev [B, T, d_model] with T = num_frames(Tin, Tin),
+ * out_lens_host[b] (optional) = num_frames(lens_host[b], Tin). Fails when Tin < 7 or T > 5000. No sync. */
+int pf_conformer_forward(pf_conformer* h, const float* feats_dev, const int32_t* lens_host, int32_t B, int32_t Tin, float* out_dev,
+                         int32_t* out_lens_host, void* stream);
+
+/* ---- Transformer decoder, one autoregressive step for all running hypotheses of a beam (funasr/models/transformer/decoder.py
+ * TransformerDecoder.forward_one_step / batch_score: embed x sqrt(D) + sinusoid, pre-LN self-attention over the hypothesis' own
+ * prefix, cross-attention over the utterance's encoder memory, ReLU feed-forward, after_norm, output layer, log-softmax; head dim 64).
+ * Tensor names are the reference's keys below `decoder.` ("embed.0.weight", "decoders.0.src_attn.linear_k.weight", "after_norm.weight",
+ * "output_layer.bias", ...) plus "pos_table" [5000, D] (row p = the sinusoid of position p, built on the host as the reference does).
+ * State on the device: the cross-attention K / V of every layer (computed once by begin) and a self-attention K / V cache per layer
+ * and hypothesis slot. All GEMMs of a step are the fp32 small-M weight-streaming kernel. */
+typedef struct pf_tdecoder pf_tdecoder;
+typedef struct pf_tdecoder_config {
+    int32_t vocab_size, d_model, n_heads, ffn_dim, n_blocks;
+    float ln_eps;
+} pf_tdecoder_config;
+pf_tdecoder* pf_tdecoder_create(const pf_tdecoder_config* cfg);
+void pf_tdecoder_destroy(pf_tdecoder* h);
+int pf_tdecoder_set_tensor(pf_tdecoder* h, const char* name, const float* data, int64_t numel);
+int pf_tdecoder_missing(const pf_tdecoder* h);
+/* a new utterance: memory_dev [T, d_model]; caches for max_hyp slots of max_len positions are (re)set. No sync. */
+int pf_tdecoder_begin(pf_tdecoder* h, const float* memory_dev, int32_t T, int32_t max_len, int32_t max_hyp, void* stream);
+/* slot k < n_hyp gets token tokens_host[k] at position pos (positions are appended in order: pos <= positions filled so far)
+ * -> logp_dev [n_hyp, vocab_size] log-probabilities of the next token. No sync. */
+int pf_tdecoder_step(pf_tdecoder* h, const int32_t* tokens_host, int32_t pos, int32_t n_hyp, float* logp_dev, void* stream);
+/* slot k < n_hyp takes the cache of slot parents_host[k] (a gather on the device; a parent may repeat or be dropped). No sync. */
+int pf_tdecoder_reorder(pf_tdecoder* h, const int32_t* parents_host, int32_t n_hyp, void* stream);
+
+/* single-kernel hooks of the two above (tests): the relative-position attention (qkv_dev [B T, 3 D] q | k | v, P_dev [T or 2 T - 1, D],
+ * u_dev / v_dev [H, 64], klens_dev [B] -> out_dev [B T, D]; see csrc/conformer.h) and the GLU + depthwise conv + BatchNorm + Swish
+ * row kernel (g_dev [B T, 2 D], dw_dev [D, taps], BatchNorm folded to scale / shift [D] -> y_dev [B T, D]) */
+int pf_k_relpos_attention(const float* qkv_dev, const float* P_dev, const float* u_dev, const float* v_dev, const int32_t* klens_dev, int32_t B,
+                          int32_t T, int32_t H, int32_t legacy, float* out_dev, void* stream);
+int pf_k_conformer_glu_dw(const float* g_dev, const float* dw_dev, const float* dw_bias_dev, const float* bn_scale_dev,
+                          const float* bn_shift_dev, int32_t B, int32_t T, int32_t D, int32_t taps, float* y_dev, void* stream);
+
 typedef struct pf_ctc pf_ctc;
 pf_ctc* pf_ctc_create(int32_t d_model, int32_t vocab_size);
 void pf_ctc_destroy(pf_ctc* c);
