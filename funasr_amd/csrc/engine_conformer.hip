@@ -6,7 +6,7 @@
 //   conv0 + ReLU into the even / odd time-row buffers -> conv1 as THREE accumulating GEMMs over overlapping strided views
 //   (element r = t (F2 + 1) + f of the output reads the contiguous 3 C floats at 2 C r of even[t], odd[t], even[t + 1]: lda = 2 C,
 //   K = 3 C, no im2col; one output column in F2 + 1 is waste) + ReLU -> the output linear over rows of (F2 + 1) C floats (weight
-//   permuted, zero for the waste column) -> x sqrt(D) into [B T, D] rows -> blocks: [macaron FFN] -> LayerNorm, q / k / v and
+//   permuted, zero for the waste column; K in slices of 1024, see cf_forward) -> x sqrt(D) into [B T, D] rows -> blocks: [macaron FFN] -> LayerNorm, q / k / v and
 //   linear_pos GEMMs, relative-position attention, linear_out (+ residual) -> LayerNorm, pointwise-1, GLU + depthwise + BatchNorm
 //   + Swish, pointwise-2 (+ residual) -> FFN -> norm_final; after_norm.
 // ff_scale = 0.5 of the macaron pair is folded into w_2 and its bias at load (an exact scaling), so the residual rides in the GEMM.
@@ -27,6 +27,8 @@ using namespace pf;
 
 namespace {
 
+constexpr int LIN_K_SLICE = 1024;      // K extent of one launch of the subsampling's output linear (a multiple of the GEMM's 32)
+
 struct CfBlockX { int e_ffm_in = 0, e_ffm_h = 0, e_mha_in = 0, e_att = 0, e_conv_in = 0, e_cm = 0, e_ff_in = 0, e_ff_h = 0; };
 
 struct Cf {
@@ -34,7 +36,7 @@ struct Cf {
     TensorTable tt;
     unsigned long long prepared = ~0ull;
     std::vector<CfBlockX> bx;
-    DevBuf bn, even, odd, ya, yb, lin, xa, xb, xn, qkv, P, att, hid, planes, klens;
+    DevBuf bn, even, odd, ya, yb, lin, lin2, xa, xb, xn, qkv, P, att, hid, planes, klens;
 
     int C() const { return cfg.d_model; }
     int F1() const { return (cfg.input_dim - 3) / 2 + 1; }
@@ -184,7 +186,8 @@ int cf_forward(Cf* h, const float* feats, const int32_t* lens, int B, int Tin, f
     const size_t M = (size_t)B * T, Mc = (size_t)B * NE * (f2 + 1), EO = (size_t)B * NE * FP * C, SL = (size_t)2 * FP * C;
     const int nP = c.legacy ? T : 2 * T - 1;
     if (h->even.ensure(sizeof(float) * (EO + SL)) || h->odd.ensure(sizeof(float) * (EO + SL)) || h->ya.ensure(sizeof(float) * Mc * C) ||
-        h->yb.ensure(sizeof(float) * Mc * C) || h->lin.ensure(sizeof(float) * (size_t)B * NE * D) || h->xa.ensure(sizeof(float) * M * D) ||
+        h->yb.ensure(sizeof(float) * Mc * C) || h->lin.ensure(sizeof(float) * (size_t)B * NE * D) ||
+        h->lin2.ensure(sizeof(float) * (size_t)B * NE * D) || h->xa.ensure(sizeof(float) * M * D) ||
         h->xb.ensure(sizeof(float) * M * D) || h->xn.ensure(sizeof(float) * M * D) || h->qkv.ensure(sizeof(float) * M * 3 * D) ||
         h->P.ensure(sizeof(float) * (size_t)nP * D) || h->att.ensure(sizeof(float) * M * D) ||
         h->hid.ensure(sizeof(float) * M * std::max(FF, 2 * D)) || h->klens.ensure(sizeof(int32_t) * B))
@@ -202,12 +205,23 @@ int cf_forward(Cf* h, const float* feats, const int32_t* lens, int B, int Tin, f
     if ((rc = cf_gemm(h, false, odd, 2 * C, (int)Mc, 3 * C, "#conv1.tap1", C, nullptr, ya, yb, C, 0, 0, s))) return rc;
     if ((rc = cf_gemm(h, false, even + (size_t)FP * C, 2 * C, (int)Mc, 3 * C, "#conv1.tap2", C, nullptr, yb, ya, C, 0, 0, s))) return rc;
     if ((rc = launch_cf_act(ya, Mc * C, 0, s))) return rc;
-    if ((rc = cf_gemm(h, false, ya, (f2 + 1) * C, B * NE, (f2 + 1) * C, "#embed.out", D, h->tt.get("embed.out.0.bias"), nullptr,
-                      h->lin.as<float>(), D, 0, 0, s)))
-        return rc;
+    // The output linear sums (F2 + 1) C terms per element (2560 at 80 features and C = 128, 8192 at 256 features). One fp32 fma chain of
+    // that length drifts several times further from the exact sum than a blocked CPU GEMM does, so K goes in slices of 1024: a
+    // slice's chain starts at zero and the running sum rides in as the addend of the next launch (ping-pong, no in-place addend).
+    float *lin = h->lin.as<float>(), *lin_prev = h->lin2.as<float>();
+    const int Kl = (f2 + 1) * C;
+    for (int k0 = 0; k0 < Kl; k0 += LIN_K_SLICE) {
+        GemmArgs g{};
+        g.A = ya + k0; g.lda = Kl; g.W = h->tt.get("#embed.out") + k0; g.ldw = Kl;
+        g.bias = k0 == 0 ? h->tt.get("embed.out.0.bias") : nullptr;
+        g.R1 = k0 == 0 ? nullptr : lin_prev; g.ldr1 = D;
+        g.C = lin; g.ldc = D; g.M = B * NE; g.N = D; g.K = std::min(LIN_K_SLICE, Kl - k0);
+        if ((rc = launch_gemm_f32(g, s))) return rc;
+        std::swap(lin, lin_prev);
+    }
     float* x = h->xa.as<float>();
     float* y = h->xb.as<float>();
-    if ((rc = launch_cf_scale_rows(h->lin.as<float>(), NE, x, B, T, D, sqrtf((float)D), s))) return rc;
+    if ((rc = launch_cf_scale_rows(lin_prev, NE, x, B, T, D, sqrtf((float)D), s))) return rc;
     const float* pos = h->tt.get("pos_table") + (c.legacy ? (size_t)0 : (size_t)(5000 - T) * D);
     float *xn = h->xn.as<float>(), *qkv = h->qkv.as<float>(), *Pm = h->P.as<float>(), *att = h->att.as<float>(), *hid = h->hid.as<float>();
     const int Mi = (int)M;

@@ -1,6 +1,7 @@
 """Conformer, CPU side: registry, the reference's state-dict names and shapes, refused options, the float64 oracle against the
 reference's recorded float64 outputs (tests/golden/conformer_<variant>.npz, written by tools/make_golden_conformer.py), and the
 host beam search driven by the oracle's decoder against the reference's recorded n-best."""
+import functools
 import json
 import os
 
@@ -180,3 +181,62 @@ def test_host_beam_search_with_the_oracle_decoder_returns_the_references_nbest(n
             d = abs(h.score - float(g[f"nbest_score_w{w}_{r}"]))
             print(f"{name} w={w} rank {r}: score {h.score:.6f} |d| {d:.2e} (bar {8 * float(g['gap_nbest_score']):.2e})")
             assert d <= 8 * float(g["gap_nbest_score"]), (name, w, r, d)
+
+
+# ------------------------------------------------------------------------------------------------ beam 10 on a random utterance
+BEAM10_SEED, BEAM10_WEIGHTS, BEAM10_TOP = 21, (0.0, 0.3), 3
+
+
+@functools.lru_cache(maxsize=None)
+def beam10_setup(seed=BEAM10_SEED):
+    """conf, weights, the float64 oracle encoder's output of a 383-frame random clip rounded to float32 (95 frames) and the CTC
+    log-probabilities of that memory in float64: what every stepper of the beam-10 searches shares, so that only the decoder differs"""
+    conf = synth.conformer_conf(vocab=60)
+    model = Conformer(**conf)
+    sd = synth.conformer_state_dict(seed, model)
+    feats = torch.randn(1, 383, 80, generator=torch.Generator().manual_seed(seed))
+    sd64 = O.cast(sd)
+    enc, olens = O.encoder(sd64, conf["encoder_conf"], feats.double(), [383])
+    assert olens == [95]
+    memory = enc[0].float()
+    ctc_logp = O.ctc_log_softmax(sd64, memory.double()).numpy()
+    return conf, sd, memory, ctc_logp, model.sos, model.eos
+
+
+def beam10_search(stepper, w, dtype, seed=BEAM10_SEED):
+    conf, sd, memory, ctc_logp, sos, eos = beam10_setup(seed)
+    bs = BeamSearchTransformer(beam_size=10, vocab_size=60, sos=sos, eos=eos, ctc_weight=w)
+    return bs(stepper, memory.shape[0], ctc_logp, dtype=dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def beam10_oracle_nbest(seed=BEAM10_SEED):
+    """{(w, "f64" | "f32"): n-best of the search driven by the oracle's stepper in that dtype}"""
+    conf, sd, memory, ctc_logp, sos, eos = beam10_setup(seed)
+    out = {}
+    for w in BEAM10_WEIGHTS:
+        out[w, "f64"] = beam10_search(O.DecoderStepper(O.cast(sd), conf["decoder_conf"], memory.double()), w, torch.float64, seed)
+        out[w, "f32"] = beam10_search(O.DecoderStepper(O.cast(sd, torch.float32), conf["decoder_conf"], memory), w, torch.float32, seed)
+    return out
+
+
+def beam10_reference_agrees_with_itself(seed=BEAM10_SEED):
+    """the precondition of the device comparison: the float32 and the float64 oracle searches return the same top-3 ids for both
+    weights and no score sits on the CTC scorer's log-zero. Returns max |score32 - score64| over the compared hypotheses."""
+    nb = beam10_oracle_nbest(seed)
+    gap = 0.0
+    for w in BEAM10_WEIGHTS:
+        h64, h32 = nb[w, "f64"][:BEAM10_TOP], nb[w, "f32"][:BEAM10_TOP]
+        assert len(h64) == BEAM10_TOP and len(h32) == BEAM10_TOP, (w, len(h64), len(h32))
+        for r, (a, b) in enumerate(zip(h64, h32)):
+            print(f"beam 10 seed {seed} w={w} rank {r}: len {len(a.yseq)}, score64 {a.score:.6f}, |score32 - score64| {abs(a.score - b.score):.3e}")
+            assert a.yseq == b.yseq, (w, r)
+            assert a.score >= -1e6 and b.score >= -1e6, (w, r, a.score, b.score)
+            gap = max(gap, abs(a.score - b.score))
+    return gap
+
+
+def test_beam_10_oracle_searches_agree_in_float32_and_float64():
+    """beam 10 over 95 frames with the two oracle steppers only: the reference must agree with itself (same top-3 ids in float32 and
+    float64 for CTC weights 0 and 0.3, every score finite-sized) before the device search is compared with it"""
+    beam10_reference_agrees_with_itself()

@@ -60,11 +60,51 @@ def test_conv_subsampling_against_the_oracle(cuda, mode):
     _check("subsampling " + mode, out, e64, _maxd(e32, e64), FACTOR[mode])
 
 
-@pytest.mark.parametrize("taps", [15, 31])
-def test_convolution_module_row_kernel_against_the_oracle(cuda, taps):
+def _encoder_model(cuda, conf, seed, mode):
+    m = Conformer(**conf)
+    sd = synth.conformer_state_dict(seed, m)
+    m.load_state_dict(sd, strict=True)
+    return m.to(cuda).set_precision(mode), sd
+
+
+@pytest.mark.parametrize("mode", ["fp32", "f16x2"])
+@pytest.mark.parametrize("enc_blocks", [0, 1])
+@pytest.mark.parametrize("input_size", [7, 83, 256])
+def test_subsampling_feature_counts_and_shortest_batches_against_the_oracle(cuda, input_size, enc_blocks, mode):
+    """the feature counts at the ends of the accepted range and an odd one (F1 = 3 / 41 / 127 conv0 columns in a pitch of 4 / 42 /
+    128, F2 = 1 / 20 / 63 plus the waste column), batches of 7 .. 15 frames (T = 1, 1, 1, 2, 2, 3: the `NE = T + 1` even / odd
+    rows and the slack behind them are most of the buffer), ragged lengths down to 1. With one block (31 taps) T = 1 .. 3 also goes
+    through the relative-position attention and through the depthwise conv with a 15-row halo on each side. Then the shape order on
+    one handle: long, shortest, long."""
+    conf = synth.conformer_conf(input_size=input_size, enc_blocks=enc_blocks, kernel=31)
+    m, sd = _encoder_model(cuda, conf, 3, mode)
+    sd64, sd32 = O.cast(sd), O.cast(sd, torch.float32)
+    g = torch.Generator().manual_seed(input_size)
+    expect = {7: (1, [1, 1, 1]), 8: (1, [1, 1, 1]), 10: (1, [1, 1, 1]), 11: (2, [2, 2, 1]), 14: (2, [2, 2, 1]), 15: (3, [3, 3, 1])}
+    for Tin in (7, 8, 10, 11, 14, 15):
+        lens = [Tin, max(1, Tin - 4), 1]
+        feats = torch.randn(3, Tin, input_size, generator=g)
+        for b, n in enumerate(lens):
+            feats[b, n:] = 0
+        out, olens = m.encode(feats.to(cuda), lens)
+        e64, ol = O.encoder(sd64, conf["encoder_conf"], feats.double(), lens)
+        e32, _ = O.encoder(sd32, conf["encoder_conf"], feats, lens)
+        assert bool(torch.isfinite(e64).all()) and (e64.shape[1], ol) == expect[Tin]
+        assert out.shape == e64.shape and olens.tolist() == ol
+        _check(f"subsampling F={input_size} blocks={enc_blocks} {mode} Tin={Tin}", out, e64, _maxd(e32, e64), FACTOR[mode])
+    long = torch.randn(3, 141, input_size, generator=g).to(cuda)
+    short = torch.randn(1, 7, input_size, generator=g).to(cuda)
+    a, _ = m.encode(long, [141] * 3)
+    s, _ = m.encode(short, [7])
+    b, _ = m.encode(long, [141] * 3)
+    assert torch.equal(a, b)
+    fresh, _ = _encoder_model(cuda, conf, 3, mode)
+    assert torch.equal(s, fresh.encode(short, [7])[0])
+
+
+def _glu_dw_against_the_oracle(cuda, B, T, D, taps):
     lib = _lib.load()
     g = torch.Generator().manual_seed(taps)
-    B, T, D = 2, 37, 128
     x = torch.randn(B, T, 2 * D, generator=g)
     sd = {"depthwise_conv.weight": torch.randn(D, 1, taps, generator=g) / taps ** 0.5, "depthwise_conv.bias": 0.1 * torch.randn(D, generator=g),
           "norm.weight": 1 + 0.2 * torch.randn(D, generator=g), "norm.bias": 0.1 * torch.randn(D, generator=g),
@@ -86,17 +126,27 @@ def test_convolution_module_row_kernel_against_the_oracle(cuda, taps):
                                          taps, y.data_ptr(), _stream()), "pf_k_conformer_glu_dw")
     torch.cuda.synchronize()
     r64 = ref(torch.float64)
-    _check(f"glu_dw taps {taps}", y, r64, _maxd(ref(torch.float32), r64), 4.0)
+    _check(f"glu_dw B={B} T={T} D={D} taps {taps}", y, r64, _maxd(ref(torch.float32), r64), 4.0)
 
 
-@pytest.mark.parametrize("legacy", [True, False])
-@pytest.mark.parametrize("T,klens", [(1, [1, 1]), (2, [2, 1]), (77, [77, 50]), (129, [129, 128]), (200, [33, 200])])
-def test_relpos_attention_against_the_oracle(cuda, legacy, T, klens):
-    """T not a multiple of any tile, ragged key lengths, T = 1 and 2 (no wrapped entries there), wave tiles (32 queries) and a
-    workgroup tile (128) whose boundary lies on the diagonal"""
+@pytest.mark.parametrize("taps", [15, 31])
+def test_convolution_module_row_kernel_against_the_oracle(cuda, taps):
+    _glu_dw_against_the_oracle(cuda, 2, 37, 128, taps)
+
+
+@pytest.mark.parametrize("taps", [1, 3, 15, 31])
+@pytest.mark.parametrize("D", [64, 192])
+@pytest.mark.parametrize("T", [1, 2, 32, 33, 37])
+def test_convolution_module_row_kernel_short_rows_tile_edges_and_tap_counts(cuda, T, D, taps):
+    """T shorter than the halo (1, 2: every tap but the centre ones reads padding), T on and one past the 32-row workgroup tile,
+    one tap (no halo at all) and three, one and three 64-channel column blocks, three sequences; same reference, same bar"""
+    _glu_dw_against_the_oracle(cuda, 3, T, D, taps)
+
+
+def _relpos_against_the_oracle(cuda, legacy, H, T, klens):
     lib = _lib.load()
     g = torch.Generator().manual_seed(T)
-    B, H, dk = 2, 2, 64
+    B, dk = len(klens), 64
     D = H * dk
     nP = T if legacy else 2 * T - 1
     qkv = torch.randn(B, T, 3 * D, generator=g)
@@ -107,14 +157,35 @@ def test_relpos_attention_against_the_oracle(cuda, legacy, T, klens):
         q, k, vv = [t.to(dt).reshape(B, T, H, dk) for t in qkv.split(D, dim=-1)]
         return O.relpos_attention(q, k, vv, P.to(dt).view(nP, H, dk), u.to(dt), v.to(dt), klens, legacy)
 
-    dev = [t.contiguous().to(cuda) for t in (qkv, P, u, v)]
+    # one row of NaN behind the last sequence: the K / V staging clamps the rows of a partial tile to the last valid key, and a
+    # kernel that read one row further instead (a masked row: probability 0) would turn the last sequence's output into NaN
+    guard = torch.full((1, 3 * D), float("nan"))
+    dev = [t.contiguous().to(cuda) for t in (torch.cat([qkv.reshape(B * T, 3 * D), guard]), P, u, v)]
     kl = torch.tensor(klens, dtype=torch.int32, device=cuda)
     out = torch.empty(B, T, D, device=cuda)
     _lib.check(lib.pf_k_relpos_attention(dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr(), dev[3].data_ptr(), kl.data_ptr(), B, T, H,
                                          int(legacy), out.data_ptr(), _stream()), "pf_k_relpos_attention")
     torch.cuda.synchronize()
     r64 = ref(torch.float64)
-    _check(f"relpos legacy={legacy} T={T}", out, r64, max(_maxd(ref(torch.float32), r64), 1e-7), 4.0)
+    _check(f"relpos legacy={legacy} H={H} T={T} klens={klens}", out, r64, max(_maxd(ref(torch.float32), r64), 1e-7), 4.0)
+
+
+@pytest.mark.parametrize("legacy", [True, False])
+@pytest.mark.parametrize("T,klens", [(1, [1, 1]), (2, [2, 1]), (77, [77, 50]), (129, [129, 128]), (200, [33, 200])])
+def test_relpos_attention_against_the_oracle(cuda, legacy, T, klens):
+    """T not a multiple of any tile, ragged key lengths, T = 1 and 2 (no wrapped entries there), wave tiles (32 queries) and a
+    workgroup tile (128) whose boundary lies on the diagonal"""
+    _relpos_against_the_oracle(cuda, legacy, 2, T, klens)
+
+
+@pytest.mark.parametrize("legacy", [True, False])
+@pytest.mark.parametrize("T,klens", [(32, [32, 31, 1]), (33, [33, 32, 1]), (64, [64, 33, 32]), (128, [128, 97, 64]), (160, [160, 129, 128]),
+                                      (33, [1, 32, 33])])
+def test_relpos_attention_on_the_tile_edges_with_four_heads(cuda, legacy, T, klens):
+    """T and key lengths exactly on, one below and one above the 32-key tile, the 32-query wave tile and the 128-query workgroup
+    tile; four heads (the head index enters every pointer), three sequences; T = 33 also with the full-length sequence last, so that
+    the row behind its one-key second tile is the guard row"""
+    _relpos_against_the_oracle(cuda, legacy, 4, T, klens)
 
 
 def test_relpos_attention_with_every_key_masked_gives_zero_rows(cuda):
