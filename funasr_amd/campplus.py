@@ -66,6 +66,7 @@ def _res_block(cin: int, c: int, stride: int) -> Holder:
 @tables.register("model_classes", "CAMPPlus")
 class CAMPPlus(HipModule):
     _prefix = "pf_campplus"
+    _push_buffers = True      # BatchNorm running statistics: the library folds them into the convs
 
     def __init__(self, feat_dim: int = 80, embedding_size: int = 192, growth_rate: int = 32, bn_size: int = 4,
                  init_channels: int = 128, config_str: str = "batchnorm-relu", memory_efficient: bool = True,
@@ -132,17 +133,6 @@ class CAMPPlus(HipModule):
 
     def _after_create(self, lib, handle):
         _lib.check(lib.pf_campplus_set_max_batch(handle, self.max_batch), "pf_campplus_set_max_batch")
-
-    def _push_weights(self, lib):
-        """parameters AND BatchNorm running statistics (the library folds them into the convs)"""
-        with torch.cuda.device(self._handle_device):
-            for name, t in list(self.named_parameters()) + list(self.named_buffers()):
-                if name.endswith("num_batches_tracked"):
-                    continue
-                t = t.detach().to(dtype=torch.float32).contiguous()
-                _lib.check(lib.pf_campplus_set_tensor(self._handle, name.encode(), t.data_ptr(), t.numel()),
-                           f"pf_campplus_set_tensor({name})")
-            torch.cuda.synchronize()
 
     def set_max_batch(self, n: int):
         """chunks per launch sequence (never changes a result). The workspace is about 31 KB per frame of a sub-batch (4.6 MB per

@@ -28,15 +28,11 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .hip_module import Holder, HipModule, ParamHolder, layer_norm, linear, stream_ptr
+from .hip_module import Holder, HipModule, ParamHolder, _truthy, layer_norm, linear, stream_ptr
 from .register import tables
 
 _PRECISIONS = {"fp32": 0, "f16x2": 3}
 MAX_LEN = 5000            # rows of the reference's positional tables (PositionalEncoding(max_len=5000))
-
-
-def _truthy(v) -> bool:
-    return v in (True, 1, "true", "True")
 
 
 def _sinusoid(position: torch.Tensor, d_model: int) -> torch.Tensor:
@@ -105,26 +101,10 @@ def _ffn(D: int, units: int) -> Holder:
     return f
 
 
-class _PushAll(HipModule):
-    """parameters AND buffers (BatchNorm's running statistics) reach the handle, then the host-built positional table"""
-
-    def _pos_table(self) -> torch.Tensor:  # pragma: no cover - abstract
-        raise NotImplementedError
-
-    def _push_weights(self, lib):
-        set_tensor = getattr(lib, self._prefix + "_set_tensor")
-        named = list(self.named_parameters()) + [(n, b) for n, b in self.named_buffers() if not n.endswith("num_batches_tracked")]
-        named.append(("pos_table", self._pos_table()))
-        with torch.cuda.device(self._handle_device):
-            for name, p in named:
-                t = p.detach().to(device=self._handle_device, dtype=torch.float32).contiguous()
-                _lib.check(set_tensor(self._handle, name.encode(), t.data_ptr(), t.numel()), f"{self._prefix}_set_tensor({name})")
-            torch.cuda.synchronize()
-
-
 @tables.register("encoder_classes", "ConformerEncoder")
-class ConformerEncoder(_PushAll):
+class ConformerEncoder(HipModule):
     _prefix = "pf_conformer"
+    _push_buffers = True
 
     def __init__(self, input_size: int, output_size: int = 256, attention_heads: int = 4, linear_units: int = 2048, num_blocks: int = 6,
                  dropout_rate: float = 0.1, positional_dropout_rate: float = 0.1, attention_dropout_rate: float = 0.0,
@@ -205,8 +185,8 @@ class ConformerEncoder(_PushAll):
     def output_size(self) -> int:
         return self._output_size
 
-    def _pos_table(self) -> torch.Tensor:
-        return self.pos_table
+    def _extra_tensors(self):
+        return (("pos_table", self.pos_table),)
 
     def pos_rows(self, T: int) -> torch.Tensor:
         """the rows of the table a forward over T encoder frames reads (a view)"""
@@ -253,7 +233,7 @@ class ConformerEncoder(_PushAll):
 
 
 @tables.register("decoder_classes", "TransformerDecoder")
-class TransformerDecoder(_PushAll):
+class TransformerDecoder(HipModule):
     _prefix = "pf_tdecoder"
 
     def __init__(self, vocab_size: int, encoder_output_size: int, attention_heads: int = 4, linear_units: int = 2048, num_blocks: int = 6,
@@ -290,8 +270,8 @@ class TransformerDecoder(_PushAll):
         self.decoders = layers
         self._memory = None
 
-    def _pos_table(self) -> torch.Tensor:
-        return abs_pos_table(self.d_model)
+    def _extra_tensors(self):
+        return (("pos_table", abs_pos_table(self.d_model)),)
 
     def _make_config(self):
         c = _lib.pf_tdecoder_config()

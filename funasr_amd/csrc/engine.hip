@@ -128,6 +128,30 @@ int gemm_simple(const float* A, int lda, const float* W, int ldw, const float* b
     g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.relu = relu;
     return gemm(g, s);
 }
+int gemm_two_mode(TensorTable& tt, DevBuf& planes, bool x2, const float* A, int width, size_t a_rows, int lda, int M, int K,
+                  const std::string& wname, int N, const float* bias, const float* R1, float* C, int ldc, int e_a, int relu, hipStream_t s) {
+    if (!x2) {
+        GemmArgs g{};
+        g.A = A; g.lda = lda; g.W = tt.get(wname); g.ldw = K; g.bias = bias; g.relu = relu;
+        g.R1 = R1; g.ldr1 = N; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
+        return launch_gemm_f32(g, s);
+    }
+    const size_t plane = a_rows * (size_t)width;
+    if (planes.ensure(sizeof(unsigned short) * 2 * plane)) return -2;
+    unsigned short* P = planes.as<unsigned short>();
+    int rc;
+    if ((rc = launch_split2(A, width, P, width, plane, (int)a_rows, width, pow2f(e_a), s))) return rc;
+    int ew = 0;
+    const unsigned short* W2 = tt.get_split2(wname, N, K, &ew, s);
+    if (!W2) return -2;
+    Gemm2Args g{};
+    g.A = P; g.lda = lda; g.a_plane = plane;
+    g.W = W2; g.ldw = K; g.w_plane = (size_t)N * K;
+    g.oscale = pow2f(-(e_a + ew));
+    g.bias = bias; g.relu = relu; g.R1 = R1; g.ldr1 = N; g.C = C; g.ldc = ldc;
+    g.M = M; g.N = N; g.K = K;
+    return launch_gemm_f16x2(g, s);
+}
 int layernorm(const float* x, int ldx, const float* g, const float* b, float* y, int ldy, int M, int D,
                      int Dpad, float eps, hipStream_t s) {
     ProfScope ps(PROF_LN, 8.0 * M * (double)D, s);   // bytes: read + write

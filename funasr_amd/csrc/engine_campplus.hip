@@ -34,38 +34,10 @@ struct Campplus {
     pf_frontend* fe = nullptr;
     int max_batch = 256;
     unsigned long long folded_version = ~0ull;
-    std::map<std::string, std::unique_ptr<DevBuf>> dw;        // folded / repacked weights
     std::vector<DenseW> layers;
     DevBuf fa, fb, fc, h, mask, wav, feats, starts, valid;
     ~Campplus() { if (fe) pf_frontend_destroy(fe); }
 
-    std::vector<float> host(const std::string& name) {
-        const Tensor& t = tt.t.at(name);
-        std::vector<float> v((size_t)t.numel);
-        if (hipMemcpy(v.data(), t.d, sizeof(float) * v.size(), hipMemcpyDeviceToHost) != hipSuccess) v.clear();
-        return v;
-    }
-    const float* put(const std::string& key, const std::vector<float>& v) {
-        std::unique_ptr<DevBuf>& b = dw[key];
-        if (!b) b.reset(new DevBuf());
-        if (b->ensure(sizeof(float) * v.size())) return nullptr;
-        if (hipMemcpy(b->p, v.data(), sizeof(float) * v.size(), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-        return b->as<float>();
-    }
-    const float* get(const std::string& key) const { return dw.at(key)->as<float>(); }
-    // scale / shift of BatchNorm `p` (p + "weight|bias|running_mean|running_var"; affine = false: weight 1, bias 0)
-    bool bn(const std::string& p, bool affine, std::vector<double>& sc, std::vector<double>& sh) {
-        std::vector<float> rm = host(p + "running_mean"), rv = host(p + "running_var"), w, b;
-        if (affine) { w = host(p + "weight"); b = host(p + "bias"); }
-        if (rm.empty() || rv.empty() || (affine && (w.empty() || b.empty()))) return false;
-        sc.resize(rm.size()); sh.resize(rm.size());
-        for (size_t i = 0; i < rm.size(); ++i) {
-            const double s = (affine ? (double)w[i] : 1.0) / std::sqrt((double)rv[i] + (double)cfg.bn_eps);
-            sc[i] = s;
-            sh[i] = (affine ? (double)b[i] : 0.0) - (double)rm[i] * s;
-        }
-        return true;
-    }
     int fold();
 };
 
@@ -77,22 +49,23 @@ struct Campplus {
 // conv2d [O, I, 3, 3] (+ BN) -> [O, 9 I (+ I2)] tap-major, the shortcut's 1x1 conv (+ its BN) appended; bias = both BN shifts
 int Campplus::fold() {
     const int mc = cfg.m_channels;
+    const double eps = (double)cfg.bn_eps;
     auto conv3 = [&](const std::string& key, const std::string& conv, const std::string& bnp, const std::string& sc_conv,
                      const std::string& sc_bn, int I) -> int {
-        std::vector<float> w = host(conv + "weight");
+        std::vector<float> w = tt.host(conv + "weight");
         std::vector<double> s, t, s2, t2;
-        CAM_CHECK(!w.empty() && bn(bnp, true, s, t));
+        CAM_CHECK(!w.empty() && tt.bn_fold(bnp, true, eps, s, t));
         const int O = mc, I2 = sc_conv.empty() ? 0 : mc, K = 9 * I + I2;
         std::vector<float> wp((size_t)O * K), bias(O);
         std::vector<float> ws;
-        if (I2) { ws = host(sc_conv + "weight"); CAM_CHECK(!ws.empty() && bn(sc_bn, true, s2, t2)); }
+        if (I2) { ws = tt.host(sc_conv + "weight"); CAM_CHECK(!ws.empty() && tt.bn_fold(sc_bn, true, eps, s2, t2)); }
         for (int o = 0; o < O; ++o) {
             for (int i = 0; i < I; ++i)
                 for (int tap = 0; tap < 9; ++tap) wp[(size_t)o * K + tap * I + i] = (float)(w[((size_t)o * I + i) * 9 + tap] * s[o]);
             for (int i = 0; i < I2; ++i) wp[(size_t)o * K + 9 * I + i] = (float)(ws[(size_t)o * I2 + i] * s2[o]);
             bias[o] = (float)(t[o] + (I2 ? t2[o] : 0.0));
         }
-        CAM_CHECK(put(key + ".w", wp) && put(key + ".b", bias));
+        CAM_CHECK(!tt.put_derived(key + ".w", wp) && !tt.put_derived(key + ".b", bias));
         return 0;
     };
     int rc;
@@ -107,9 +80,9 @@ int Campplus::fold() {
     // TDNN [C0, mc * F, 5]: input channel c * F + f of the reference is column f * mc + c of the head's output
     {
         const int F = cfg.feat_dim / 8, Cin = mc * F, O = cfg.init_channels;
-        std::vector<float> w = host("xvector.tdnn.linear.weight");
+        std::vector<float> w = tt.host("xvector.tdnn.linear.weight");
         std::vector<double> s, t;
-        CAM_CHECK(!w.empty() && bn("xvector.tdnn.nonlinear.batchnorm.", true, s, t));
+        CAM_CHECK(!w.empty() && tt.bn_fold("xvector.tdnn.nonlinear.batchnorm.", true, eps, s, t));
         std::vector<float> wp((size_t)O * 5 * Cin), bias(O);
         for (int o = 0; o < O; ++o) {
             for (int c = 0; c < mc; ++c)
@@ -118,12 +91,12 @@ int Campplus::fold() {
                         wp[(size_t)o * 5 * Cin + k * Cin + f * mc + c] = (float)(w[((size_t)o * Cin + c * F + f) * 5 + k] * s[o]);
             bias[o] = (float)t[o];
         }
-        CAM_CHECK(put("tdnn.w", wp) && put("tdnn.b", bias));
+        CAM_CHECK(!tt.put_derived("tdnn.w", wp) && !tt.put_derived("tdnn.b", bias));
     }
     auto pre = [&](const std::string& key, const std::string& bnp) -> int {
         std::vector<double> s, t;
-        CAM_CHECK(bn(bnp, true, s, t));
-        CAM_CHECK(put(key + ".sc", std::vector<float>(s.begin(), s.end())) && put(key + ".sh", std::vector<float>(t.begin(), t.end())));
+        CAM_CHECK(tt.bn_fold(bnp, true, eps, s, t));
+        CAM_CHECK(!tt.put_derived(key + ".sc", std::vector<float>(s.begin(), s.end())) && !tt.put_derived(key + ".sh", std::vector<float>(t.begin(), t.end())));
         return 0;
     };
     const int G = cfg.growth_rate, BNC = cfg.bn_size * cfg.growth_rate;
@@ -134,9 +107,9 @@ int Campplus::fold() {
             const std::string p = "xvector.block" + std::to_string(blk + 1) + ".tdnnd" + std::to_string(i + 1) + ".";
             const int Cin = ch + i * G;
             if ((rc = pre(p + "pre", p + "nonlinear1.batchnorm."))) return rc;
-            std::vector<float> w1 = host(p + "linear1.weight"), wl = host(p + "cam_layer.linear_local.weight");
+            std::vector<float> w1 = tt.host(p + "linear1.weight"), wl = tt.host(p + "cam_layer.linear_local.weight");
             std::vector<double> s, t;
-            CAM_CHECK(!w1.empty() && !wl.empty() && bn(p + "nonlinear2.batchnorm.", true, s, t));
+            CAM_CHECK(!w1.empty() && !wl.empty() && tt.bn_fold(p + "nonlinear2.batchnorm.", true, eps, s, t));
             std::vector<float> w1p((size_t)BNC * Cin), b1(BNC), wlp((size_t)G * 3 * BNC);
             for (int o = 0; o < BNC; ++o) {
                 for (int c = 0; c < Cin; ++c) w1p[(size_t)o * Cin + c] = (float)(w1[(size_t)o * Cin + c] * s[o]);
@@ -145,10 +118,10 @@ int Campplus::fold() {
             for (int o = 0; o < G; ++o)
                 for (int c = 0; c < BNC; ++c)
                     for (int k = 0; k < 3; ++k) wlp[(size_t)o * 3 * BNC + k * BNC + c] = wl[((size_t)o * BNC + c) * 3 + k];
-            CAM_CHECK(put(p + "w1", w1p) && put(p + "b1", b1) && put(p + "wl", wlp));
+            CAM_CHECK(!tt.put_derived(p + "w1", w1p) && !tt.put_derived(p + "b1", b1) && !tt.put_derived(p + "wl", wlp));
             DenseW d;
-            d.pre_sc = get(p + "pre.sc"); d.pre_sh = get(p + "pre.sh");
-            d.w1 = get(p + "w1"); d.b1 = get(p + "b1"); d.wl = get(p + "wl");
+            d.pre_sc = tt.get(p + "pre.sc"); d.pre_sh = tt.get(p + "pre.sh");
+            d.w1 = tt.get(p + "w1"); d.b1 = tt.get(p + "b1"); d.wl = tt.get(p + "wl");
             d.cw1 = tt.get(p + "cam_layer.linear1.weight"); d.cb1 = tt.get(p + "cam_layer.linear1.bias");
             d.cw2 = tt.get(p + "cam_layer.linear2.weight"); d.cb2 = tt.get(p + "cam_layer.linear2.bias");
             layers.push_back(d);
@@ -161,13 +134,13 @@ int Campplus::fold() {
     if ((rc = pre("out", "xvector.out_nonlinear.batchnorm."))) return rc;
     {
         const int E = cfg.embedding_size, K = 2 * ch;
-        std::vector<float> w = host("xvector.dense.linear.weight"), wt((size_t)K * E);
+        std::vector<float> w = tt.host("xvector.dense.linear.weight"), wt((size_t)K * E);
         std::vector<double> s, t;
-        CAM_CHECK(!w.empty() && bn("xvector.dense.nonlinear.batchnorm.", false, s, t));
+        CAM_CHECK(!w.empty() && tt.bn_fold("xvector.dense.nonlinear.batchnorm.", false, eps, s, t));
         for (int o = 0; o < E; ++o)
             for (int k = 0; k < K; ++k) wt[(size_t)k * E + o] = w[(size_t)o * K + k];
-        CAM_CHECK(put("dense.wt", wt) && put("dense.sc", std::vector<float>(s.begin(), s.end())) &&
-                  put("dense.sh", std::vector<float>(t.begin(), t.end())));
+        CAM_CHECK(!tt.put_derived("dense.wt", wt) && !tt.put_derived("dense.sc", std::vector<float>(s.begin(), s.end())) &&
+                  !tt.put_derived("dense.sh", std::vector<float>(t.begin(), t.end())));
     }
     folded_version = tt.version;
     return 0;
@@ -180,7 +153,7 @@ int head_conv(Campplus* c, const std::string& key, const float* A, int Cin, int 
     CamGemmArgs g{};
     g.conv2d = 1;
     g.M = n * T * Fo; g.N = mc; g.K = 9 * Cin + (A2 ? mc : 0);
-    g.W = c->get(key + ".w"); g.ldw = g.K; g.bias = c->get(key + ".b");
+    g.W = c->tt.get(key + ".w"); g.ldw = g.K; g.bias = c->tt.get(key + ".b");
     g.C = out; g.ldc = mc; g.R = R; g.ldr = mc; g.relu = 1;
     g.A = A; g.lda = Cin; g.Cin = Cin; g.T = T; g.Fin = Fin; g.Fo = Fo; g.fstride = fstride;
     g.A2 = A2; g.Cin2 = A2 ? mc : 0; g.Fin2 = Fin2; g.fstride2 = fstride2;
@@ -232,7 +205,7 @@ int run_net(Campplus* c, const float* feats, int n, int T, float* emb, hipStream
     // ---- tdnn: B [n T, F3 mc] -> A cols 0..C0
     const int C0 = c->cfg.init_channels;
     int ld = C0 + kLayers[0] * G;
-    if ((rc = tdnn_gemm(B, F3 * mc, T, T2, F3 * mc, 5, 2, 1, 2, c->get("tdnn.w"), C0, c->get("tdnn.b"), 1, nullptr, nullptr,
+    if ((rc = tdnn_gemm(B, F3 * mc, T, T2, F3 * mc, 5, 2, 1, 2, c->tt.get("tdnn.w"), C0, c->tt.get("tdnn.b"), 1, nullptr, nullptr,
                         nullptr, A, ld, n, s)))
         return rc;
     // ---- D-TDNN blocks; buffers: block 1 in A, block 2 in C, block 3 in A, transit 3 out in C
@@ -255,20 +228,19 @@ int run_net(Campplus* c, const float* feats, int n, int T, float* emb, hipStream
         const int out_ch = ch / 2;
         const int nld = blk < 2 ? out_ch + kLayers[blk + 1] * G : out_ch;
         const std::string p = "xvector.transit" + std::to_string(blk + 1) + ".";
-        if ((rc = tdnn_gemm(cur, ld, T2, T2, ch, 1, 1, 1, 0, c->tt.get(p + "linear.weight"), out_ch, nullptr, 0, c->get(p + "pre.sc"),
-                            c->get(p + "pre.sh"), nullptr, nxt, nld, n, s)))
+        if ((rc = tdnn_gemm(cur, ld, T2, T2, ch, 1, 1, 1, 0, c->tt.get(p + "linear.weight"), out_ch, nullptr, 0, c->tt.get(p + "pre.sc"),
+                            c->tt.get(p + "pre.sh"), nullptr, nxt, nld, n, s)))
             return rc;
         ch = out_ch;
         ld = nld;
         float* tmp = cur; cur = nxt; nxt = tmp;
     }
-    return launch_cam_pool_dense(cur, T2, ch, n, c->get("out.sc"), c->get("out.sh"), c->get("dense.wt"), c->cfg.embedding_size,
-                                 c->get("dense.sc"), c->get("dense.sh"), emb, s);
+    return launch_cam_pool_dense(cur, T2, ch, n, c->tt.get("out.sc"), c->tt.get("out.sh"), c->tt.get("dense.wt"), c->cfg.embedding_size,
+                                 c->tt.get("dense.sc"), c->tt.get("dense.sh"), emb, s);
 }
 
 int ready(Campplus* c) {
-    std::string first;
-    if (c->tt.missing(&first)) { set_error("campplus: tensor not set: " + first); return -3; }
+    if (c->tt.require_all("campplus")) return -3;
     if (c->folded_version != c->tt.version) return c->fold();
     return 0;
 }

@@ -36,7 +36,7 @@ struct Cf {
     TensorTable tt;
     unsigned long long prepared = ~0ull;
     std::vector<CfBlockX> bx;
-    DevBuf bn, even, odd, ya, yb, lin, lin2, xa, xb, xn, qkv, P, att, hid, planes, klens;
+    DevBuf even, odd, ya, yb, lin, lin2, xa, xb, xn, qkv, P, att, hid, planes, klens;
 
     int C() const { return cfg.d_model; }
     int F1() const { return (cfg.input_dim - 3) / 2 + 1; }
@@ -45,22 +45,8 @@ struct Cf {
     static int sub(int L, int n) { const int m = std::min(L, n - 2); return m <= 0 ? 0 : (m + 1) / 2; }
     // encoder frames of a length-L clip inside a batch padded to n frames (the mask rule x_mask[:, :, :-2:2][:, :, :-2:2])
     static int out_len(int L, int n) { const int n1 = sub(n, n); return sub(sub(L, n), n1); }
-    std::vector<float> host(const std::string& name) {
-        const Tensor& t = tt.t.at(name);
-        std::vector<float> v((size_t)t.numel);
-        if (hipMemcpy(v.data(), t.d, sizeof(float) * v.size(), hipMemcpyDeviceToHost) != hipSuccess) v.clear();
-        return v;
-    }
-    int derived(const std::string& name, const std::vector<float>& v) {
-        if (!tt.t.count(name) && tt.add(name, (int64_t)v.size())) return -2;
-        return tt.set(name.c_str(), v.data(), (int64_t)v.size());
-    }
-    float ln_bound(const std::string& p) {
-        std::vector<float> g = host(p + "weight"), b = host(p + "bias");
-        float mg = 0.f, mb = 0.f;
-        for (float v : g) mg = fmaxf(mg, fabsf(v));
-        for (float v : b) mb = fmaxf(mb, fabsf(v));
-        return sqrtf((float)cfg.d_model) * mg + mb;
+    int ln_bound(const std::string& p, float* out, hipStream_t s) {
+        return TensorTable::dev_ln_bound(tt.get(p + "weight"), tt.get(p + "bias"), cfg.d_model, out, s);
     }
     int prepare(hipStream_t s);
 };
@@ -70,48 +56,47 @@ std::string blk(int i) { return "encoders." + std::to_string(i) + "."; }
 int Cf::prepare(hipStream_t s) {
     const int C = cfg.d_model, D = cfg.d_model, f2 = F2(), NB = cfg.n_blocks, K = cfg.kernel_size, FF = cfg.ffn_dim;
     {   // conv1 [C, C, 3, 3] -> per time tap dt the [C, 3 C] matrix W_dt[co][df C + ci]
-        std::vector<float> w = host("embed.conv.2.weight");
+        std::vector<float> w = tt.host("embed.conv.2.weight");
         if (w.empty()) { set_error("conformer: weight copy failed"); return -2; }
         for (int dt = 0; dt < 3; ++dt) {
             std::vector<float> m((size_t)C * 3 * C);
             for (int co = 0; co < C; ++co)
                 for (int df = 0; df < 3; ++df)
                     for (int ci = 0; ci < C; ++ci) m[((size_t)co * 3 + df) * C + ci] = w[(((size_t)co * C + ci) * 3 + dt) * 3 + df];
-            if (derived("#conv1.tap" + std::to_string(dt), m)) return -2;
+            if (tt.put_derived("#conv1.tap" + std::to_string(dt), m)) return -2;
         }
         // output linear [D, C F2] (feature c F2 + f) -> [D, (F2 + 1) C] (feature f C + c, zero for the waste column)
-        std::vector<float> l = host("embed.out.0.weight");
+        std::vector<float> l = tt.host("embed.out.0.weight");
         std::vector<float> m((size_t)D * (f2 + 1) * C, 0.f);
         for (int d = 0; d < D; ++d)
             for (int c = 0; c < C; ++c)
                 for (int f = 0; f < f2; ++f) m[((size_t)d * (f2 + 1) + f) * C + c] = l[((size_t)d * C + c) * f2 + f];
-        if (derived("#embed.out", m)) return -2;
+        if (tt.put_derived("#embed.out", m)) return -2;
     }
     std::vector<float> bnv((size_t)NB * 2 * D);
     bx.assign(NB, CfBlockX());
     if (cfg.precision == 3) tt.drop_bf16();
     for (int i = 0; i < NB; ++i) {
         const std::string p = blk(i);
-        std::vector<float> g = host(p + "conv_module.norm.weight"), b = host(p + "conv_module.norm.bias"),
-                           mu = host(p + "conv_module.norm.running_mean"), var = host(p + "conv_module.norm.running_var");
-        if (g.empty() || b.empty() || mu.empty() || var.empty()) { set_error("conformer: weight copy failed"); return -2; }
+        std::vector<double> sc, sh;
+        if (!tt.bn_fold(p + "conv_module.norm.", true, 1e-5, sc, sh)) { set_error("conformer: weight copy failed"); return -2; }
         for (int c = 0; c < D; ++c) {
-            const double sc = (double)g[c] / std::sqrt((double)var[c] + 1e-5);
-            bnv[((size_t)i * 2) * D + c] = (float)sc;
-            bnv[((size_t)i * 2 + 1) * D + c] = (float)((double)b[c] - (double)mu[c] * sc);
+            bnv[((size_t)i * 2) * D + c] = (float)sc[c];
+            bnv[((size_t)i * 2 + 1) * D + c] = (float)sh[c];
         }
         for (const char* ff : {"feed_forward.", "feed_forward_macaron."}) {
             if (!cfg.macaron) break;
-            std::vector<float> w = host(p + ff + "w_2.weight"), bb = host(p + ff + "w_2.bias");
+            std::vector<float> w = tt.host(p + ff + "w_2.weight"), bb = tt.host(p + ff + "w_2.bias");
             for (float& v : w) v *= 0.5f;
             for (float& v : bb) v *= 0.5f;
-            if (derived(p + ff + "w_2.weight#half", w) || derived(p + ff + "w_2.bias#half", bb)) return -2;
+            if (tt.put_derived(p + ff + "w_2.weight#half", w) || tt.put_derived(p + ff + "w_2.bias#half", bb)) return -2;
         }
         if (cfg.precision != 3) continue;
         CfBlockX& x = bx[i];
-        float hb = 0.f;
+        float hb = 0.f, mb, cb;
         auto ffn = [&](const std::string& f, const std::string& norm, int* e_in, int* e_h) {
-            const float nb = ln_bound(p + norm);
+            float nb;
+            if (ln_bound(p + norm, &nb, s)) return -2;
             *e_in = exp_for_bound(nb);
             if (TensorTable::dev_linear_bound(tt.get(p + f + "w_1.weight"), FF, D, D, tt.get(p + f + "w_1.bias"), nb, &hb, s)) return -2;
             *e_h = exp_for_bound(hb);
@@ -119,17 +104,17 @@ int Cf::prepare(hipStream_t s) {
         };
         if (cfg.macaron && ffn("feed_forward_macaron.", "norm_ff_macaron.", &x.e_ffm_in, &x.e_ffm_h)) return -2;
         if (ffn("feed_forward.", "norm_ff.", &x.e_ff_in, &x.e_ff_h)) return -2;
-        const float mb = ln_bound(p + "norm_mha.");
+        if (ln_bound(p + "norm_mha.", &mb, s)) return -2;
         x.e_mha_in = exp_for_bound(mb);
         if (TensorTable::dev_linear_bound(tt.get(p + "self_attn.linear_v.weight"), D, D, D, tt.get(p + "self_attn.linear_v.bias"), mb, &hb, s))
             return -2;
         x.e_att = exp_for_bound(hb);
-        const float cb = ln_bound(p + "norm_conv.");
+        if (ln_bound(p + "norm_conv.", &cb, s)) return -2;
         x.e_conv_in = exp_for_bound(cb);
         if (TensorTable::dev_linear_bound(tt.get(p + "conv_module.pointwise_conv1.weight"), D, D, D,
                                           tt.get(p + "conv_module.pointwise_conv1.bias"), cb, &hb, s))
             return -2;
-        std::vector<float> dw = host(p + "conv_module.depthwise_conv.weight"), db = host(p + "conv_module.depthwise_conv.bias");
+        std::vector<float> dw = tt.host(p + "conv_module.depthwise_conv.weight"), db = tt.host(p + "conv_module.depthwise_conv.bias");
         float zb = 0.f;
         for (int c = 0; c < D; ++c) {
             float l1 = 0.f;
@@ -138,38 +123,9 @@ int Cf::prepare(hipStream_t s) {
         }
         x.e_cm = exp_for_bound(zb);
     }
-    if (NB > 0) {
-        if (bn.ensure(sizeof(float) * bnv.size())) return -2;
-        PF_HIP_TRY(hipMemcpy(bn.p, bnv.data(), sizeof(float) * bnv.size(), hipMemcpyHostToDevice));
-    }
+    if (NB > 0 && tt.put_derived("#bn", bnv)) return -2;
     prepared = tt.version;
     return 0;
-}
-
-// C[M, N] = A[M, K] (row stride lda) W^T + bias (+ R1) (ReLU before the addend); x2: two-plane fp16 operands with A's exponent e_a
-int cf_gemm(Cf* h, bool x2, const float* A, int lda, int M, int K, const std::string& wname, int N, const float* bias, const float* R1,
-            float* C, int ldc, int e_a, int relu, hipStream_t s) {
-    if (!x2) {
-        GemmArgs g{};
-        g.A = A; g.lda = lda; g.W = h->tt.get(wname); g.ldw = K; g.bias = bias; g.relu = relu;
-        g.R1 = R1; g.ldr1 = N; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
-        return launch_gemm_f32(g, s);
-    }
-    const size_t plane = (size_t)M * K;
-    if (h->planes.ensure(sizeof(unsigned short) * 2 * plane)) return -2;
-    unsigned short* P = h->planes.as<unsigned short>();
-    int rc;
-    if ((rc = launch_split2(A, lda, P, K, plane, M, K, pow2f(e_a), s))) return rc;
-    int ew = 0;
-    const unsigned short* W2 = h->tt.get_split2(wname, N, K, &ew, s);
-    if (!W2) return -2;
-    Gemm2Args g{};
-    g.A = P; g.lda = K; g.a_plane = plane;
-    g.W = W2; g.ldw = K; g.w_plane = (size_t)N * K;
-    g.oscale = pow2f(-(e_a + ew));
-    g.bias = bias; g.relu = relu; g.R1 = R1; g.ldr1 = N; g.C = C; g.ldc = ldc;
-    g.M = M; g.N = N; g.K = K;
-    return launch_gemm_f16x2(g, s);
 }
 
 int cf_forward(Cf* h, const float* feats, const int32_t* lens, int B, int Tin, float* out, int32_t* olens, hipStream_t s) {
@@ -194,6 +150,11 @@ int cf_forward(Cf* h, const float* feats, const int32_t* lens, int B, int Tin, f
         return -2;
     if (upload_h2d(h->klens.p, kl.data(), sizeof(int32_t) * B, s)) return -2;
     int rc;
+    // C[M, N] = A[M, K] (row stride lda) W^T + bias (+ R1); the subsampling's overlapping views (lda = 2 C, K = 3 C) are fp32 only
+    auto gm = [&](bool x2_, const float* A, int lda, int M_, int K, const std::string& w, int N, const float* bias, const float* R1, float* Cc,
+                  int ldc, int e_a) {
+        return gemm_two_mode(h->tt, h->planes, x2_, A, K, (size_t)M_, lda, M_, K, w, N, bias, R1, Cc, ldc, e_a, 0, s);
+    };
     float *even = h->even.as<float>(), *odd = h->odd.as<float>(), *ya = h->ya.as<float>(), *yb = h->yb.as<float>();
     PF_HIP_TRY(hipMemsetAsync(even + EO, 0, sizeof(float) * SL, s));
     PF_HIP_TRY(hipMemsetAsync(odd + EO, 0, sizeof(float) * SL, s));
@@ -201,9 +162,9 @@ int cf_forward(Cf* h, const float* feats, const int32_t* lens, int B, int Tin, f
                               odd, s)))
         return rc;
     const float* cb = h->tt.get("embed.conv.2.bias");
-    if ((rc = cf_gemm(h, false, even, 2 * C, (int)Mc, 3 * C, "#conv1.tap0", C, cb, nullptr, ya, C, 0, 0, s))) return rc;
-    if ((rc = cf_gemm(h, false, odd, 2 * C, (int)Mc, 3 * C, "#conv1.tap1", C, nullptr, ya, yb, C, 0, 0, s))) return rc;
-    if ((rc = cf_gemm(h, false, even + (size_t)FP * C, 2 * C, (int)Mc, 3 * C, "#conv1.tap2", C, nullptr, yb, ya, C, 0, 0, s))) return rc;
+    if ((rc = gm(false, even, 2 * C, (int)Mc, 3 * C, "#conv1.tap0", C, cb, nullptr, ya, C, 0))) return rc;
+    if ((rc = gm(false, odd, 2 * C, (int)Mc, 3 * C, "#conv1.tap1", C, nullptr, ya, yb, C, 0))) return rc;
+    if ((rc = gm(false, even + (size_t)FP * C, 2 * C, (int)Mc, 3 * C, "#conv1.tap2", C, nullptr, yb, ya, C, 0))) return rc;
     if ((rc = launch_cf_act(ya, Mc * C, 0, s))) return rc;
     // The output linear sums (F2 + 1) C terms per element (2560 at 80 features and C = 128, 8192 at 256 features). One fp32 fma chain of
     // that length drifts several times further from the exact sum than a blocked CPU GEMM does, so K goes in slices of 1024: a
@@ -235,9 +196,9 @@ int cf_forward(Cf* h, const float* feats, const int32_t* lens, int B, int Tin, f
         auto ffn = [&](const std::string& f, const std::string& norm, int e_in, int e_h) {
             int r;
             if ((r = ln(p + norm, x, xn))) return r;
-            if ((r = cf_gemm(h, x2, xn, D, Mi, D, p + f + "w_1.weight", FF, h->tt.get(p + f + "w_1.bias"), nullptr, hid, FF, e_in, 0, s))) return r;
+            if ((r = gm(x2, xn, D, Mi, D, p + f + "w_1.weight", FF, h->tt.get(p + f + "w_1.bias"), nullptr, hid, FF, e_in))) return r;
             if ((r = launch_cf_act(hid, M * FF, 1, s))) return r;
-            if ((r = cf_gemm(h, x2, hid, FF, Mi, FF, p + f + "w_2.weight" + half, D, h->tt.get(p + f + "w_2.bias" + half), x, y, D, e_h, 0, s)))
+            if ((r = gm(x2, hid, FF, Mi, FF, p + f + "w_2.weight" + half, D, h->tt.get(p + f + "w_2.bias" + half), x, y, D, e_h)))
                 return r;
             std::swap(x, y);
             return 0;
@@ -247,28 +208,28 @@ int cf_forward(Cf* h, const float* feats, const int32_t* lens, int B, int Tin, f
         if ((rc = ln(p + "norm_mha.", x, xn))) return rc;
         const char* names[3] = {"self_attn.linear_q.", "self_attn.linear_k.", "self_attn.linear_v."};
         for (int j = 0; j < 3; ++j)
-            if ((rc = cf_gemm(h, x2, xn, D, Mi, D, p + names[j] + "weight", D, h->tt.get(p + names[j] + "bias"), nullptr, qkv + (size_t)j * D,
-                              3 * D, e.e_mha_in, 0, s)))
+            if ((rc = gm(x2, xn, D, Mi, D, p + names[j] + "weight", D, h->tt.get(p + names[j] + "bias"), nullptr, qkv + (size_t)j * D,
+                              3 * D, e.e_mha_in)))
                 return rc;
-        if ((rc = cf_gemm(h, false, pos, D, nP, D, p + "self_attn.linear_pos.weight", D, nullptr, nullptr, Pm, D, 0, 0, s))) return rc;
+        if ((rc = gm(false, pos, D, nP, D, p + "self_attn.linear_pos.weight", D, nullptr, nullptr, Pm, D, 0))) return rc;
         if ((rc = launch_cf_relpos_attention(qkv, Pm, h->tt.get(p + "self_attn.pos_bias_u"), h->tt.get(p + "self_attn.pos_bias_v"),
                                              h->klens.as<int>(), B, T, c.n_heads, c.legacy, att, s)))
             return rc;
-        if ((rc = cf_gemm(h, x2, att, D, Mi, D, p + "self_attn.linear_out.weight", D, h->tt.get(p + "self_attn.linear_out.bias"), x, y, D,
-                          e.e_att, 0, s)))
+        if ((rc = gm(x2, att, D, Mi, D, p + "self_attn.linear_out.weight", D, h->tt.get(p + "self_attn.linear_out.bias"), x, y, D,
+                          e.e_att)))
             return rc;
         std::swap(x, y);
         // convolution module
         if ((rc = ln(p + "norm_conv.", x, xn))) return rc;
-        if ((rc = cf_gemm(h, x2, xn, D, Mi, D, p + "conv_module.pointwise_conv1.weight", 2 * D, h->tt.get(p + "conv_module.pointwise_conv1.bias"),
-                          nullptr, hid, 2 * D, e.e_conv_in, 0, s)))
+        if ((rc = gm(x2, xn, D, Mi, D, p + "conv_module.pointwise_conv1.weight", 2 * D, h->tt.get(p + "conv_module.pointwise_conv1.bias"),
+                          nullptr, hid, 2 * D, e.e_conv_in)))
             return rc;
-        const float* bnp = h->bn.as<float>() + (size_t)i * 2 * D;
+        const float* bnp = h->tt.get("#bn") + (size_t)i * 2 * D;
         if ((rc = launch_cf_glu_dw(hid, h->tt.get(p + "conv_module.depthwise_conv.weight"), h->tt.get(p + "conv_module.depthwise_conv.bias"),
                                    bnp, bnp + D, B, T, D, c.kernel_size, att, s)))
             return rc;
-        if ((rc = cf_gemm(h, x2, att, D, Mi, D, p + "conv_module.pointwise_conv2.weight", D, h->tt.get(p + "conv_module.pointwise_conv2.bias"),
-                          x, y, D, e.e_cm, 0, s)))
+        if ((rc = gm(x2, att, D, Mi, D, p + "conv_module.pointwise_conv2.weight", D, h->tt.get(p + "conv_module.pointwise_conv2.bias"),
+                          x, y, D, e.e_cm)))
             return rc;
         std::swap(x, y);
         if ((rc = ffn("feed_forward.", "norm_ff.", e.e_ff_in, e.e_ff_h))) return rc;
@@ -351,15 +312,12 @@ pf_conformer* pf_conformer_create(const pf_conformer_config* cfg) {
 void pf_conformer_destroy(pf_conformer* h) { delete reinterpret_cast<Cf*>(h); }
 int pf_conformer_set_tensor(pf_conformer* hh, const char* name, const float* data, int64_t numel) {
     Cf* h = reinterpret_cast<Cf*>(hh);
-    PF_REQUIRE(h && name && data && name[0] != '#', "conformer_set_tensor: null");
+    PF_REQUIRE(h && name && data, "conformer_set_tensor: null");
     return h->tt.set(name, data, numel);
 }
 int pf_conformer_missing(const pf_conformer* hh) {
     const Cf* h = reinterpret_cast<const Cf*>(hh);
-    if (!h) return -1;
-    int n = 0;
-    for (auto& kv : h->tt.t) if (!kv.second.set && kv.first.find('#') == std::string::npos) ++n;
-    return n;
+    return h ? h->tt.missing() : -1;
 }
 int pf_conformer_set_precision(pf_conformer* hh, int32_t precision) {
     Cf* h = reinterpret_cast<Cf*>(hh);
@@ -380,9 +338,8 @@ int pf_conformer_forward(pf_conformer* hh, const float* feats, const int32_t* le
     for (int b = 0; b < B; ++b) PF_REQUIRE(lens_host[b] >= 0 && lens_host[b] <= Tin, "conformer_forward: a length exceeds the padded length");
     const int T = Cf::out_len(Tin, Tin);
     if (T > 5000) { set_error("conformer: " + std::to_string(T) + " encoder frames; the positional tables hold 5000 (200 s)"); return -1; }
-    for (auto& kv : h->tt.t)
-        if (!kv.second.set && kv.first.find('#') == std::string::npos) { set_error("conformer: tensor not set: " + kv.first); return -3; }
     int rc;
+    if ((rc = h->tt.require_all("conformer"))) return rc;
     if (h->prepared != h->tt.version && (rc = h->prepare(s))) return rc;
     return cf_forward(h, feats, lens_host, B, Tin, out, out_lens_host, s);
 }
@@ -434,8 +391,7 @@ int pf_tdecoder_begin(pf_tdecoder* hh, const float* memory, int32_t T, int32_t m
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     PF_REQUIRE(h && memory && T > 0 && T <= 12000 && max_len > 0 && max_len <= 5000 && max_hyp > 0 && max_hyp <= 256,
                "tdecoder_begin: 1 .. 12000 memory rows, 1 .. 5000 positions, 1 .. 256 hypotheses");
-    std::string first;
-    if (h->tt.missing(&first)) { set_error("tdecoder: tensor not set: " + first); return -3; }
+    if (h->tt.require_all("tdecoder")) return -3;
     const int D = h->cfg.d_model, L = h->cfg.n_blocks;
     h->T = T; h->max_len = max_len; h->max_hyp = max_hyp; h->filled = 0; h->cur = 0;
     const size_t n = (size_t)max_hyp;

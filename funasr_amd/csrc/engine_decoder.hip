@@ -111,23 +111,23 @@ int gemm2_simple(const unsigned short* A2, int lda, int M, int ea, const unsigne
 int dec_layer_x2(Decoder* d, DecLayerW& w, const std::string& p, bool attn, hipStream_t s) {
     if (w.x2_ready) return 0;
     const int D = d->cfg.d_model, F = d->cfg.ffn_dim;
-    float g, b;
-    if (TensorTable::dev_absmax(w.n1g, D, &g, s) || TensorTable::dev_absmax(w.n1b, D, &b, s)) return -2;
-    w.e_n1 = exp_for_bound(sqrtf((float)D) * g + b);
-    if (TensorTable::dev_absmax(w.fng, F, &g, s) || TensorTable::dev_absmax(w.fnb, F, &b, s)) return -2;
-    w.e_fn = exp_for_bound(sqrtf((float)F) * g + b);
+    float b;
+    if (TensorTable::dev_ln_bound(w.n1g, w.n1b, D, &b, s)) return -2;
+    w.e_n1 = exp_for_bound(b);
+    if (TensorTable::dev_ln_bound(w.fng, w.fnb, F, &b, s)) return -2;
+    w.e_fn = exp_for_bound(b);
     w.w1_2 = d->tt.get_split2(p + "feed_forward.w_1.weight", F, D, &w.ew_1, s);
     w.w2_2 = d->tt.get_split2(p + "feed_forward.w_2.weight", D, F, &w.ew_2, s);
     if (!w.w1_2 || !w.w2_2) return -2;
     if (attn) {
-        if (TensorTable::dev_absmax(w.n3g, D, &g, s) || TensorTable::dev_absmax(w.n3b, D, &b, s)) return -2;
-        w.e_n3 = exp_for_bound(sqrtf((float)D) * g + b);
+        if (TensorTable::dev_ln_bound(w.n3g, w.n3b, D, &b, s)) return -2;
+        w.e_n3 = exp_for_bound(b);
         w.q_2 = d->tt.get_split2(p + "src_attn.linear_q.weight", D, D, &w.ew_q, s);
         w.kv_2 = d->tt.get_split2(p + "src_attn.linear_k_v.weight", 2 * D, D, &w.ew_kv, s);
         w.o_2 = d->tt.get_split2(p + "src_attn.linear_out.weight", D, D, &w.ew_o, s);
         if (!w.q_2 || !w.kv_2 || !w.o_2) return -2;
         float bq;
-        if (TensorTable::dev_linear_bound(w.q_w, D, D, D, w.q_b, sqrtf((float)D) * g + b, &bq, s)) return -2;
+        if (TensorTable::dev_linear_bound(w.q_w, D, D, D, w.q_b, b, &bq, s)) return -2;
         w.e_q = exp_for_bound(bq * powf((float)(D / d->cfg.n_heads), -0.5f));
         if (TensorTable::dev_linear_bound(w.kv_w, D, D, D, nullptr, 1.f, &w.kv_l1b[0], s) ||
             TensorTable::dev_absmax(w.kv_b, D, &w.kv_l1b[1], s) ||
@@ -398,8 +398,7 @@ namespace pf {
 int predictor_alphas_enqueue(Predictor* p, int slot, const float* hidden, const int32_t* lens_host, int B, int T, hipStream_t s) {
     PF_REQUIRE(p && hidden && lens_host && B > 0 && T > 0 && (slot == 0 || slot == 1), "predictor_alphas: null/empty argument");
     for (int b = 0; b < B; ++b) PF_REQUIRE(lens_host[b] >= 1 && lens_host[b] <= T, "predictor_alphas: lens out of range");
-    std::string first;
-    if (p->tt.missing(&first)) { set_error("predictor: tensor not set: " + first); return -3; }
+    if (p->tt.require_all("predictor")) return -3;
     const pf_predictor_config& c = p->cfg;
     const int D = c.d_model, Te = T + 1;
     Predictor::CifState& S = p->st[slot];
@@ -525,8 +524,7 @@ int pf_predictor_timestamp(pf_predictor* ph, const float* hidden, const int32_t*
                "predictor_timestamp: null/empty argument");
     PF_REQUIRE(p->v3, "predictor_timestamp: the handle was not made by pf_predictor_create_v3");
     for (int b = 0; b < B; ++b) PF_REQUIRE(lens_host[b] >= 1 && lens_host[b] <= T, "predictor_timestamp: lens out of range");
-    std::string first;
-    if (p->tt.missing(&first)) { set_error("predictor: tensor not set: " + first); return -3; }
+    if (p->tt.require_all("predictor")) return -3;
     const pf_predictor_config& c = p->cfg;
     const int D = c.d_model, U = p->c3.upsample_times, taps = c.l_order + c.r_order + 1, Tu = T * U;
     const size_t M = (size_t)B * T;
@@ -1003,9 +1001,9 @@ static int decoder_forward_impl(Decoder* d, const float* memory, const int32_t* 
         const unsigned short* wv2 = d->tt.get_split2("output_layer.weight", V, D, &ew_v, s);
         if (!wv2) return -2;
         if (d->e_an == INT32_MIN) {
-            float g, b;
-            if (TensorTable::dev_absmax(d->tt.get("after_norm.weight"), D, &g, s) || TensorTable::dev_absmax(d->tt.get("after_norm.bias"), D, &b, s)) return -2;
-            d->e_an = exp_for_bound(sqrtf((float)D) * g + b);
+            float b;
+            if (TensorTable::dev_ln_bound(d->tt.get("after_norm.weight"), d->tt.get("after_norm.bias"), D, &b, s)) return -2;
+            d->e_an = exp_for_bound(b);
         }
         unsigned short* h2 = d->t16.as<unsigned short>();
         {
@@ -1068,8 +1066,7 @@ int pf_ctc_greedy(pf_ctc* ch, const float* hidden, int32_t M, int32_t* ids, floa
     Ctc* c = reinterpret_cast<Ctc*>(ch);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     PF_REQUIRE(c && hidden && M > 0, "ctc_greedy: null/empty");
-    std::string first;
-    if (c->tt.missing(&first)) { set_error("ctc: tensor not set: " + first); return -3; }
+    if (c->tt.require_all("ctc")) return -3;
     if (c->precision == 3 && ids && !logits && !g_stream_mode && c->d_model % 32 == 0) {
         const int D = c->d_model, V = c->vocab;
         int ew = 0, rc;

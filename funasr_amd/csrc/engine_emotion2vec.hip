@@ -31,8 +31,7 @@ struct E2v {
     int64_t max_samples = (int64_t)8 << 20;
     unsigned long long prepared = ~0ull;
     std::vector<std::string> blocks;                  // prefixes of the prenet and main blocks, in order
-    std::vector<float> h_slope, h_scale;              // per block: [H] slopes and clamped scales
-    DevBuf posw, slope, scale, mask;
+    DevBuf mask;
     bool mask_set = false;
     // f16x2: exponents of the GEMM A operands
     std::vector<int> e_conv;                          // input of conv layer l (l >= 1)
@@ -42,18 +41,8 @@ struct E2v {
 
     int D() const { return cfg.embed_dim; }
     int C() const { return cfg.vocab_size; }
-    std::vector<float> host(const std::string& name) {
-        const Tensor& t = tt.t.at(name);
-        std::vector<float> v((size_t)t.numel);
-        if (hipMemcpy(v.data(), t.d, sizeof(float) * v.size(), hipMemcpyDeviceToHost) != hipSuccess) v.clear();
-        return v;
-    }
-    float ln_bound(const std::string& p, int D) {
-        std::vector<float> g = host(p + "weight"), b = host(p + "bias");
-        float mg = 0.f, mb = 0.f;
-        for (float v : g) mg = fmaxf(mg, fabsf(v));
-        for (float v : b) mb = fmaxf(mb, fabsf(v));
-        return sqrtf((float)D) * mg + mb;
+    int ln_bound(const std::string& p, int D, float* out, hipStream_t s) {
+        return TensorTable::dev_ln_bound(tt.get(p + "weight"), tt.get(p + "bias"), D, out, s);
     }
     int prepare(hipStream_t s);
     // frames after conv layer l of an utterance of n samples (0: too short)
@@ -76,7 +65,7 @@ int E2v::prepare(hipStream_t s) {
     // positional conv weights [D, Cg, K] -> [G][K][Cg (in)][Cg (out)]
     std::vector<float> wp((size_t)cfg.conv_pos_depth * D * Cg * K);
     for (int l = 0; l < cfg.conv_pos_depth; ++l) {
-        std::vector<float> w = host(std::string(kA) + "relative_positional_encoder." + std::to_string(l + 1) + ".0.weight");
+        std::vector<float> w = tt.host(std::string(kA) + "relative_positional_encoder." + std::to_string(l + 1) + ".0.weight");
         if (w.empty()) { set_error("emotion2vec: weight copy failed"); return -2; }
         float* dst = wp.data() + (size_t)l * D * Cg * K;
         for (int g = 0; g < G; ++g)
@@ -85,8 +74,7 @@ int E2v::prepare(hipStream_t s) {
                     for (int k = 0; k < K; ++k)
                         dst[(((size_t)g * K + k) * Cg + ci) * Cg + o] = w[(((size_t)(g * Cg + o)) * Cg + ci) * K + k];
     }
-    if (posw.ensure(sizeof(float) * wp.size())) return -2;
-    PF_HIP_TRY(hipMemcpy(posw.p, wp.data(), sizeof(float) * wp.size(), hipMemcpyHostToDevice));
+    if (!wp.empty() && tt.put_derived("#posw", wp)) return -2;
     // ALiBi slopes (get_slopes of the reference) and per-block scales clamp_min(alibi_scale, 0)
     const int NA = cfg.num_alibi_heads, NB = (int)blocks.size();
     std::vector<double> sl;
@@ -107,19 +95,16 @@ int E2v::prepare(hipStream_t s) {
         sl = a;
     };
     slopes(NA);
-    std::vector<float> sc = host(std::string(kA) + "alibi_scale");
+    std::vector<float> sc = tt.host(std::string(kA) + "alibi_scale");
     if (sc.empty()) { set_error("emotion2vec: weight copy failed"); return -2; }
-    h_slope.assign((size_t)NB * H, 0.f);
-    h_scale.assign((size_t)NB * H, 0.f);
+    std::vector<float> h_slope((size_t)NB * H, 0.f), h_scale((size_t)NB * H, 0.f);     // per block: [H] slopes and clamped scales
     for (int i = 0; i < NB; ++i)
         for (int h = 0; h < NA; ++h) {
             const int row = cfg.alibi_scale_layers > 1 ? i : 0, col = cfg.alibi_scale_heads > 1 ? h : 0;
             h_slope[(size_t)i * H + h] = (float)sl[h];
             h_scale[(size_t)i * H + h] = fmaxf(sc[(size_t)row * cfg.alibi_scale_heads + col], 0.f);
         }
-    if (slope.ensure(sizeof(float) * h_slope.size()) || scale.ensure(sizeof(float) * h_scale.size())) return -2;
-    PF_HIP_TRY(hipMemcpy(slope.p, h_slope.data(), sizeof(float) * h_slope.size(), hipMemcpyHostToDevice));
-    PF_HIP_TRY(hipMemcpy(scale.p, h_scale.data(), sizeof(float) * h_scale.size(), hipMemcpyHostToDevice));
+    if (NB > 0 && (tt.put_derived("#slope", h_slope) || tt.put_derived("#scale", h_scale))) return -2;
     if (!mask_set && C() > 0) {
         std::vector<int32_t> z((size_t)C(), 0);
         if (mask.ensure(sizeof(int32_t) * z.size())) return -2;
@@ -130,54 +115,33 @@ int E2v::prepare(hipStream_t s) {
     if (cfg.precision == 3) {
         tt.drop_bf16();
         e_conv.assign(cfg.n_conv, 0);
-        for (int l = 1; l < cfg.n_conv; ++l) e_conv[l] = exp_for_bound(ln_bound(conv_name(l - 1, ".2.1."), 512));
-        e_pf = exp_for_bound(ln_bound(std::string(kA) + "project_features.1.", 512));
+        float xb;
+        for (int l = 1; l < cfg.n_conv; ++l) {
+            if (ln_bound(conv_name(l - 1, ".2.1."), 512, &xb, s)) return -2;
+            e_conv[l] = exp_for_bound(xb);
+        }
+        if (ln_bound(std::string(kA) + "project_features.1.", 512, &xb, s)) return -2;
+        e_pf = exp_for_bound(xb);
         e_x.assign(NB, 0); e_attn.assign(NB, 0); e_x1.assign(NB, 0); e_hid.assign(NB, 0);
-        float xb = ln_bound(std::string(kA) + "context_encoder.norm.", D);
+        if (ln_bound(std::string(kA) + "context_encoder.norm.", D, &xb, s)) return -2;
         for (int i = 0; i < NB; ++i) {
             const std::string& p = blocks[i];
             e_x[i] = exp_for_bound(xb);
-            float vb = 0.f, hb = 0.f;
+            float vb = 0.f, hb = 0.f, b1;
             if (TensorTable::dev_linear_bound(tt.get(p + "attn.qkv.weight") + (size_t)2 * D * D, D, D, D, tt.get(p + "attn.qkv.bias") + 2 * D,
                                               xb, &vb, s))
                 return -2;
             e_attn[i] = exp_for_bound(vb);
-            const float b1 = ln_bound(p + "norm1.", D);
+            if (ln_bound(p + "norm1.", D, &b1, s)) return -2;
             e_x1[i] = exp_for_bound(b1);
             if (TensorTable::dev_linear_bound(tt.get(p + "mlp.fc1.weight"), cfg.ffn_dim, D, D, tt.get(p + "mlp.fc1.bias"), b1, &hb, s))
                 return -2;
             e_hid[i] = exp_for_bound(hb);
-            xb = ln_bound(p + "norm2.", D);
+            if (ln_bound(p + "norm2.", D, &xb, s)) return -2;
         }
     }
     prepared = tt.version;
     return 0;
-}
-
-// C[M, N] = A (rows a_rows of width `width`, physical row stride `width`; viewed with row stride lda, K columns) W^T + bias (+ R1)
-int e2v_gemm(E2v* h, const float* A, int width, size_t a_rows, int lda, int M, int K, const std::string& wname, int N, const float* bias,
-             const float* R1, float* C, int e_a, hipStream_t s) {
-    if (h->cfg.precision == 0) {
-        GemmArgs g{};
-        g.A = A; g.lda = lda; g.W = h->tt.get(wname); g.ldw = K; g.bias = bias;
-        g.R1 = R1; g.ldr1 = N; g.C = C; g.ldc = N; g.M = M; g.N = N; g.K = K;
-        return launch_gemm_f32(g, s);
-    }
-    const size_t plane = a_rows * (size_t)width;
-    if (h->planes.ensure(sizeof(unsigned short) * 2 * plane)) return -2;
-    unsigned short* P = h->planes.as<unsigned short>();
-    int rc;
-    if ((rc = launch_split2(A, width, P, width, plane, (int)a_rows, width, pow2f(e_a), s))) return rc;
-    int ew = 0;
-    const unsigned short* W2 = h->tt.get_split2(wname, N, K, &ew, s);
-    if (!W2) return -2;
-    Gemm2Args g{};
-    g.A = P; g.lda = lda; g.a_plane = plane;
-    g.W = W2; g.ldw = K; g.w_plane = (size_t)N * K;
-    g.oscale = pow2f(-(e_a + ew));
-    g.bias = bias; g.R1 = R1; g.ldr1 = N; g.C = C; g.ldc = N;
-    g.M = M; g.N = N; g.K = K;
-    return launch_gemm_f16x2(g, s);
 }
 
 int e2v_rows(const float* x, int ldx, const int* in_map, const float* g, const float* b, int ln, int gelu, float eps, float* y, int M,
@@ -228,6 +192,12 @@ int run(E2v* h, const float* wav, const int64_t* n, int B, float* feats, float* 
         upload_h2d(h->foff.p, foff.data(), sizeof(int32_t) * (B + 1), s) || upload_h2d(h->toff.p, toff.data(), sizeof(int32_t) * (B + 1), s))
         return -2;
     int rc;
+    const bool x2 = c.precision == 3;
+    // C[M, N] = A (a_rows physical rows of `width` floats, viewed at row stride lda with K columns) W^T + bias (+ R1)
+    auto gm = [&](const float* A, int width, size_t a_rows, int lda, int M_, int K, const std::string& w, int N, const float* bias,
+                  const float* R1, float* C, int e_a) {
+        return gemm_two_mode(h->tt, h->planes, x2, A, width, a_rows, lda, M_, K, w, N, bias, R1, C, N, e_a, 0, s);
+    };
     const int *d_so = h->so.as<int>(), *d_foff = h->foff.as<int>(), *d_toff = h->toff.as<int>();
     if ((rc = launch_e2v_wav_stats(wav, h->woff.as<int64_t>(), B, c.normalize, h->stats.as<float>(), s))) return rc;
     float* cur = h->convA.as<float>();
@@ -240,8 +210,8 @@ int run(E2v* h, const float* wav, const int64_t* n, int B, float* feats, float* 
     for (int l = 1; l < NL; ++l) {
         const int k = c.conv_kernel[l], st = c.conv_stride[l], Mo = M / st;
         PF_HIP_TRY(hipMemsetAsync(cur + (size_t)M * 512, 0, sizeof(float) * SL * 512, s));
-        if ((rc = e2v_gemm(h, cur, 512, (size_t)M + SL, st * 512, Mo, k * 512, conv_name(l, ".0.weight"), 512, nullptr, nullptr, nxt,
-                           h->cfg.precision == 3 ? h->e_conv[l] : 0, s)))
+        if ((rc = gm(cur, 512, (size_t)M + SL, st * 512, Mo, k * 512, conv_name(l, ".0.weight"), 512, nullptr, nullptr, nxt,
+                           x2 ? h->e_conv[l] : 0)))
             return rc;
         if ((rc = e2v_rows(nxt, 512, nullptr, h->tt.get(conv_name(l, ".2.1.weight")), h->tt.get(conv_name(l, ".2.1.bias")), 1, 1, eps, nxt,
                            Mo, 512, s)))
@@ -254,8 +224,8 @@ int run(E2v* h, const float* wav, const int64_t* n, int B, float* feats, float* 
     if ((rc = e2v_rows(cur, 512, h->inmap.as<int>(), h->tt.get(pf + "1.weight"), h->tt.get(pf + "1.bias"), 1, 0, eps, h->feat.as<float>(), F,
                        512, s)))
         return rc;
-    if ((rc = e2v_gemm(h, h->feat.as<float>(), 512, F, 512, F, 512, pf + "2.weight", D, h->tt.get(pf + "2.bias"), nullptr, h->xf.as<float>(),
-                       h->e_pf, s)))
+    if ((rc = gm(h->feat.as<float>(), 512, F, 512, F, 512, pf + "2.weight", D, h->tt.get(pf + "2.bias"), nullptr, h->xf.as<float>(),
+                       h->e_pf)))
         return rc;
     // relative positional encoder
     const float* pin = h->xf.as<float>();
@@ -264,7 +234,7 @@ int run(E2v* h, const float* wav, const int64_t* n, int B, float* feats, float* 
     const int Cg = D / c.conv_pos_groups;
     for (int l = 0; l < c.conv_pos_depth; ++l) {
         const std::string p = std::string(kA) + "relative_positional_encoder." + std::to_string(l + 1) + ".0.";
-        if ((rc = launch_e2v_posconv(pin, h->posw.as<float>() + (size_t)l * D * Cg * c.conv_pos_kernel, h->tt.get(p + "bias"), d_foff, B, F,
+        if ((rc = launch_e2v_posconv(pin, h->tt.get("#posw") + (size_t)l * D * Cg * c.conv_pos_kernel, h->tt.get(p + "bias"), d_foff, B, F,
                                      D, c.conv_pos_groups, c.conv_pos_kernel, pa, s)))
             return rc;
         if ((rc = e2v_rows(pa, D, nullptr, nullptr, nullptr, 1, 1, eps, pa, F, D, s))) return rc;
@@ -276,26 +246,25 @@ int run(E2v* h, const float* wav, const int64_t* n, int B, float* feats, float* 
                                 h->tt.get(std::string(kA) + "context_encoder.norm.weight"),
                                 h->tt.get(std::string(kA) + "context_encoder.norm.bias"), eps, x, s)))
         return rc;
-    const bool x2 = c.precision == 3;
     for (size_t i = 0; i < h->blocks.size(); ++i) {
         const std::string& p = h->blocks[i];
         float *qkv = h->qkv.as<float>(), *at = h->attn.as<float>(), *y1 = h->y1.as<float>(), *x1 = h->x1.as<float>(), *hd = h->hid.as<float>();
-        if ((rc = e2v_gemm(h, x, D, Ntok, D, Ntok, D, p + "attn.qkv.weight", 3 * D, h->tt.get(p + "attn.qkv.bias"), nullptr, qkv,
-                           x2 ? h->e_x[i] : 0, s)))
+        if ((rc = gm(x, D, Ntok, D, Ntok, D, p + "attn.qkv.weight", 3 * D, h->tt.get(p + "attn.qkv.bias"), nullptr, qkv,
+                           x2 ? h->e_x[i] : 0)))
             return rc;
-        if ((rc = launch_e2v_attention(qkv, d_toff, B, maxlen, c.num_heads, c.num_alibi_heads, E, h->slope.as<float>() + i * c.num_heads,
-                                       h->scale.as<float>() + i * c.num_heads, at, s)))
+        if ((rc = launch_e2v_attention(qkv, d_toff, B, maxlen, c.num_heads, c.num_alibi_heads, E, h->tt.get("#slope") + i * c.num_heads,
+                                       h->tt.get("#scale") + i * c.num_heads, at, s)))
             return rc;
-        if ((rc = e2v_gemm(h, at, D, Ntok, D, Ntok, D, p + "attn.proj.weight", D, h->tt.get(p + "attn.proj.bias"), x, y1,
-                           x2 ? h->e_attn[i] : 0, s)))
+        if ((rc = gm(at, D, Ntok, D, Ntok, D, p + "attn.proj.weight", D, h->tt.get(p + "attn.proj.bias"), x, y1,
+                           x2 ? h->e_attn[i] : 0)))
             return rc;
         if ((rc = e2v_rows(y1, D, nullptr, h->tt.get(p + "norm1.weight"), h->tt.get(p + "norm1.bias"), 1, 0, eps, x1, Ntok, D, s))) return rc;
-        if ((rc = e2v_gemm(h, x1, D, Ntok, D, Ntok, D, p + "mlp.fc1.weight", FF, h->tt.get(p + "mlp.fc1.bias"), nullptr, hd,
-                           x2 ? h->e_x1[i] : 0, s)))
+        if ((rc = gm(x1, D, Ntok, D, Ntok, D, p + "mlp.fc1.weight", FF, h->tt.get(p + "mlp.fc1.bias"), nullptr, hd,
+                           x2 ? h->e_x1[i] : 0)))
             return rc;
         if ((rc = e2v_rows(hd, FF, nullptr, nullptr, nullptr, 0, 1, eps, hd, Ntok, FF, s))) return rc;
-        if ((rc = e2v_gemm(h, hd, FF, Ntok, FF, Ntok, FF, p + "mlp.fc2.weight", D, h->tt.get(p + "mlp.fc2.bias"), x1, y1,
-                           x2 ? h->e_hid[i] : 0, s)))
+        if ((rc = gm(hd, FF, Ntok, FF, Ntok, FF, p + "mlp.fc2.weight", D, h->tt.get(p + "mlp.fc2.bias"), x1, y1,
+                           x2 ? h->e_hid[i] : 0)))
             return rc;
         if ((rc = e2v_rows(y1, D, nullptr, h->tt.get(p + "norm2.weight"), h->tt.get(p + "norm2.bias"), 1, 0, eps, x, Ntok, D, s))) return rc;
     }
@@ -427,9 +396,8 @@ int pf_emotion2vec_forward(pf_emotion2vec* hh, const float* wav, const int64_t* 
                       std::to_string(need));
             return -1;
         }
-    std::string first;
-    if (h->tt.missing(&first)) { set_error("emotion2vec: tensor not set: " + first); return -3; }
     int rc;
+    if ((rc = h->tt.require_all("emotion2vec"))) return rc;
     if (h->prepared != h->tt.version && (rc = h->prepare(s))) return rc;
     int64_t so = 0, fo = 0;
     for (int b0 = 0; b0 < B;) {

@@ -51,10 +51,8 @@ int encoder_prepare_x2(Encoder* e, hipStream_t s) {
         if (!w.qkv_w2 || !w.out_w2 || !w.w1_2 || !w.w2_2) return -2;
         // a-priori bounds -> plane exponents. LayerNorm: |y| <= sqrt(D) max|gamma| + max|beta|; a Linear over inputs
         // bounded by b: |W x + c| <= b max_n sum_k |W[n, k]| + |c[n]|; attention output <= max |v|; relu only shrinks
-        float g1, b1, g2, b2, bq, bk, bv, bh;
-        if (TensorTable::dev_absmax(w.n1g, w.in_dim, &g1, s) || TensorTable::dev_absmax(w.n1b, w.in_dim, &b1, s) ||
-            TensorTable::dev_absmax(w.n2g, D, &g2, s) || TensorTable::dev_absmax(w.n2b, D, &b2, s)) return -2;
-        const float bx1 = sqrtf((float)w.in_dim) * g1 + b1, bx2 = sqrtf((float)D) * g2 + b2;
+        float bx1, bx2, bq, bk, bv, bh;
+        if (TensorTable::dev_ln_bound(w.n1g, w.n1b, w.in_dim, &bx1, s) || TensorTable::dev_ln_bound(w.n2g, w.n2b, D, &bx2, s)) return -2;
         if (TensorTable::dev_linear_bound(w.qkv_w, D, w.in_pad, w.in_pad, w.qkv_b, bx1, &bq, s) ||
             TensorTable::dev_linear_bound(w.qkv_w + (size_t)D * w.in_pad, D, w.in_pad, w.in_pad, w.qkv_b + D, bx1, &bk, s) ||
             TensorTable::dev_linear_bound(w.qkv_w + (size_t)2 * D * w.in_pad, D, w.in_pad, w.in_pad, w.qkv_b + 2 * D, bx1, &bv, s) ||

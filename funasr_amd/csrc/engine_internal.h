@@ -1,8 +1,14 @@
 // Internal header of the C-ABI layer (include/paraformer_hip.h): the handle types of every module family and the helpers they
 // share. The layer is split by family -- engine.hip (shared state: errors, profiling, staging ring, instrumented launch helpers,
 // ABI version), engine_frontend.hip, engine_encoder.hip, engine_decoder.hip (predictor, decoder, CTC), engine_stream.hip,
-// engine_vad.hip, engine_kernels.hip (the pf_k_* single-kernel hooks) -- so that a kernel change recompiles one family
+// engine_vad.hip, engine_pipeline.hip, engine_campplus.hip, engine_emotion2vec.hip, engine_conformer.hip (Conformer encoder and
+// Transformer decoder step), engine_kernels.hip (the pf_k_* single-kernel hooks) -- so that a kernel change recompiles one family
 // (round-3 review: engine.hip was one 3 400-line translation unit).
+//
+// Load-time weight preparation has ONE home, the TensorTable: what the library computes from the caller's weights (folded BatchNorms,
+// repacked convolutions, scaled copies, constant tables) is stored with put_derived() beside them, served by get() / get_split2() like
+// any tensor, never writable through set(), and never counted by missing(); a family re-derives when `version` differs from the
+// one it prepared for. The helpers every family's preparation shares (host(), bn_fold(), dev_ln_bound(), require_all()) live there too.
 //
 // Memory model: weights are copied once into library-owned HBM (repacked where a kernel wants a different
 // layout); activations live in a per-handle workspace that only grows (hipMalloc outside the steady state,
@@ -12,6 +18,7 @@
 #include <math.h>
 #include <string.h>
 
+#include <cmath>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -87,6 +94,7 @@ struct Tensor {
     float* d = nullptr;      // device storage (library owned)
     int64_t numel = 0;       // expected element count of the SOURCE tensor
     bool set = false;
+    bool derived = false;    // computed by the library from the caller's weights (put_derived), never written through set()
     // optional repack description
     int kind = 0;            // 0 plain copy, 1 pad rows [rows, cols] -> [rows, cols_pad], 2 conv [O, I, K] -> [O, K*I],
                              // 3 upsampling conv, 4 tiled vector (see add_upsample / add_tiled)
@@ -138,7 +146,7 @@ struct TensorTable {
     int add_lstm_hh(const std::string& name, int H) { return add(name, (int64_t)4 * H * H); }
     int set(const char* name, const float* data, int64_t numel) {
         auto it = t.find(name);
-        if (it == t.end()) { set_error(std::string("unknown tensor name: ") + name); return -1; }
+        if (it == t.end() || it->second.derived) { set_error(std::string("unknown tensor name: ") + name); return -1; }
         Tensor& x = it->second;
         ++version;
         if (numel != x.numel) {
@@ -186,7 +194,57 @@ struct TensorTable {
         for (auto& kv : t) if (!kv.second.set) { if (n == 0 && first) *first = kv.first; ++n; }
         return n;
     }
+    // 0 when every tensor is set; else the one refusal of a forward on an incomplete handle: "<family>: tensor not set: <name>", -3
+    int require_all(const char* family) const {
+        std::string first;
+        if (!missing(&first)) return 0;
+        set_error(std::string(family) + ": tensor not set: " + first);
+        return -3;
+    }
     const float* get(const std::string& name) const { return t.at(name).d; }
+    // a tensor's source elements back on the host (load-time preparation; empty when the copy failed)
+    std::vector<float> host(const std::string& name) const {
+        const Tensor& x = t.at(name);
+        std::vector<float> v((size_t)x.numel);
+        if (hipMemcpy(v.data(), x.d, sizeof(float) * v.size(), hipMemcpyDeviceToHost) != hipSuccess) v.clear();
+        return v;
+    }
+    // Store a tensor the library computed from the caller's weights. `version` stays: derived data follows the weights, it is not a
+    // change of them. Sizes are fixed by the config, so a name is allocated once and overwritten in place (synchronous copy; never
+    // freed while kernels may be queued); its cached planes go with the old contents.
+    int put_derived(const std::string& name, const std::vector<float>& v) {
+        auto it = t.find(name);
+        if (it == t.end()) {
+            if (add(name, (int64_t)v.size())) return -2;
+            it = t.find(name);
+            it->second.derived = it->second.set = true;
+        } else if (!it->second.derived || it->second.numel != (int64_t)v.size()) {
+            set_error("derived tensor " + name + ": not a derived name, or its size changed");
+            return -2;
+        }
+        PF_HIP_TRY(hipMemcpy(it->second.d, v.data(), sizeof(float) * v.size(), hipMemcpyHostToDevice));
+        for (const char* suffix : {"", "#split2", "#split3"}) {
+            auto c = b16.find(name + suffix);
+            if (c == b16.end()) continue;
+            (void)hipFree(c->second);
+            b16.erase(c);
+            exp2.erase(name + suffix);
+        }
+        return 0;
+    }
+    // double scale / shift of the BatchNorm `p` (p + "weight|bias|running_mean|running_var"; affine = false: weight 1, bias 0)
+    bool bn_fold(const std::string& p, bool affine, double eps, std::vector<double>& sc, std::vector<double>& sh) const {
+        std::vector<float> rm = host(p + "running_mean"), rv = host(p + "running_var"), w, b;
+        if (affine) { w = host(p + "weight"); b = host(p + "bias"); }
+        if (rm.empty() || rv.empty() || (affine && (w.empty() || b.empty()))) return false;
+        sc.resize(rm.size()); sh.resize(rm.size());
+        for (size_t i = 0; i < rm.size(); ++i) {
+            const double s = (affine ? (double)w[i] : 1.0) / std::sqrt((double)rv[i] + eps);
+            sc[i] = s;
+            sh[i] = (affine ? (double)b[i] : 0.0) - (double)rm[i] * s;
+        }
+        return true;
+    }
     // bf16 copy of a (repacked) tensor for the bf16-operand mode, made on first use and dropped when the fp32
     // master changes
     std::map<std::string, unsigned short*> b16;
@@ -245,6 +303,13 @@ struct TensorTable {
         if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = -2;
         (void)hipFree(d);
         return rc;
+    }
+    // |LayerNorm output| <= sqrt(D) max|gamma| + max|beta|: the a-priori bound that fixes every f16x2 plane exponent
+    static int dev_ln_bound(const float* gamma, const float* beta, int D, float* out, hipStream_t s) {
+        float g, b;
+        if (dev_absmax(gamma, D, &g, s) || dev_absmax(beta, D, &b, s)) return -2;
+        *out = sqrtf((float)D) * g + b;
+        return 0;
     }
     // max over rows n of (in_bound * sum_k |W[n, k]| + |bias[n]|): an a-priori bound on |W x + b| for |x_k| <= in_bound
     static int dev_linear_bound(const float* W, int rows, int cols, int ld, const float* bias, float in_bound, float* out,
@@ -601,6 +666,12 @@ std::string dec_layer_prefix(bool contextual, int n_blocks, int i);
 int decoder_resolve(Decoder* d);
 int vocab_project(const float* hidden, int M, int D, const float* W, const float* bias, int V, float* logits,
                          int32_t* ids, DevBuf& pval, DevBuf& pidx, hipStream_t s);
+// C[M, N] = A W^T + bias (+ R1) (ReLU before the addend) in one of two modes. A is a_rows physical rows of `width` floats, viewed as M
+// rows of K columns at row stride lda (an overlapping view where lda < K). x2 = false: the exact-fp32 MFMA GEMM. x2 = true: A's rows
+// are split into two fp16 planes at the a-priori exponent e_a (into `planes`), the weight's cached planes are fetched, and the GEMM
+// runs on the fp16 matrix cores with fp32 results.
+int gemm_two_mode(TensorTable& tt, DevBuf& planes, bool x2, const float* A, int width, size_t a_rows, int lda, int M, int K,
+                  const std::string& wname, int N, const float* bias, const float* R1, float* C, int ldc, int e_a, int relu, hipStream_t s);
 int gemm3_simple(const unsigned short* A3, int lda, int M, const unsigned short* W3, const float* bias, float* C,
                         int ldc, int N, int K, int relu, hipStream_t s);
 int gemm2_simple(const unsigned short* A2, int lda, int M, int ea, const unsigned short* W2, int ew, const float* bias,

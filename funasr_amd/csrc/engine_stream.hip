@@ -34,15 +34,14 @@ static int stream_prepare_x2(Stream* st, hipStream_t s) {
     for (int l = 0; l < dc.n_blocks; ++l)
         if ((rc = dec_layer_x2(d, d->layers[l], dec_layer_prefix(d->contextual, dc.n_blocks, l), true, s))) return rc;
     if ((rc = dec_layer_x2(d, d->last, "decoders3.0.", false, s))) return rc;
-    float g, b;
-    if (TensorTable::dev_absmax(e->tt.get("after_norm.weight"), D, &g, s) || TensorTable::dev_absmax(e->tt.get("after_norm.bias"), D, &b, s)) return -2;
-    const float bmem = sqrtf((float)D) * g + b;
+    float bmem, b;
+    if (TensorTable::dev_ln_bound(e->tt.get("after_norm.weight"), e->tt.get("after_norm.bias"), D, &bmem, s)) return -2;
     st->e_mem = exp_for_bound(bmem);
     st->e_ctx.assign((size_t)dc.n_blocks, 0);
     for (int l = 0; l < dc.n_blocks; ++l)      // |attention output| <= max |v|,  v = Wv m + bv
         st->e_ctx[l] = exp_for_bound(bmem * d->layers[l].kv_l1b[2] + d->layers[l].kv_l1b[3]);
-    if (TensorTable::dev_absmax(d->tt.get("after_norm.weight"), D, &g, s) || TensorTable::dev_absmax(d->tt.get("after_norm.bias"), D, &b, s)) return -2;
-    st->e_an = exp_for_bound(sqrtf((float)D) * g + b);
+    if (TensorTable::dev_ln_bound(d->tt.get("after_norm.weight"), d->tt.get("after_norm.bias"), D, &b, s)) return -2;
+    st->e_an = exp_for_bound(b);
     int ew_v = 0;
     if (!d->tt.get_split2("output_layer.weight", dc.vocab_size, D, &ew_v, s)) return -2;
     // the layers' linear_k_v weights as one matrix (Stream.kvcat_*): rows [l * 2 D, (l + 1) * 2 D) = layer l
@@ -504,7 +503,7 @@ pf_stream* pf_stream_create(pf_encoder* eh, pf_predictor* ph, pf_decoder* dh, co
     int rc;
     if (!e->resolved && (rc = encoder_resolve(e))) return nullptr;
     if (!d->resolved && (rc = decoder_resolve(d))) return nullptr;
-    { std::string first; if (p->tt.missing(&first)) { set_error("predictor: tensor not set: " + first); return nullptr; } }
+    if (p->tt.require_all("predictor")) return nullptr;
     std::unique_ptr<Stream> st(new Stream());
     st->e = e; st->p = p; st->d = d; st->cfg = c;
     st->S = c.n_streams; st->keep = c.chunk_left + c.chunk_right; st->Wmax = st->keep + c.max_frames;

@@ -61,8 +61,7 @@ int pf_vad_forward(pf_vad* vh, const float* feats, int32_t B, int32_t T, float* 
     Vad* v = reinterpret_cast<Vad*>(vh);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     PF_REQUIRE(v && feats && p_sil && sil_ids_host && B > 0 && T > 0 && n_sil >= 1, "vad_forward: null/empty argument");
-    std::string first;
-    if (v->tt.missing(&first)) { set_error("vad: tensor not set: " + first); return -3; }
+    if (v->tt.require_all("vad")) return -3;
     const pf_vad_config& c = v->cfg;
     const int M = B * T;
     const int Kin = vad_pad(c.input_dim), Ka = vad_pad(c.input_affine_dim), Kl = vad_pad(c.linear_dim), Kp = vad_pad(c.proj_dim),

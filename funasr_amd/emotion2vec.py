@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .hip_module import Holder, HipModule, ParamHolder, stream_ptr
+from .hip_module import Holder, HipModule, ParamHolder, _truthy, stream_ptr
 from .register import tables
 
 SAMPLE_RATE = 16000
@@ -57,10 +57,6 @@ def _num(v, kind=float):
     if isinstance(v, str):
         v = float(v)
     return kind(v)
-
-
-def _truthy(v) -> bool:
-    return v in (True, 1, "true", "True")
 
 
 def get_slopes(n: int) -> list:

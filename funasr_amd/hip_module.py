@@ -49,11 +49,17 @@ def depthwise(channels, k):
     return ParamHolder((channels, 1, k), None)
 
 
+def _truthy(v) -> bool:
+    """a yaml / omegaconf boolean in any of its spellings"""
+    return v in (True, 1, "true", "True")
+
+
 class HipModule(nn.Module):
     """Owns one C handle. Subclasses set _create / _destroy / _set_tensor names and _skip_keys."""
 
     _prefix = ""              # e.g. "pf_encoder"
     _skip_keys: tuple = ()    # state_dict keys the device does not need (training-only tensors)
+    _push_buffers = False     # True: buffers (BatchNorm's running statistics) reach the handle beside the parameters
 
     def __init__(self):
         super().__init__()
@@ -99,13 +105,20 @@ class HipModule(nn.Module):
     def _after_create(self, lib, handle):  # settings that register further tensors, before the first set_tensor
         pass
 
+    def _extra_tensors(self):  # (name, tensor) pairs built on the host that are no part of the state_dict (positional tables)
+        return ()
+
     def _push_weights(self, lib):
         set_tensor = getattr(lib, self._prefix + "_set_tensor")
+        named = list(self.named_parameters())
+        if self._push_buffers:
+            named += [(n, b) for n, b in self.named_buffers() if not n.endswith("num_batches_tracked")]
+        named += list(self._extra_tensors())
         with torch.cuda.device(self._handle_device):
-            for name, p in self.named_parameters():
+            for name, p in named:
                 if name in self._skip_keys or any(name.startswith(s) for s in self._skip_keys if s.endswith(".")):
                     continue
-                t = p.detach().to(dtype=torch.float32).contiguous()
+                t = p.detach().to(device=self._handle_device, dtype=torch.float32).contiguous()
                 _lib.check(set_tensor(self._handle, name.encode(), t.data_ptr(), t.numel()),
                            f"{self._prefix}_set_tensor({name})")
             torch.cuda.synchronize()

@@ -70,6 +70,16 @@ def test_batch_invariance_and_determinism(cuda):
     assert torch.equal(m(x), full)
 
 
+def test_weights_replaced_on_a_live_handle(cuda):
+    """a second state dict loaded into a module that already ran: every folded / repacked weight is rebuilt from it"""
+    g = torch.Generator().manual_seed(0)
+    x = torch.randn(2, 20, 80, generator=g).to(cuda)
+    m = _model(cuda, 4)
+    m(x)
+    m.load_state_dict(synth.campplus_state_dict(1), strict=True)
+    assert torch.equal(m(x), _model(cuda, 1)(x))
+
+
 def test_embed_chunks_equals_fbank_then_forward(cuda):
     m = _model(cuda, 6)
     wav = synth.speech_like(16000 * 6, seed=3).to(cuda) * 0.3

@@ -102,6 +102,50 @@ def test_subsampling_feature_counts_and_shortest_batches_against_the_oracle(cuda
     assert torch.equal(s, fresh.encode(short, [7])[0])
 
 
+@pytest.fixture(scope="module")
+def live(cuda):
+    """model A after an encode with seed 1 and a load_state_dict of seed 2 on the live handle; B is a fresh model with seed 2"""
+    conf = synth.conformer_conf(enc_blocks=1, macaron=True)
+    g = torch.Generator().manual_seed(0)
+    lens = [23, 17]
+    feats = torch.randn(2, 23, 80, generator=g)
+    feats[1, 17:] = 0
+    feats = feats.to(cuda)
+    a, _ = _encoder_model(cuda, conf, 1, "f16x2")
+    a.encode(feats, lens)                                                     # primes the handle with seed 1
+    a.load_state_dict(synth.conformer_state_dict(2, a), strict=True)
+    b, _ = _encoder_model(cuda, conf, 2, "f16x2")
+    return conf, a, b.encode(feats, lens)[0], feats, lens
+
+
+def test_weights_and_precision_replaced_on_a_live_handle(cuda, live):
+    """One handle through load_state_dict and set_precision: every encode equals a fresh model's with the same weights and mode, so
+    nothing derived at load time (conv taps, output linear, folded BatchNorm, halved macaron w_2, plane caches and exponents) outlives
+    the weights or the mode it was made for."""
+    conf, a, want_x2, feats, lens = live
+    assert torch.equal(a.encode(feats, lens)[0], want_x2)
+    a.set_precision("fp32")
+    c, _ = _encoder_model(cuda, conf, 2, "fp32")
+    assert torch.equal(a.encode(feats, lens)[0], c.encode(feats, lens)[0])
+    a.set_precision("f16x2")
+    assert torch.equal(a.encode(feats, lens)[0], want_x2)
+
+
+def test_derived_tensor_names_are_not_writable(cuda, live):
+    """what the library derives from the weights is refused by set_tensor like any unknown name -- also once a forward has put the
+    names into the table -- and never counts as missing"""
+    _, a, want_x2, feats, lens = live
+    before = a.encode(feats, lens)[0]
+    assert torch.equal(before, want_x2)
+    lib, h = _lib.load(), a.encoder._handle
+    one = torch.zeros(1, device=cuda)
+    for name in (b"#embed.out", b"#conv1.tap0", b"#bn", b"encoders.0.feed_forward.w_2.weight#half"):
+        assert lib.pf_conformer_set_tensor(h, name, one.data_ptr(), 1) != 0, name
+        assert "unknown tensor name" in _lib.last_error(), (name, _lib.last_error())
+    assert lib.pf_conformer_missing(h) == 0
+    assert torch.equal(a.encode(feats, lens)[0], before)
+
+
 def _glu_dw_against_the_oracle(cuda, B, T, D, taps):
     lib = _lib.load()
     g = torch.Generator().manual_seed(taps)

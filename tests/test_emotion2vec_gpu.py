@@ -141,6 +141,23 @@ def test_batch_invariance_and_determinism(cuda, precision):
     assert torch.equal(fr, fr3) and torch.equal(pooled, pooled3) and torch.equal(probs, probs3)
 
 
+@pytest.mark.parametrize("precision", ["fp32", "f16x2"])
+def test_weights_replaced_on_a_live_handle(cuda, precision):
+    """a second state dict loaded into a module that already ran: the positional conv weights, ALiBi scales, plane caches and
+    exponents derived from the first one are all replaced -- the outputs are a fresh model's, bit for bit"""
+    conf = synth.emotion2vec_conf(prenet_depth=1, depth=1)
+    lens = [400, 6400]
+    wav = torch.cat([_wav(n, i) for i, n in enumerate(lens)])
+    m, _ = _model(cuda, conf, 5, precision=precision)
+    m.forward_packed(wav, lens)
+    m.load_state_dict(synth.emotion2vec_state_dict(6, m), strict=True)
+    got = m.forward_packed(wav, lens)
+    fresh, _ = _model(cuda, conf, 6, precision=precision)
+    want = fresh.forward_packed(wav, lens)
+    for x, y in zip(got, want):
+        assert torch.equal(x, y)
+
+
 def test_automodel_end_to_end(cuda, tmp_path):
     import yaml
     from funasr_amd.auto_model import AutoModel
