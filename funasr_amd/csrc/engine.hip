@@ -253,12 +253,7 @@ TensorTable* table_of(int kind, void* h) {
 int handle_weights_replaced(int kind, void* handle) {
     TensorTable* tt = handle ? table_of(kind, handle) : nullptr;
     if (!tt) { set_error("dp: null handle or unknown handle kind"); return -1; }
-    for (auto& kv : tt->t) kv.second.set = true;
-    ++tt->version;
-    tt->drop_bf16();
-    if (kind == HANDLE_ENCODER) reinterpret_cast<Encoder*>(handle)->resolved = false;
-    if (kind == HANDLE_DECODER) reinterpret_cast<Decoder*>(handle)->resolved = false;
-    if (kind == HANDLE_PREDICTOR) reinterpret_cast<Predictor*>(handle)->packed = false;
+    tt->replaced_in_place();
     return 0;
 }
 }  // namespace pf

@@ -9,10 +9,8 @@ std::string dec_layer_prefix(bool contextual, int n_blocks, int i) {
 }
 
 
-int decoder_resolve(Decoder* d) {
-    std::string first;
-    const int miss = d->tt.missing(&first);
-    if (miss) { set_error("decoder: " + std::to_string(miss) + " tensors not set, e.g. " + first); return -3; }
+static int decoder_resolve(Decoder* d) {
+    if (d->tt.require_all("decoder")) return -3;
     d->layers.clear();
     for (int i = 0; i < d->cfg.n_blocks; ++i) {
         const std::string p = dec_layer_prefix(d->contextual, d->cfg.n_blocks, i);
@@ -50,9 +48,8 @@ int decoder_resolve(Decoder* d) {
         w.w2 = d->tt.get(p + "feed_forward.w_2.weight");
         d->last = w;
     }
-    d->lb_uploaded = false;
-    d->e_an = INT32_MIN;
-    d->resolved = true;
+    d->resolved_for = d->tt.version;
+    d->x2_for = TensorTable::NOT_PREPARED;
     return 0;
 }
 
@@ -107,9 +104,8 @@ int gemm2_simple(const unsigned short* A2, int lda, int M, int ea, const unsigne
     return launch_gemm_f16x2(g, s);
 }
 
-// f16x2 mode: exponents and weight planes of one decoder layer (once)
-int dec_layer_x2(Decoder* d, DecLayerW& w, const std::string& p, bool attn, hipStream_t s) {
-    if (w.x2_ready) return 0;
+// f16x2 mode: exponents and weight planes of one decoder layer (the per-layer worker of decoder_prepare)
+static int dec_layer_x2(Decoder* d, DecLayerW& w, const std::string& p, bool attn, hipStream_t s) {
     const int D = d->cfg.d_model, F = d->cfg.ffn_dim;
     float b;
     if (TensorTable::dev_ln_bound(w.n1g, w.n1b, D, &b, s)) return -2;
@@ -134,7 +130,32 @@ int dec_layer_x2(Decoder* d, DecLayerW& w, const std::string& p, bool attn, hipS
             TensorTable::dev_linear_bound(w.kv_w + (size_t)D * D, D, D, D, nullptr, 1.f, &w.kv_l1b[2], s) ||
             TensorTable::dev_absmax(w.kv_b + D, D, &w.kv_l1b[3], s)) return -2;
     }
-    w.x2_ready = true;
+    return 0;
+}
+
+// The f16x2 state in one piece: every layer's planes and exponents, the linear_k_v bounds on the device (dlb), after_norm's exponent
+// and the vocabulary planes (load-time reductions with host round trips -- never inside a graph capture)
+int decoder_prepare(Decoder* d, bool x2, hipStream_t s) {
+    int rc;
+    if (d->resolved_for != d->tt.version && (rc = decoder_resolve(d))) return rc;
+    if (!x2 || d->x2_for == d->tt.version) return 0;
+    const pf_decoder_config& c = d->cfg;
+    for (int l = 0; l < c.n_blocks; ++l)
+        if ((rc = dec_layer_x2(d, d->layers[l], dec_layer_prefix(d->contextual, c.n_blocks, l), true, s))) return rc;
+    for (int l = 0; l < d->n_blocks2; ++l)
+        if ((rc = dec_layer_x2(d, d->layers2[l], "decoders2." + std::to_string(l) + ".", false, s))) return rc;
+    if ((rc = dec_layer_x2(d, d->last, "decoders3.0.", false, s))) return rc;
+    std::vector<float> lb((size_t)4 * c.n_blocks);
+    for (int l = 0; l < c.n_blocks; ++l) for (int j = 0; j < 4; ++j) lb[4 * l + j] = d->layers[l].kv_l1b[j];
+    if (d->dlb.ensure(sizeof(float) * lb.size())) return -2;
+    PF_HIP_TRY(hipMemcpyAsync(d->dlb.p, lb.data(), sizeof(float) * lb.size(), hipMemcpyHostToDevice, s));
+    PF_HIP_TRY(hipStreamSynchronize(s));                     // `lb` is a stack object
+    float b;
+    if (TensorTable::dev_ln_bound(d->tt.get("after_norm.weight"), d->tt.get("after_norm.bias"), c.d_model, &b, s)) return -2;
+    d->e_an = exp_for_bound(b);
+    int ew_v = 0;
+    if (c.vocab_size > 0 && !d->tt.get_split2("output_layer.weight", c.vocab_size, c.d_model, &ew_v, s)) return -2;
+    d->x2_for = d->tt.version;
     return 0;
 }
 
@@ -361,7 +382,6 @@ void pf_predictor_destroy(pf_predictor* p) { delete reinterpret_cast<Predictor*>
 int pf_predictor_set_tensor(pf_predictor* ph, const char* name, const float* data, int64_t numel) {
     Predictor* p = reinterpret_cast<Predictor*>(ph);
     PF_REQUIRE(p && name && data, "predictor_set_tensor: null");
-    p->packed = false;
     return p->tt.set(name, data, numel);
 }
 int pf_predictor_missing(const pf_predictor* ph) {
@@ -554,14 +574,14 @@ int pf_predictor_timestamp(pf_predictor* ph, const float* hidden, const int32_t*
         float* pack = p->pack.as<float>();
         float* bi = pack + 2 * hh;
         float* bh = bi + 2 * bb;
-        if (!p->packed) {
+        if (p->packed_for != p->tt.version) {
             PF_HIP_TRY(hipMemcpyAsync(pack, p->tt.get("blstm.weight_hh_l0"), sizeof(float) * hh, hipMemcpyDeviceToDevice, s));
             PF_HIP_TRY(hipMemcpyAsync(pack + hh, p->tt.get("blstm.weight_hh_l0_reverse"), sizeof(float) * hh, hipMemcpyDeviceToDevice, s));
             PF_HIP_TRY(hipMemcpyAsync(bi, p->tt.get("blstm.bias_ih_l0"), sizeof(float) * bb, hipMemcpyDeviceToDevice, s));
             PF_HIP_TRY(hipMemcpyAsync(bi + bb, p->tt.get("blstm.bias_ih_l0_reverse"), sizeof(float) * bb, hipMemcpyDeviceToDevice, s));
             PF_HIP_TRY(hipMemcpyAsync(bh, p->tt.get("blstm.bias_hh_l0"), sizeof(float) * bb, hipMemcpyDeviceToDevice, s));
             PF_HIP_TRY(hipMemcpyAsync(bh + bb, p->tt.get("blstm.bias_hh_l0_reverse"), sizeof(float) * bb, hipMemcpyDeviceToDevice, s));
-            p->packed = true;
+            p->packed_for = p->tt.version;
         }
         w.w_hh = pack; w.b_ih = bi; w.b_hh = bh;
         if ((rc = lstm_forward(w, p->x_tm.as<float>(), Tu, B, D, D, 2, p->lstm_out.as<float>(), 1, p->pre, p->h_a, p->h_b,
@@ -681,14 +701,12 @@ int pf_decoder_set_decoders2(pf_decoder* dh, int32_t n_layers) {
     }
     if (rc) return -2;
     d->n_blocks2 = n_layers;
-    d->resolved = false;
+    ++d->tt.version;         // the table's structure changed: what was resolved and prepared before is stale
     return 0;
 }
 int pf_decoder_set_tensor(pf_decoder* dh, const char* name, const float* data, int64_t numel) {
     Decoder* d = reinterpret_cast<Decoder*>(dh);
     PF_REQUIRE(d && name && data, "decoder_set_tensor: null");
-    d->resolved = false;
-    d->tt.drop_bf16();
     return d->tt.set(name, data, numel);
 }
 /* same modes as pf_encoder_set_precision; the bf16 mode serves the fused arg-max route (logits_dev == NULL) */
@@ -749,7 +767,7 @@ static int decoder_forward_impl(Decoder* d, const float* memory, const int32_t* 
         PF_REQUIRE(tok_lens[b] >= 0 && tok_lens[b] <= N, "decoder_forward: token lens out of range");
     }
     int rc;
-    if (!d->resolved && (rc = decoder_resolve(d))) return rc;
+    if ((rc = decoder_prepare(d, d->precision == 3 && asf_layer < 0 && !cx, s))) return rc;
     const pf_decoder_config& c = d->cfg;
     const int D = c.d_model, F = c.ffn_dim, V = c.vocab_size;
     int Mq = B * N;                                          // rows processed per token-side op (shrinks when packed, below)
@@ -793,23 +811,11 @@ static int decoder_forward_impl(Decoder* d, const float* memory, const int32_t* 
             d->q16.ensure(sizeof(unsigned short) * 2 * (size_t)Mq * D) || d->ctx16.ensure(sizeof(unsigned short) * 2 * (size_t)Mq * D) ||
             d->mem16.ensure(sizeof(unsigned short) * 2 * (size_t)Mkp * D) || d->dsc.ensure(sizeof(float) * 4) ||
             d->k2.ensure(sizeof(unsigned short) * 2 * ((size_t)Mkp + 32) * D) || d->vt2.ensure(sizeof(unsigned short) * 2 * D * ((size_t)Mkp + 64)) ||
-            d->dscl.ensure(sizeof(float) * 4 * c.n_blocks) || d->dlb.ensure(sizeof(float) * 4 * c.n_blocks))
+            d->dscl.ensure(sizeof(float) * 4 * c.n_blocks))
             return -2;
         // rows / columns past the last sequence are read by the last key tile (and masked): keep them finite
         if (d->k2.cap != cap_k) PF_HIP_TRY(hipMemsetAsync(d->k2.p, 0, d->k2.cap, s));
         if (d->vt2.cap != cap_v) PF_HIP_TRY(hipMemsetAsync(d->vt2.p, 0, d->vt2.cap, s));
-        for (int l = 0; l < c.n_blocks; ++l)
-            if ((rc = dec_layer_x2(d, d->layers[l], dec_layer_prefix(d->contextual, c.n_blocks, l), true, s))) return rc;
-        for (int l = 0; l < d->n_blocks2; ++l)
-            if ((rc = dec_layer_x2(d, d->layers2[l], "decoders2." + std::to_string(l) + ".", false, s))) return rc;
-        if ((rc = dec_layer_x2(d, d->last, "decoders3.0.", false, s))) return rc;
-        if (!d->lb_uploaded) {
-            std::vector<float> lb((size_t)4 * c.n_blocks);
-            for (int l = 0; l < c.n_blocks; ++l) for (int j = 0; j < 4; ++j) lb[4 * l + j] = d->layers[l].kv_l1b[j];
-            PF_HIP_TRY(hipMemcpyAsync(d->dlb.p, lb.data(), sizeof(float) * lb.size(), hipMemcpyHostToDevice, s));
-            PF_HIP_TRY(hipStreamSynchronize(s));             // `lb` is a stack object
-            d->lb_uploaded = true;
-        }
         dsc = d->dsc.as<float>();
         if ((rc = launch_absmax(memory, (size_t)Mk * D, dsc, s))) return rc;
         if ((rc = launch_pow2_scale(dsc, dsc + 1, s))) return rc;
@@ -1000,11 +1006,6 @@ static int decoder_forward_impl(Decoder* d, const float* memory, const int32_t* 
         int ew_v = 0;
         const unsigned short* wv2 = d->tt.get_split2("output_layer.weight", V, D, &ew_v, s);
         if (!wv2) return -2;
-        if (d->e_an == INT32_MIN) {
-            float b;
-            if (TensorTable::dev_ln_bound(d->tt.get("after_norm.weight"), d->tt.get("after_norm.bias"), D, &b, s)) return -2;
-            d->e_an = exp_for_bound(b);
-        }
         unsigned short* h2 = d->t16.as<unsigned short>();
         {
             ProfScope ps(PROF_LN, 8.0 * Mq * (double)D, s);
@@ -1047,8 +1048,7 @@ void pf_ctc_destroy(pf_ctc* c) { delete reinterpret_cast<Ctc*>(c); }
 int pf_ctc_set_tensor(pf_ctc* ch, const char* name, const float* data, int64_t numel) {
     Ctc* c = reinterpret_cast<Ctc*>(ch);
     PF_REQUIRE(c && name && data, "ctc_set_tensor: null");
-    c->tt.drop_bf16();          // the f16x2 arg-max route caches weight planes: they follow the fp32 master
-    return c->tt.set(name, data, numel);
+    return c->tt.set(name, data, numel);          // (the f16x2 arg-max route's cached weight planes follow the fp32 master there)
 }
 int pf_ctc_missing(const pf_ctc* ch) {
     const Ctc* c = reinterpret_cast<const Ctc*>(ch);

@@ -10,10 +10,8 @@ static void enc_layer_names(std::vector<std::pair<std::string, int>>& out, const
     for (int i = 0; i < c.tp_blocks; ++i) out.push_back({"tp_encoders." + std::to_string(i) + ".", c.d_model});
 }
 
-int encoder_resolve(Encoder* e) {
-    std::string first;
-    const int miss = e->tt.missing(&first);
-    if (miss) { set_error("encoder: " + std::to_string(miss) + " tensors not set, e.g. " + first); return -3; }
+static int encoder_resolve(Encoder* e) {
+    if (e->tt.require_all("encoder")) return -3;
     std::vector<std::pair<std::string, int>> names;
     enc_layer_names(names, e->cfg);
     e->layers.clear();
@@ -31,23 +29,36 @@ int encoder_resolve(Encoder* e) {
         w.w2 = e->tt.get(p + "feed_forward.w_2.weight"); w.b2 = e->tt.get(p + "feed_forward.w_2.bias");
         e->layers.push_back(w);
     }
-    e->resolved = true;
+    e->resolved_for = e->tt.version;
+    for (auto& stamp : e->planes_for) stamp = TensorTable::NOT_PREPARED;
     return 0;
 }
 
-// f16x2 mode: weight planes with their exponents and the exponents of the activation planes of every block (once per
-// weight set; load-time reductions with host round trips -- never inside a graph capture)
-int encoder_prepare_x2(Encoder* e, hipStream_t s) {
+// The planes of one arithmetic mode in every block: 1 bf16 copies, 2 bf16x3 planes, 3 f16x2 planes with their exponents and the
+// exponents of the activation planes (load-time reductions with host round trips -- never inside a graph capture)
+static int encoder_prepare_planes(Encoder* e, int mode, hipStream_t s) {
     const pf_encoder_config& c = e->cfg;
     const int D = c.d_model, F = c.ffn_dim;
     const float dk_scale = powf((float)(D / c.n_heads), -0.5f);
     for (auto& w : e->layers) {
-        if (w.qkv_w2) continue;
-        const std::string qkv_name = w.prefix + "self_attn.linear_q_k_v.weight";
-        w.qkv_w2 = e->tt.get_split2(qkv_name, 3 * D, w.in_pad, &w.ew_qkv, s);
-        w.out_w2 = e->tt.get_split2(w.prefix + "self_attn.linear_out.weight", D, D, &w.ew_out, s);
-        w.w1_2 = e->tt.get_split2(w.prefix + "feed_forward.w_1.weight", F, D, &w.ew_1, s);
-        w.w2_2 = e->tt.get_split2(w.prefix + "feed_forward.w_2.weight", D, F, &w.ew_2, s);
+        const std::string qkv = w.prefix + "self_attn.linear_q_k_v.weight", out = w.prefix + "self_attn.linear_out.weight",
+                          w1 = w.prefix + "feed_forward.w_1.weight", w2 = w.prefix + "feed_forward.w_2.weight";
+        if (mode == 1) {
+            w.qkv_w16 = e->tt.get_bf16(qkv, s); w.out_w16 = e->tt.get_bf16(out, s);
+            w.w1_16 = e->tt.get_bf16(w1, s); w.w2_16 = e->tt.get_bf16(w2, s);
+            if (!w.qkv_w16 || !w.out_w16 || !w.w1_16 || !w.w2_16) return -2;
+            continue;
+        }
+        if (mode == 2) {
+            w.qkv_w3 = e->tt.get_split3(qkv, 3 * D, w.in_pad, s); w.out_w3 = e->tt.get_split3(out, D, D, s);
+            w.w1_3 = e->tt.get_split3(w1, F, D, s); w.w2_3 = e->tt.get_split3(w2, D, F, s);
+            if (!w.qkv_w3 || !w.out_w3 || !w.w1_3 || !w.w2_3) return -2;
+            continue;
+        }
+        w.qkv_w2 = e->tt.get_split2(qkv, 3 * D, w.in_pad, &w.ew_qkv, s);
+        w.out_w2 = e->tt.get_split2(out, D, D, &w.ew_out, s);
+        w.w1_2 = e->tt.get_split2(w1, F, D, &w.ew_1, s);
+        w.w2_2 = e->tt.get_split2(w2, D, F, &w.ew_2, s);
         if (!w.qkv_w2 || !w.out_w2 || !w.w1_2 || !w.w2_2) return -2;
         // a-priori bounds -> plane exponents. LayerNorm: |y| <= sqrt(D) max|gamma| + max|beta|; a Linear over inputs
         // bounded by b: |W x + c| <= b max_n sum_k |W[n, k]| + |c[n]|; attention output <= max |v|; relu only shrinks
@@ -60,6 +71,19 @@ int encoder_prepare_x2(Encoder* e, hipStream_t s) {
         w.e_x1 = exp_for_bound(bx1); w.e_x2 = exp_for_bound(bx2);
         w.e_q = exp_for_bound(bq * dk_scale); w.e_k = exp_for_bound(bk); w.e_v = exp_for_bound(bv); w.e_h = exp_for_bound(bh);
     }
+    return 0;
+}
+
+int encoder_prepare(Encoder* e, int mode, hipStream_t s) {
+    int rc;
+    if (e->resolved_for != e->tt.version && (rc = encoder_resolve(e))) return rc;
+    if (mode == 0 || e->planes_for[mode] == e->tt.version) return 0;
+    if (mode == 3 && (e->cfg.d_model / e->cfg.n_heads != 128 || e->cfg.d_model % 256 != 0)) {
+        set_error("encoder: the f16x2 mode needs d_model / n_heads == 128 and d_model % 256 == 0");
+        return -1;
+    }
+    if ((rc = encoder_prepare_planes(e, mode, s))) return rc;
+    e->planes_for[mode] = e->tt.version;
     return 0;
 }
 
@@ -309,7 +333,7 @@ int encoder_block(Encoder* e, const EncLayerW& w, float* x_in, int ld_in, float*
         return gemm2(ffn2, F, w.e_h, w.w2_2, w.ew_2, w.b2, x, D, nullptr, 0, D, F, 0, nullptr, 0, x, D);
     }
     // Streaming step in its f16x2 form (cc->x2, pf_stream_set_option "gemm_mode" 3): the block's four GEMMs take two-plane
-    // fp16 operands with the a-priori exponents of the offline f16x2 mode (encoder_prepare_x2) and write fp32, so the FSMN,
+    // fp16 operands with the a-priori exponents of the offline f16x2 mode (encoder_prepare, mode 3) and write fp32, so the FSMN,
     // the few-query attention over the K/V ring and the ring itself stay the fp32 kernels of the default step. The attention
     // output (a convex combination of v rows, ring rows included: the same projection of earlier frames) is bounded by v's bound.
     const bool x2c = cc && cc->x2;
@@ -359,7 +383,7 @@ int encoder_block(Encoder* e, const EncLayerW& w, float* x_in, int ld_in, float*
         ProfScope ps(PROF_GEMM, 2.0 * M * (double)N * K, s);
         return gemm(g, s);
     };
-    if (x2c && (!w.qkv_w2 || !w.out_w2 || !w.w1_2 || !w.w2_2)) { set_error("encoder: streaming f16x2 step without prepared weight planes"); return -1; }
+    if (x2c && e->planes_for[3] != e->tt.version) { set_error("encoder: streaming f16x2 step without prepared weight planes"); return -1; }
     // norm1 -> fused QKV projection
     if (x2c) {
         // (norm1's planes already written by the block before: the second launch of its w_2, see gemm2c)
@@ -504,8 +528,6 @@ void pf_encoder_destroy(pf_encoder* e) { delete reinterpret_cast<Encoder*>(e); }
 int pf_encoder_set_tensor(pf_encoder* eh, const char* name, const float* data, int64_t numel) {
     Encoder* e = reinterpret_cast<Encoder*>(eh);
     PF_REQUIRE(e && name && data, "encoder_set_tensor: null");
-    e->resolved = false;
-    e->tt.drop_bf16();
     return e->tt.set(name, data, numel);
 }
 /* 0 = fp32 MFMA, 1 = bf16 operands for the GEMMs and the attention (fp32 accumulate, fp32
@@ -606,7 +628,7 @@ int pf_encoder_forward(pf_encoder* eh, const float* xs, const int32_t* lens_host
     e->prof_rows = e->prof_sq = 0;
     for (int b = 0; b < B; ++b) { e->prof_rows += lens_host[b]; e->prof_sq += (double)lens_host[b] * lens_host[b]; }
     int rc;
-    if (!e->resolved && (rc = encoder_resolve(e))) return rc;
+    if ((rc = encoder_prepare(e, e->precision, s))) return rc;
     const pf_encoder_config& c = e->cfg;
     // f16x2 mode: every sequence occupies Tp = T rounded up to 16 rows (attention_f16x2.hip's tile alignment); the
     // extra rows are zero on entry, masked as keys, never returned
@@ -635,7 +657,6 @@ int pf_encoder_forward(pf_encoder* eh, const float* xs, const int32_t* lens_host
     const size_t M = pack ? (size_t)packed_rows : (size_t)B * Tp;
     const int D = c.d_model, F = c.ffn_dim, Din = c.input_dim, Dpad = round_up(Din, 64);
     const int Fbuf = F > Din ? F : Din;
-    if (e->precision == 3 && !x2) { set_error("encoder: the f16x2 mode needs d_model / n_heads == 128 and d_model % 256 == 0"); return -1; }
     if (x2) {
         const size_t cap_q = e->q2.cap, cap_k = e->k2.cap, cap_v = e->vt2.cap;
         if (e->xn16.ensure(sizeof(unsigned short) * 2 * M * (Dpad > D ? Dpad : D)) ||
@@ -647,33 +668,16 @@ int pf_encoder_forward(pf_encoder* eh, const float* xs, const int32_t* lens_host
         if (e->q2.cap != cap_q) PF_HIP_TRY(hipMemsetAsync(e->q2.p, 0, e->q2.cap, s));
         if (e->k2.cap != cap_k) PF_HIP_TRY(hipMemsetAsync(e->k2.p, 0, e->k2.cap, s));
         if (e->vt2.cap != cap_v) PF_HIP_TRY(hipMemsetAsync(e->vt2.p, 0, e->vt2.cap, s));
-        if ((rc = encoder_prepare_x2(e, s))) return rc;
     }
     if (e->precision == 1) {
         if (e->xn16.ensure(sizeof(unsigned short) * M * (Dpad > D ? Dpad : D)) || e->qkv16.ensure(sizeof(unsigned short) * M * 3 * D) ||
             e->ctx16.ensure(sizeof(unsigned short) * M * D) || e->ffn16.ensure(sizeof(unsigned short) * M * F))
             return -2;
-        for (auto& w : e->layers) {
-            if (w.qkv_w16) continue;
-            w.qkv_w16 = e->tt.get_bf16(w.prefix + "self_attn.linear_q_k_v.weight", s);
-            w.out_w16 = e->tt.get_bf16(w.prefix + "self_attn.linear_out.weight", s);
-            w.w1_16 = e->tt.get_bf16(w.prefix + "feed_forward.w_1.weight", s);
-            w.w2_16 = e->tt.get_bf16(w.prefix + "feed_forward.w_2.weight", s);
-            if (!w.qkv_w16 || !w.out_w16 || !w.w1_16 || !w.w2_16) return -2;
-        }
     }
     if (e->precision == 2) {
         if (e->xn16.ensure(sizeof(unsigned short) * 3 * M * (Dpad > D ? Dpad : D)) ||
             e->ctx16.ensure(sizeof(unsigned short) * 3 * M * D) || e->ffn16.ensure(sizeof(unsigned short) * 3 * M * F))
             return -2;
-        for (auto& w : e->layers) {
-            if (w.qkv_w3) continue;
-            w.qkv_w3 = e->tt.get_split3(w.prefix + "self_attn.linear_q_k_v.weight", 3 * D, w.in_pad, s);
-            w.out_w3 = e->tt.get_split3(w.prefix + "self_attn.linear_out.weight", D, D, s);
-            w.w1_3 = e->tt.get_split3(w.prefix + "feed_forward.w_1.weight", F, D, s);
-            w.w2_3 = e->tt.get_split3(w.prefix + "feed_forward.w_2.weight", D, F, s);
-            if (!w.qkv_w3 || !w.out_w3 || !w.w1_3 || !w.w2_3) return -2;
-        }
     }
     if (e->x.ensure(sizeof(float) * M * D) || e->xn.ensure(sizeof(float) * M * (Dpad > D ? Dpad : D)) ||
         e->qkv.ensure(sizeof(float) * M * 3 * D) || e->mem.ensure(sizeof(float) * M * D) ||

@@ -7,8 +7,13 @@
 //
 // Load-time weight preparation has ONE home, the TensorTable: what the library computes from the caller's weights (folded BatchNorms,
 // repacked convolutions, scaled copies, constant tables) is stored with put_derived() beside them, served by get() / get_split2() like
-// any tensor, never writable through set(), and never counted by missing(); a family re-derives when `version` differs from the
-// one it prepared for. The helpers every family's preparation shares (host(), bn_fold(), dev_ln_bound(), require_all()) live there too.
+// any tensor, never writable through set(), and never counted by missing(). The helpers every family's preparation shares (host(),
+// bn_fold(), dev_ln_bound(), require_all()) live there too.
+//
+// Coherence has ONE rule, for every family: whatever is prepared from the weights (resolved pointers, planes, exponents, packs, folded
+// constants) carries a stamp of the table `version` it was made for and is made again when the stamp differs. The table moves the
+// version on every accepted set(), on replaced_in_place() and on a change of its structure, and drops the cached planes of exactly the
+// tensors that were written; a refused set() changes nothing. No entry point clears a flag, and nothing infers readiness from a pointer.
 //
 // Memory model: weights are copied once into library-owned HBM (repacked where a kernel wants a different
 // layout); activations live in a per-handle workspace that only grows (hipMalloc outside the steady state,
@@ -108,7 +113,11 @@ struct Tensor {
 
 struct TensorTable {
     std::map<std::string, Tensor> t;
-    unsigned long long version = 0;    // bumped by every set(): consumers that cache derived data (streaming f16x2 step) compare it
+    // Moved by every accepted set(), by replaced_in_place() and by a change of the table's structure after creation
+    // (pf_decoder_set_decoders2). THE coherence rule of the layer: whatever a family prepares from the weights keeps a stamp of the
+    // version it was made for and is made again when the stamp differs (NOT_PREPARED never equals a version).
+    unsigned long long version = 0;
+    static constexpr unsigned long long NOT_PREPARED = ~0ull;
     ~TensorTable() {
         for (auto& kv : t) if (kv.second.d) (void)hipFree(kv.second.d);
         for (auto& kv : b16) if (kv.second) (void)hipFree(kv.second);
@@ -148,12 +157,14 @@ struct TensorTable {
         auto it = t.find(name);
         if (it == t.end() || it->second.derived) { set_error(std::string("unknown tensor name: ") + name); return -1; }
         Tensor& x = it->second;
-        ++version;
         if (numel != x.numel) {
             set_error(std::string("tensor ") + name + ": expected " + std::to_string(x.numel) + " elements, got " +
                       std::to_string(numel));
             return -1;
         }
+        // accepted (a refused call changes nothing): the version moves and the planes of THIS tensor go, the others stay cached
+        ++version;
+        drop_planes(name);
         if (x.kind == 0) {
             PF_HIP_TRY(hipMemcpy(x.d, data, sizeof(float) * (size_t)numel, hipMemcpyDefault));
         } else if (x.kind == 1) {
@@ -223,13 +234,7 @@ struct TensorTable {
             return -2;
         }
         PF_HIP_TRY(hipMemcpy(it->second.d, v.data(), sizeof(float) * v.size(), hipMemcpyHostToDevice));
-        for (const char* suffix : {"", "#split2", "#split3"}) {
-            auto c = b16.find(name + suffix);
-            if (c == b16.end()) continue;
-            (void)hipFree(c->second);
-            b16.erase(c);
-            exp2.erase(name + suffix);
-        }
+        drop_planes(name);
         return 0;
     }
     // double scale / shift of the BatchNorm `p` (p + "weight|bias|running_mean|running_var"; affine = false: weight 1, bias 0)
@@ -245,14 +250,31 @@ struct TensorTable {
         }
         return true;
     }
-    // bf16 copy of a (repacked) tensor for the bf16-operand mode, made on first use and dropped when the fp32
-    // master changes
+    // bf16 copy of a (repacked) tensor for the bf16-operand mode, made on first use and dropped when set() overwrites
+    // the fp32 master
     std::map<std::string, unsigned short*> b16;
     std::map<std::string, int> exp2;    // exponents of the #split2 entries
     void drop_bf16() {
         for (auto& kv : b16) if (kv.second) (void)hipFree(kv.second);
         b16.clear();
         exp2.clear();
+    }
+    // the cached planes of one tensor (bf16 copy, #split2 with its exponent, #split3) go with its old contents
+    void drop_planes(const std::string& name) {
+        for (const char* suffix : {"", "#split2", "#split3"}) {
+            auto c = b16.find(name + suffix);
+            if (c == b16.end()) continue;
+            (void)hipFree(c->second);
+            b16.erase(c);
+            exp2.erase(name + suffix);
+        }
+    }
+    // the weights were rewritten behind the table's back (the data-parallel in-place broadcast): every tensor counts as set, the
+    // version moves, every plane goes
+    void replaced_in_place() {
+        for (auto& kv : t) kv.second.set = true;
+        ++version;
+        drop_bf16();
     }
     // the three bf16 planes [3][rows, cols] of a [rows, cols] weight (gemm_split3.hip); shares the b16 cache under a
     // suffixed key, so it is dropped with it
@@ -394,8 +416,13 @@ struct EncLayerW {
 struct Encoder {
     pf_encoder_config cfg;
     TensorTable tt;
-    std::vector<EncLayerW> layers;   // resolved lazily
-    bool resolved = false;
+    // What is prepared from the weights, each with the stamp of the table version it was made for (encoder_prepare): the resolved
+    // pointers of `layers`, and per arithmetic mode m = 1 .. 3 the planes in them (bf16 copies, bf16x3 planes, f16x2 planes with the
+    // a-priori exponents). One stamp per mode: a handle may serve an offline forward in one mode and a streaming session in gemm_mode 3
+    // at a time. Re-resolving rebuilds `layers` and clears the mode stamps.
+    std::vector<EncLayerW> layers;
+    unsigned long long resolved_for = TensorTable::NOT_PREPARED;
+    unsigned long long planes_for[4] = {TensorTable::NOT_PREPARED, TensorTable::NOT_PREPARED, TensorTable::NOT_PREPARED, TensorTable::NOT_PREPARED};
     DevBuf x, xn, qkv, mem, ctx, ffn, lens, pe;
     int pe_T = 0;
     // 0: fp32 MFMA everywhere; 1: bf16 operands for GEMMs + attention (throughput mode, bf16-class error);
@@ -513,7 +540,8 @@ struct Predictor {
     bool v3 = false;
     pf_predictor_v3_config c3{};
     DevBuf up, x_tm, pre, lstm_out, h_a, h_b, cell, tok_dev, ulens, pack, ts_lens;
-    bool packed = false;                 // pack = both directions' re-laid weight_hh, then bias_ih, bias_hh back to back
+    // pack = both directions' re-laid weight_hh, then bias_ih, bias_hh back to back; the table version it was copied for
+    unsigned long long packed_for = TensorTable::NOT_PREPARED;
     std::vector<int32_t> ul_host;
 };
 
@@ -532,7 +560,6 @@ struct DecLayerW {
     const unsigned short *w1_2 = nullptr, *w2_2 = nullptr, *q_2 = nullptr, *kv_2 = nullptr, *o_2 = nullptr;
     int ew_1 = 0, ew_2 = 0, ew_q = 0, ew_kv = 0, ew_o = 0, e_n1 = 0, e_fn = 0, e_n3 = 0, e_q = 0;
     float kv_l1b[4] = {0.f, 0.f, 0.f, 0.f};      // max row L1 norm and max |bias| of the k half, then of the v half, of linear_k_v
-    bool x2_ready = false;
 };
 
 
@@ -545,7 +572,10 @@ struct Decoder {
     int n_blocks2 = 0;       // decoders2: num_blocks - att_layer_num blocks of FFN + FSMN without cross-attention (decoder.py:363-380)
     std::vector<DecLayerW> layers2;
     DecLayerW last;          // decoders3.0 (FFN only)
-    bool resolved = false;
+    // stamps (decoder_prepare): the table version the resolved pointers were made for, and the one the f16x2 state was made for -- the
+    // planes and exponents of layers / layers2 / last, the kv_l1b constants uploaded to dlb, e_an and the vocabulary planes.
+    // Re-resolving clears the second. (The bf16 / bf16x3 planes are fetched from the table on every call and need no stamp.)
+    unsigned long long resolved_for = TensorTable::NOT_PREPARED, x2_for = TensorTable::NOT_PREPARED;
     DevBuf x, t1, t2, ffn, ffn2, q, kv, ctx, mem_lens, tok_lens, pval, pidx, hid;
     int precision = 0;       // 0 fp32, 1 bf16 operands (GEMMs + cross-attention), fp32 residual / LN statistics / FSMN
     DevBuf t16, ffn16, ffn2_16, q16, kv16, ctx16, mem16, hid16;
@@ -553,8 +583,7 @@ struct Decoder {
     DevBuf dscl, dlb;        // per layer {k_mul, v_mul, 1/k_mul, 1/v_mul} (device-chosen) and the constants they come from
     DevBuf k2, vt2;          // cross-attention operands written by the KV form of linear_k_v (attention_f16x2.hip)
     DevBuf splitk;           // streaming f16x2 step: split-K partials of the FFN's w_2
-    bool lb_uploaded = false;
-    int e_an = INT32_MIN;    // exponent of the after_norm output planes (f16x2 vocabulary projection)
+    int e_an = 0;            // exponent of the after_norm output planes (f16x2 vocabulary projection)
     DevBuf asf_p;            // SeACo score filter: attention probabilities of sequence 0 [H, N, T]
     // token packing (f16x2 greedy route): row offsets per sequence, packed row -> padded row map, packed ids
     DevBuf offs_dev, map_dev, ids_packed;
@@ -603,10 +632,10 @@ struct Stream {
     bool wide_k = false;                                     // long-K N = 512 projections of a <= 32-row step over four workgroups per tile
     DevBuf ws_part, ws_count;                                // their slice tiles and tile counters (GemmArgs.ws_part / ws_count)
     // constants c1 = W gamma, c2 = W beta + bias of every LayerNorm -> GEMM pair of the fp32 step (launch_ln_consts), prepared from
-    // the handles' weights (ln_ver_*: their TensorTable versions then). Encoder block l: [qkv c1, c2 | w_1 c1, c2]; decoder layer l
+    // the handles' weights (ln_ver_*: stamps, see ver_e / ver_d). Encoder block l: [qkv c1, c2 | w_1 c1, c2]; decoder layer l
     // (and decoders3 as layer n_blocks): [w_1 c1, c2 | w_2 c1, c2 | linear_q c1, c2]; then the vocabulary projection's c1, c2.
     DevBuf ln_consts;
-    uint64_t ln_ver_e = ~0ull, ln_ver_d = ~0ull;
+    unsigned long long ln_ver_e = TensorTable::NOT_PREPARED, ln_ver_d = TensorTable::NOT_PREPARED;
     DevBuf dec_ln_a, dec_ln_b, dec_ln_f;                     // decoder: block partials of the token rows (d_model wide twice, ffn wide)
     // f16x2 step, handles of <= 2048 rows (streams x largest window: most CUs idle): K = d_model projections in the four-slice split-K
     // form. 3 (default) = linear_out only -- its second launch computes norm2 and so REPLACES a launch: S = 64 7.91 -> 7.67 ms;
@@ -620,8 +649,12 @@ struct Stream {
     DevBuf kvcat_w, kvcat_b, kvcat_2;
     int kvcat_e = 0;
     bool kv_batched = true;                                  // fp32 step: the decoder's key/value projections of the encoder rows as one launch
-    unsigned long long ver_e = ~0ull, ver_d = ~0ull;         // TensorTable versions the prepared exponents / planes belong to
-    int e_mem = 0, e_an = 0;
+    // Stamps: the two handles' table versions the prepared exponents / planes belong to. Comparing them is ALL a step checks, by this
+    // invariant: the planes and the resolved pointers of a handle are freed or rebuilt only when its table version moves (set(),
+    // replaced_in_place(), encoder_prepare / decoder_prepare after such a move). While both stamps match, what the step reads in the
+    // handles is what was prepared for it -- whichever modes offline forwards on the same handles ran in between.
+    unsigned long long ver_e = TensorTable::NOT_PREPARED, ver_d = TensorTable::NOT_PREPARED;
+    int e_mem = 0;
     std::vector<int> e_ctx;                                  // per decoder layer: exponent of the cross-attention output planes
     DevBuf mem2;                                             // planes of the step's encoder output [2][S * Wmax, D]
     ~Stream() {
@@ -657,13 +690,14 @@ int fsmn(const FsmnArgs& a, hipStream_t s);
 int attention(const AttnArgs& a, double flops, hipStream_t s, bool x3 = false, int dk = 128, bool* appended = nullptr);
 int frontend_upload_tables(Frontend* f, const std::vector<float>& window, const std::vector<float>& mel);
 int frontend_default_tables(Frontend* f);
-int encoder_resolve(Encoder* e);
-int encoder_prepare_x2(Encoder* e, hipStream_t s);
+// resolve the weights and prepare the planes of arithmetic mode 0 .. 3 (0: nothing but resolving); a no-op while the stamps match
+int encoder_prepare(Encoder* e, int mode, hipStream_t s);
 int encoder_default_pe(Encoder* e, int T, hipStream_t s);
 int encoder_block(Encoder* e, const EncLayerW& w, float* x_in, int ld_in, float* x, int B, int T,
                          hipStream_t s, const EncChunkCtx* cc = nullptr, bool xn_ready = false, const EncLayerW* next = nullptr);
 std::string dec_layer_prefix(bool contextual, int n_blocks, int i);
-int decoder_resolve(Decoder* d);
+// resolve the weights and, with x2, prepare the f16x2 state; a no-op while the stamps match
+int decoder_prepare(Decoder* d, bool x2, hipStream_t s);
 int vocab_project(const float* hidden, int M, int D, const float* W, const float* bias, int V, float* logits,
                          int32_t* ids, DevBuf& pval, DevBuf& pidx, hipStream_t s);
 // C[M, N] = A W^T + bias (+ R1) (ReLU before the addend) in one of two modes. A is a_rows physical rows of `width` floats, viewed as M
@@ -677,7 +711,6 @@ int gemm3_simple(const unsigned short* A3, int lda, int M, const unsigned short*
 int gemm2_simple(const unsigned short* A2, int lda, int M, int ea, const unsigned short* W2, int ew, const float* bias,
                         float* C, int ldc, int N, int K, int relu, const float* R2, int ldr2, hipStream_t s,
                         const float* oscale_dev = nullptr, float* splitk_part = nullptr);
-int dec_layer_x2(Decoder* d, DecLayerW& w, const std::string& p, bool attn, hipStream_t s);
 struct FoldedLn { const float* g; const float* b; float* y; int out; float oscale; };   // out: 0 fp32 rows, 3 two fp16 planes of y * oscale
 int dec_ffn_x2(Decoder* d, const DecLayerW& w, const float* x, float* out, int M, hipStream_t s, float* splitk_part = nullptr,
                const FoldedLn* ln = nullptr, bool fold_fn = false);

@@ -21,8 +21,6 @@ static int stream_reset(Stream* st, hipStream_t s) {
 static int stream_prepare_x2(Stream* st, hipStream_t s) {
     Encoder* e = st->e; Decoder* d = st->d;
     int rc;
-    if (!e->resolved && (rc = encoder_resolve(e))) return rc;
-    if (!d->resolved && (rc = decoder_resolve(d))) return rc;
     const pf_decoder_config& dc = d->cfg;
     const int D = e->cfg.d_model;
     if (D / e->cfg.n_heads != 128 || D % 256 != 0 || e->cfg.ffn_dim % 256 != 0 || dc.ffn_dim % 256 != 0 || dc.d_model != D ||
@@ -30,20 +28,13 @@ static int stream_prepare_x2(Stream* st, hipStream_t s) {
         set_error("stream: gemm_mode 3 (f16x2) needs d_model / n_heads == 128, d_model % 256 == 0, ffn_dim % 256 == 0");
         return -1;
     }
-    if ((rc = encoder_prepare_x2(e, s))) return rc;
-    for (int l = 0; l < dc.n_blocks; ++l)
-        if ((rc = dec_layer_x2(d, d->layers[l], dec_layer_prefix(d->contextual, dc.n_blocks, l), true, s))) return rc;
-    if ((rc = dec_layer_x2(d, d->last, "decoders3.0.", false, s))) return rc;
-    float bmem, b;
+    if ((rc = encoder_prepare(e, 3, s)) || (rc = decoder_prepare(d, true, s))) return rc;
+    float bmem;
     if (TensorTable::dev_ln_bound(e->tt.get("after_norm.weight"), e->tt.get("after_norm.bias"), D, &bmem, s)) return -2;
     st->e_mem = exp_for_bound(bmem);
     st->e_ctx.assign((size_t)dc.n_blocks, 0);
     for (int l = 0; l < dc.n_blocks; ++l)      // |attention output| <= max |v|,  v = Wv m + bv
         st->e_ctx[l] = exp_for_bound(bmem * d->layers[l].kv_l1b[2] + d->layers[l].kv_l1b[3]);
-    if (TensorTable::dev_ln_bound(d->tt.get("after_norm.weight"), d->tt.get("after_norm.bias"), D, &b, s)) return -2;
-    st->e_an = exp_for_bound(b);
-    int ew_v = 0;
-    if (!d->tt.get_split2("output_layer.weight", dc.vocab_size, D, &ew_v, s)) return -2;
     // the layers' linear_k_v weights as one matrix (Stream.kvcat_*): rows [l * 2 D, (l + 1) * 2 D) = layer l
     if (dc.n_blocks > 0) {
         const size_t rows = (size_t)dc.n_blocks * 2 * D, n = rows * D;
@@ -60,27 +51,18 @@ static int stream_prepare_x2(Stream* st, hipStream_t s) {
     st->ver_e = e->tt.version; st->ver_d = d->tt.version;
     return 0;
 }
-static bool stream_x2_ready(const Stream* st) {
-    const Encoder* e = st->e; const Decoder* d = st->d;
-    if (!e->resolved || !d->resolved || st->ver_e != e->tt.version || st->ver_d != d->tt.version) return false;
-    for (auto& w : e->layers) if (!w.qkv_w2 || !w.out_w2 || !w.w1_2 || !w.w2_2) return false;
-    for (auto& w : d->layers) if (!w.x2_ready) return false;
-    return d->last.x2_ready && d->tt.b16.count("output_layer.weight#split2") != 0 && (int)st->e_ctx.size() == d->cfg.n_blocks;
-}
+static bool stream_x2_ready(const Stream* st) { return st->ver_e == st->e->tt.version && st->ver_d == st->d->tt.version; }
 
 // ---- constants of the fp32 step's LayerNorm -> GEMM pairs (Stream.ln_consts)
 static size_t ln_enc_stride(const Stream* st) { return 2 * ((size_t)3 * st->e->cfg.d_model + st->e->cfg.ffn_dim); }
 static size_t ln_dec_stride(const Stream* st) { return 2 * ((size_t)st->d->cfg.ffn_dim + 2 * st->d->cfg.d_model); }
 static size_t ln_dec_base(const Stream* st) { return ln_enc_stride(st) * st->e->layers.size(); }
 static size_t ln_voc_base(const Stream* st) { return ln_dec_base(st) + ln_dec_stride(st) * (st->d->cfg.n_blocks + 1); }
-static bool stream_ln_ready(const Stream* st) {
-    return st->ln_consts.p && st->e->resolved && st->d->resolved && st->ln_ver_e == st->e->tt.version && st->ln_ver_d == st->d->tt.version;
-}
+static bool stream_ln_ready(const Stream* st) { return st->ln_ver_e == st->e->tt.version && st->ln_ver_d == st->d->tt.version; }
 static int stream_prepare_ln_consts(Stream* st, hipStream_t s) {
     Encoder* e = st->e; Decoder* d = st->d;
     int rc;
-    if (!e->resolved && (rc = encoder_resolve(e))) return rc;
-    if (!d->resolved && (rc = decoder_resolve(d))) return rc;
+    if ((rc = encoder_prepare(e, 0, s)) || (rc = decoder_prepare(d, false, s))) return rc;
     const int D = e->cfg.d_model, F = e->cfg.ffn_dim, Fd = d->cfg.ffn_dim, V = d->cfg.vocab_size;
     if (st->ln_consts.ensure(sizeof(float) * (ln_voc_base(st) + 2 * (size_t)V))) return -2;
     float* base = st->ln_consts.as<float>();
@@ -275,7 +257,7 @@ static int stream_enqueue(Stream* st, int n, int is_final, int tail, hipStream_t
     }
     // ---- f16x2 step: the same in one GEMM over the concatenated weight planes (Stream.kvcat_*): layer l's K | V are columns
     // [l * 2 D, (l + 1) * 2 D) of a [rows, n_blocks * 2 D] result
-    const bool kv_cat = x2 && st->kv_batched && dc.n_blocks > 0 && st->kvcat_2.p;
+    const bool kv_cat = x2 && st->kv_batched && dc.n_blocks > 0;
     const int kv_ld = kv_cat ? dc.n_blocks * 2 * D : 2 * D;
     if (kv_cat) {
         if (d->kv.ensure(sizeof(float) * (size_t)S * st->Wmax * kv_ld)) return -2;
@@ -412,7 +394,7 @@ static int stream_enqueue(Stream* st, int n, int is_final, int tail, hipStream_t
     } else if (x2) {
         // decoders3's FFN; after_norm's planes (the vocabulary projection's operand) from the second launch of its split-K w_2
         const bool fold = st->ln_folded && dc.ffn_dim % 128 == 0;
-        const FoldedLn an{d->tt.get("after_norm.weight"), d->tt.get("after_norm.bias"), reinterpret_cast<float*>(t2p), 3, pow2f(st->e_an)};
+        const FoldedLn an{d->tt.get("after_norm.weight"), d->tt.get("after_norm.bias"), reinterpret_cast<float*>(t2p), 3, pow2f(d->e_an)};
         if ((rc = dec_ffn_x2(d, d->last, dx, t2, Mq, s, d->splitk.as<float>(), fold ? &an : nullptr, x2_fold_fn(st)))) return rc;
         an_folded = fold;
     } else if ((rc = dec_ffn(d, d->last, dx, t2, Mq, s))) return rc;
@@ -426,13 +408,13 @@ static int stream_enqueue(Stream* st, int n, int is_final, int tail, hipStream_t
         if (!an_folded) {
             ProfScope ps(PROF_LN, 8.0 * Mq * (double)D, s);
             if ((rc = launch_layernorm(t2, D, d->tt.get("after_norm.weight"), d->tt.get("after_norm.bias"), reinterpret_cast<float*>(t2p), D,
-                                       Mq, D, D, dc.ln_eps, s, 3, 0, (size_t)Mq * D, pow2f(st->e_an)))) return rc;
+                                       Mq, D, D, dc.ln_eps, s, 3, 0, (size_t)Mq * D, pow2f(d->e_an)))) return rc;
         }
         const int nparts = gemm_f16x2_argmax_parts(Mq, V);
         if (d->pval.ensure(sizeof(float) * (size_t)Mq * nparts) || d->pidx.ensure(sizeof(int) * (size_t)Mq * nparts)) return -2;
         Gemm2Args g{};
         g.A = t2p; g.lda = D; g.a_plane = (size_t)Mq * D; g.W = wv->second; g.ldw = D; g.w_plane = (size_t)V * D;
-        g.oscale = pow2f(-(st->e_an + ew_v)); g.bias = d->tt.get("output_layer.bias"); g.M = Mq; g.N = V; g.K = D;
+        g.oscale = pow2f(-(d->e_an + ew_v)); g.bias = d->tt.get("output_layer.bias"); g.M = Mq; g.N = V; g.K = D;
         g.amax_val = d->pval.as<float>(); g.amax_idx = d->pidx.as<int>(); g.amax_ld = nparts;
         {
             ProfScope ps(PROF_GEMM3, 2.0 * Mq * (double)V * D, s);
@@ -500,9 +482,7 @@ pf_stream* pf_stream_create(pf_encoder* eh, pf_predictor* ph, pf_decoder* dh, co
         set_error("stream: chunk_size[0] + chunk_size[2] == 0 is not supported (the reference's overlap window x[:, -0:] is the whole history in that geometry)");
         return nullptr;
     }
-    int rc;
-    if (!e->resolved && (rc = encoder_resolve(e))) return nullptr;
-    if (!d->resolved && (rc = decoder_resolve(d))) return nullptr;
+    if (encoder_prepare(e, 0, nullptr) || decoder_prepare(d, false, nullptr)) return nullptr;
     if (p->tt.require_all("predictor")) return nullptr;
     std::unique_ptr<Stream> st(new Stream());
     st->e = e; st->p = p; st->d = d; st->cfg = c;

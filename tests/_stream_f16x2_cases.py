@@ -164,6 +164,41 @@ def case_weight_reload_fp32_step(dev):
     case_weight_reload(dev, "fp32")
 
 
+def case_shared_encoder_handle(dev):
+    """One encoder handle serves an offline forward in fp32 and a gemm_mode 3 session at a time (StreamBatch runs over the model's
+    own handles): the planes of each mode carry their own version stamp, so both give BITWISE what handles that serve only one of
+    the two give -- before and after a weight reload on the live model"""
+    from funasr_amd.paraformer_streaming import StreamBatch
+    g, cfg, sd = load()
+    sd2 = synth.paraformer_state_dict(cfg, seed=int(g["seed"]) + 1, cif_bias=float(g["cif_bias"]))
+    feats = torch.from_numpy(g["feats_0"]).repeat(2, 1, 1).to(dev)
+    xs = (torch.randn(2, 40, 560, generator=torch.Generator().manual_seed(6)) * 0.7).to(dev)
+    xs[1, 33:] = 0
+
+    def offline(model):
+        return model.encoder.set_precision("fp32")(xs, [40, 33])[0].cpu()
+
+    def one_step(model, sb=None):
+        own = sb or StreamBatch(model, 2, [0, 10, 5], 4, 1, use_graph=False, precision="f16x2")
+        ids, enc = own.step(feats, return_enc=True)
+        if sb is None:
+            own.close()
+        return ids, enc.cpu()
+
+    model = build(cfg, sd, dev)
+    sb = StreamBatch(model, 2, [0, 10, 5], 4, 1, use_graph=True, precision="f16x2")
+    got = [(offline(model), one_step(model, sb))]
+    model.load_state_dict(sd2, strict=False)
+    sb.reset()
+    got.append((offline(model), one_step(model, sb)))
+    sb.close()
+    for (off, (ids, enc)), weights in zip(got, (sd, sd2)):
+        assert torch.equal(off, offline(build(cfg, weights, dev))), "offline fp32 forward on the shared handle"
+        rids, renc = one_step(build(cfg, weights, dev))
+        assert ids == rids and torch.equal(enc, renc), "gemm_mode 3 step on the shared handle"
+    assert not torch.equal(got[0][0], got[1][0])
+
+
 def case_oracle_geometry_many_tokens(dev):
     """chunk_size [0, 20, 10] (up to 42 fires per step) against the reference-pinned streaming oracle"""
     from funasr_amd.paraformer_streaming import StreamBatch

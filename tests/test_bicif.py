@@ -129,6 +129,39 @@ def test_predictor_v3_on_the_gpu_equals_reference_golden(cuda):
 
 
 @pytest.mark.gpu
+def test_blstm_pack_of_the_timestamp_head_follows_a_weight_reload(cuda):
+    """pf_predictor_timestamp keeps both directions' recurrent weights and biases in one packed buffer: after the blstm.* tensors are
+    replaced on the live handle the upsampled alphas and peaks are BITWISE those of a fresh predictor with the same weights"""
+    from funasr_amd.cif_predictor import CifPredictorV3
+    from oracle import bicif_oracle as BO
+    g = _gold()
+    cfg = json.loads(str(g["blstm_cfg"]))
+    assert cfg["upsample_type"] == "cnn_blstm"
+    sd_a = BO.predictor_v3_state_dict(cfg, seed=int(g["blstm_seed"]), cif_bias=-0.6)
+    sd_b = BO.predictor_v3_state_dict(cfg, seed=int(g["blstm_seed"]) + 1, cif_bias=-0.6)
+    mixed = {k: (sd_b[k] if k.startswith("blstm.") else v) for k, v in sd_a.items()}
+    assert any(k.startswith("blstm.") for k in mixed)
+    hidden, lens = _t(g, "blstm_hidden").to(cuda), _t(g, "blstm_lens")
+
+    def stamps(pred):
+        tok = pred(hidden, lengths=lens)[1]
+        _, _, usa, usp = pred.get_upsample_timestamp(hidden, None, tok.round().long(), lengths=lens)
+        return usa.cpu(), usp.cpu()
+
+    live = CifPredictorV3(**cfg)
+    live.load_state_dict(sd_a, strict=True)
+    live = live.to(cuda)
+    before = stamps(live)
+    live.load_state_dict(mixed, strict=True)
+    got = stamps(live)
+    fresh = CifPredictorV3(**cfg)
+    fresh.load_state_dict(mixed, strict=True)
+    want = stamps(fresh.to(cuda))
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+    assert not torch.equal(got[0], before[0])
+
+
+@pytest.mark.gpu
 def test_predictor_halves_with_two_batches_in_flight_are_bitwise_forward(cuda):
     """pf_predictor_alphas_begin / pf_predictor_embeds_slot (CifPredictorV2.forward_begin / forward_finish, V3 through the same
     entry points): begin(A), begin(B), finish(A), finish(B) -- both scan states alive at once -- give what forward(A), forward(B) give"""

@@ -378,6 +378,160 @@ def test_decoder_with_decoders2_bf16_mode_close_to_reference(cuda):
         assert dd.mean().item() < 0.03 * ref[b, :n].abs().mean().item()       # bf16 operands: the bar of the other bf16-mode tests
 
 
+# ---------------------------------------------------------------------- weights replaced on a live handle
+# Everything a handle prepares from its weights (resolved pointers, bf16 / bf16x3 / f16x2 planes, a-priori exponents, uploaded
+# bounds) follows the tensor table's version: after any write the live handle gives BITWISE what a fresh module built from the
+# same weights gives, in every arithmetic mode. Tiny Paraformer (2 + 2 blocks, vocabulary 97: the smallest sizes every mode
+# accepts), batch 2 with 40 and 33 frames (a padded row and a partial 16-row slot), weight sets A (seed 31) and B (seed 32).
+_MODES = ("fp32", "bf16", "bf16x3", "f16x2")
+_TINY = synth.tiny(synth.PARAFORMER_LARGE)
+_LIVE_LENS = torch.tensor([40, 33], dtype=torch.int32)
+
+
+def _live_sd(kind, seed, cfg=None):
+    if kind == "enc":
+        return synth.encoder_state_dict(cfg or _TINY["encoder"], seed=seed)
+    return synth.decoder_state_dict(cfg or _TINY["decoder"], seed=seed, with_embed=True)
+
+
+def _enc_out(enc, mode, cuda):
+    g = torch.Generator().manual_seed(41)
+    xs = torch.randn(2, 40, 560, generator=g) * 0.7
+    xs[1, 33:] = 0
+    return enc.set_precision(mode)(xs.to(cuda), _LIVE_LENS)[0].cpu()
+
+
+_fresh_cache = {}
+
+
+def _fresh_enc_b(mode, cuda):
+    """a fresh encoder with the weights B in `mode` (computed once, shared by the cases)"""
+    if ("enc", mode) not in _fresh_cache:
+        _fresh_cache[("enc", mode)] = _enc_out(_encoder(_TINY["encoder"], _live_sd("enc", 32), cuda), mode, cuda)
+    return _fresh_cache[("enc", mode)]
+
+
+@pytest.mark.parametrize("mode", _MODES)
+def test_encoder_follows_a_weight_reload_in_every_mode(cuda, mode):
+    enc = _encoder(_TINY["encoder"], _live_sd("enc", 31), cuda)
+    a = _enc_out(enc, mode, cuda)
+    enc.load_state_dict(_live_sd("enc", 32), strict=True)
+    b = _enc_out(enc, mode, cuda)
+    assert torch.equal(b, _fresh_enc_b(mode, cuda)) and not torch.equal(a, b)
+    for m in [x for x in _MODES if x != mode] + [mode]:               # the live handle through the other modes and back
+        assert torch.equal(_enc_out(enc, m, cuda), _fresh_enc_b(m, cuda)), (mode, m)
+
+
+def _set_on_handle(mod, name, value, cuda):
+    from funasr_amd import _lib
+    v = value.to(device=cuda, dtype=torch.float32).contiguous()
+    torch.cuda.synchronize()
+    _lib.check(getattr(_lib.load(), mod._prefix + "_set_tensor")(mod._handle, name.encode(), v.data_ptr(), v.numel()), "set_tensor " + name)
+
+
+@pytest.mark.parametrize("name", ["encoders.0.feed_forward.w_1.weight", "encoders0.0.norm1.weight"])
+def test_encoder_one_tensor_written_on_the_handle(cuda, name):
+    """f16x2: a GEMM weight (its own planes are stale, every other plane survives) and a LayerNorm gamma (no plane is touched, the
+    exponents beside the surviving planes move)"""
+    sd_a, sd_b = _live_sd("enc", 31), _live_sd("enc", 32)
+    enc = _encoder(_TINY["encoder"], sd_a, cuda)
+    before = _enc_out(enc, "f16x2", cuda)
+    _set_on_handle(enc, name, sd_b[name], cuda)
+    got = _enc_out(enc, "f16x2", cuda)
+    mixed = dict(sd_a)
+    mixed[name] = sd_b[name]
+    assert torch.equal(got, _enc_out(_encoder(_TINY["encoder"], mixed, cuda), "f16x2", cuda)) and not torch.equal(got, before)
+
+
+def test_refused_writes_do_not_disturb_an_encoder_handle(cuda):
+    from funasr_amd import _lib
+    sd = _live_sd("enc", 31)
+    enc = _encoder(_TINY["encoder"], sd, cuda)
+    before = _enc_out(enc, "f16x2", cuda)
+    with pytest.raises(_lib.HipRuntimeError, match="unknown tensor name"):
+        _set_on_handle(enc, "encoders.7.norm1.weight", sd["encoders.0.norm1.weight"], cuda)
+    with pytest.raises(_lib.HipRuntimeError, match="expected 512 elements, got 511"):
+        _set_on_handle(enc, "encoders.0.norm1.weight", sd["encoders.0.norm1.weight"][:511], cuda)
+    assert torch.equal(_enc_out(enc, "f16x2", cuda), before)
+    assert _lib.load().pf_encoder_missing(enc._handle) == 0
+
+
+def test_forward_on_an_incomplete_encoder_handle_names_the_tensor(cuda):
+    from funasr_amd import _lib
+    enc = _encoder(_TINY["encoder"], _live_sd("enc", 31), cuda)
+    enc._skip_keys = ("encoders.0.norm2.bias",)                       # every tensor reaches the handle but this one
+    with pytest.raises(_lib.HipRuntimeError, match=r"status -3: encoder: tensor not set: encoders\.0\.norm2\.bias"):
+        _enc_out(enc, "f16x2", cuda)
+    assert _lib.load().pf_encoder_missing(enc._handle) == 1
+    enc._skip_keys = ()
+    enc.mark_dirty()
+    assert torch.equal(_enc_out(enc, "f16x2", cuda), _enc_out(_encoder(_TINY["encoder"], _live_sd("enc", 31), cuda), "f16x2", cuda))
+
+
+def _decoder(cfg, sd, cuda):
+    from funasr_amd.paraformer_decoder import ParaformerSANMDecoder
+    d = ParaformerSANMDecoder(**cfg)
+    d.load_state_dict(sd, strict=True)
+    return d.to(cuda)
+
+
+def _dec_out(d, mode, cuda):
+    """(ids of the greedy route, hidden states of the hidden_out route; bf16: its greedy route only), valid token rows"""
+    g = torch.Generator().manual_seed(43)
+    tok = [7, 5]
+    args = ((torch.randn(2, 40, 512, generator=g) * 0.5).to(cuda), _LIVE_LENS, (torch.randn(2, 7, 512, generator=g) * 0.5).to(cuda),
+            torch.tensor(tok, dtype=torch.int32))
+    d.set_precision(mode)
+    ids = d.greedy(*args)[0].cpu()
+    hid = None if mode == "bf16" else d(*args, return_hidden=True)[0].cpu()
+    return [(ids[b, :n], None if hid is None else hid[b, :n]) for b, n in enumerate(tok)]
+
+
+def _same(x, y):
+    return all(torch.equal(a[0], b[0]) and (a[1] is None or torch.equal(a[1], b[1])) for a, b in zip(x, y))
+
+
+def _fresh_dec_b(mode, cuda):
+    if ("dec", mode) not in _fresh_cache:
+        _fresh_cache[("dec", mode)] = _dec_out(_decoder(_TINY["decoder"], _live_sd("dec", 32), cuda), mode, cuda)
+    return _fresh_cache[("dec", mode)]
+
+
+@pytest.mark.parametrize("mode", _MODES)
+def test_decoder_follows_a_weight_reload_in_every_mode(cuda, mode):
+    """f16x2: the packed greedy route (ids only) and the hidden_out route"""
+    d = _decoder(_TINY["decoder"], _live_sd("dec", 31), cuda)
+    a = _dec_out(d, mode, cuda)
+    d.load_state_dict(_live_sd("dec", 32), strict=True)
+    b = _dec_out(d, mode, cuda)
+    assert _same(b, _fresh_dec_b(mode, cuda)) and not _same(a, b)
+    for m in [x for x in _MODES if x != mode] + [mode]:
+        assert _same(_dec_out(d, m, cuda), _fresh_dec_b(m, cuda)), (mode, m)
+
+
+@pytest.mark.parametrize("name", ["decoders.0.src_attn.linear_k_v.weight", "after_norm.weight"])
+def test_decoder_one_tensor_written_on_the_handle(cuda, name):
+    """f16x2: linear_k_v feeds the bounds uploaded for the device-chosen K / V scales, after_norm the exponent of the vocabulary
+    projection's operand planes"""
+    sd_a, sd_b = _live_sd("dec", 31), _live_sd("dec", 32)
+    d = _decoder(_TINY["decoder"], sd_a, cuda)
+    _dec_out(d, "f16x2", cuda)
+    _set_on_handle(d, name, sd_b[name], cuda)
+    mixed = dict(sd_a)
+    mixed[name] = sd_b[name]
+    assert _same(_dec_out(d, "f16x2", cuda), _dec_out(_decoder(_TINY["decoder"], mixed, cuda), "f16x2", cuda))
+
+
+def test_decoder_with_decoders2_follows_a_weight_reload(cuda):
+    cfg = dict(_TINY["decoder"], num_blocks=2, att_layer_num=1)
+    d = _decoder(cfg, _live_sd("dec", 31, cfg), cuda)
+    assert d.decoders2 is not None and len(d.decoders2) == 1
+    a = _dec_out(d, "f16x2", cuda)
+    d.load_state_dict(_live_sd("dec", 32, cfg), strict=True)
+    b = _dec_out(d, "f16x2", cuda)
+    assert _same(b, _dec_out(_decoder(cfg, _live_sd("dec", 32, cfg), cuda), "f16x2", cuda)) and not _same(a, b)
+
+
 # ---------------------------------------------------------------------------------------------------- pipeline
 def test_pipeline_token_ids_equal_reference(cuda, f32_mode):
     from funasr_amd.paraformer import Paraformer
