@@ -20,6 +20,15 @@ namespace pf {
 
 namespace {
 
+// A product rounded to fp32 that no later sum may absorb. hip's __fmul_rn is a plain `*` compiled under the default
+// -ffp-contract=fast, so `frame + __fmul_rn(cur, h)` became one v_fmac_f32 in cif_emit_loop_kernel: not the reference's product
+// and sum, each rounded (`cif`, bicif_paraformer/cif_predictor.py:70). With contraction off here the product carries no
+// permission to fuse, whatever kernel it is inlined into.
+__device__ __forceinline__ float mul_rn(const float a, const float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+
 __global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ h, float* __restrict__ out, int B,
                                                      int T, int D4, int l_order, int taps) {
     // one thread per float4 of the output row [taps * D]
@@ -59,7 +68,7 @@ __global__ __launch_bounds__(256) void alpha_kernel(AlphaArgs p) {
     if (lane == 0) {
         const float z = s + p.bias[0];
         float a = 1.0f / (1.0f + expf(-z));
-        a = fmaxf(__fsub_rn(__fmul_rn(a, p.smooth), p.noise), 0.f);
+        a = fmaxf(__fsub_rn(mul_rn(a, p.smooth), p.noise), 0.f);
         if (t >= p.lens[b]) a = 0.f;
         p.alphas[(size_t)b * p.T_ext + t] = a;
     }
@@ -226,11 +235,11 @@ __global__ __launch_bounds__(256) void cif_emit_loop_kernel(CifEmitArgs p) {
         for (int j = 0; j < 8; ++j) {
             const int t = t0 + j;
             if (t >= Te) break;
-            frame = __fadd_rn(frame, __fmul_rn(s_cur[t], hv[j]));
+            frame = __fadd_rn(frame, mul_rn(s_cur[t], hv[j]));
             if (s_ff[t]) {
                 if (k < p.N) out[(size_t)k * p.D] = frame;
                 ++k;
-                frame = __fmul_rn(s_rm[t], hv[j]);
+                frame = mul_rn(s_rm[t], hv[j]);
             }
         }
     }
@@ -276,11 +285,11 @@ __global__ __launch_bounds__(256) void cif_emit_kernel(CifEmitArgs p) {
             const int t = t0 + j;
             if (t >= Te) break;
             const float a = staged ? s_al[t] : al[t];
-            const float prod = __fmul_rn(a, hv[j]);
+            const float prod = mul_rn(a, hv[j]);
             acc += (double)prod;
             const float P = (float)acc;
             if (staged ? s_ff[t] : ff[t]) {
-                const float remh = __fmul_rn(staged ? s_rm[t] : rm[t], hv[j]);
+                const float remh = mul_rn(staged ? s_rm[t] : rm[t], hv[j]);
                 // frames - shift_frames + shift_remain_frames - remain_frames, left to right (cif_predictor.py:896)
                 const float v = __fsub_rn(__fadd_rn(__fsub_rn(P, prevP), prev_remh), remh);
                 if (k < p.N) out[(size_t)k * p.D] = v;
@@ -313,7 +322,7 @@ __global__ __launch_bounds__(256) void argmax_reduce_kernel(const float* __restr
         if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
     }
     if (lane == 0) {
-        ids[row] = bi;
+        ids[row] = bi == 0x7fffffff ? 0 : bi;     // nothing exceeded -inf: every value is -inf, the first column (torch.argmax)
         if (best) best[row] = bv;
     }
 }
@@ -354,7 +363,7 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
 #pragma unroll
         for (int w = 1; w < 4; ++w)
             if (sv[w] > bv || (sv[w] == bv && si[w] < bi)) { bv = sv[w]; bi = si[w]; }
-        ids[row] = bi;
+        ids[row] = bi == 0x7fffffff ? 0 : bi;     // a row of -inf only: no value was accepted, the first column (torch.argmax)
     }
 }
 

@@ -422,6 +422,46 @@ int pf_k_cif(const float* alphas, const float* hidden, int32_t B, int32_t T, int
     PF_HIP_TRY(hipStreamSynchronize(s));   // `lens` is a host temporary
     return 0;
 }
+/* pf_k_cif with the utterance lengths and the tail of the predictors: the launches predictor_alphas_enqueue /
+ * predictor_embeds_slot make after alpha_kernel, on caller-provided alphas (loop = 0: CifPredictorV2, 1: CifPredictorV3) */
+int pf_k_cif_tail(const float* alphas, const float* hidden, const int32_t* lens_host, int32_t B, int32_t T, int32_t D, int32_t N,
+                  float tail_threshold, int32_t tail_mask, int32_t loop, float* alphas_out, float* peaks, int32_t* n_fires,
+                  int32_t* n_tok, float* embeds, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    PF_REQUIRE(alphas && hidden && lens_host && alphas_out && peaks && n_fires && embeds && B > 0 && T > 0 && D > 0 && N >= 0,
+               "k_cif_tail: null/empty");
+    PF_REQUIRE(!loop || n_tok, "k_cif_tail: the loop form reports n_tok");
+    for (int b = 0; b < B; ++b) PF_REQUIRE(lens_host[b] >= 1 && lens_host[b] <= T, "k_cif_tail: lens out of range");
+    static DevBuf rm, ff, cu, ln;
+    const int Te = T + 1;
+    if (rm.ensure(sizeof(float) * (size_t)B * Te) || ff.ensure(sizeof(int) * (size_t)B * Te) ||
+        (loop && cu.ensure(sizeof(float) * (size_t)B * Te)) || ln.ensure(sizeof(int) * (size_t)B)) return -2;
+    if (upload_h2d(ln.p, lens_host, sizeof(int) * B, s)) return -2;
+    PF_HIP_TRY(hipMemcpy2DAsync(alphas_out, sizeof(float) * Te, alphas, sizeof(float) * T, sizeof(float) * T, B,
+                                hipMemcpyDeviceToDevice, s));
+    CifScanArgs sa{};
+    sa.alphas = alphas_out; sa.peaks = peaks; sa.rems = rm.as<float>(); sa.fire_flag = ff.as<int>();
+    sa.n_fires = n_fires; sa.lens = ln.as<int>(); sa.B = B; sa.T = T; sa.tail_threshold = tail_threshold; sa.tail_mask = tail_mask;
+    CifEmitArgs ea{};
+    ea.hidden = hidden; ea.alphas = alphas_out; ea.rems = rm.as<float>(); ea.fire_flag = ff.as<int>();
+    ea.embeds = embeds; ea.B = B; ea.T = T; ea.D = D; ea.N = N;
+    int rc;
+    if (loop) {
+        if ((rc = launch_cif_scan_loop(sa, cu.as<float>(), n_tok, s))) return rc;
+        ea.alphas = cu.as<float>();
+        if (N > 0 && (rc = launch_cif_emit_loop(ea, s))) return rc;
+    } else {
+        if ((rc = launch_cif_scan(sa, s))) return rc;
+        if ((rc = launch_cif_emit(ea, s))) return rc;
+    }
+    PF_HIP_TRY(hipStreamSynchronize(s));   // the upload reads the caller's host array
+    return 0;
+}
+/* ids[row] = the first column of the largest value of x[row, 0 .. N) (row stride ldx), like torch.argmax */
+int pf_k_argmax_rows(const float* x, int32_t ldx, int32_t M, int32_t N, int32_t* ids, void* stream) {
+    PF_REQUIRE(x && ids && M > 0 && N > 0 && ldx >= N, "k_argmax_rows: null/empty");
+    return launch_argmax_rows(x, ldx, M, N, ids, reinterpret_cast<hipStream_t>(stream));
+}
 int pf_k_gemm_f32_time(const float* A, int32_t lda, const float* W, int32_t ldw, const float* bias, float* C,
                        int32_t ldc, int32_t M, int32_t N, int32_t K, int32_t iters, float* ms_out, void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);

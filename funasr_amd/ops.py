@@ -226,6 +226,40 @@ def cif(alphas: torch.Tensor, hidden: torch.Tensor, n_max: int):
     return peaks, nf, emb
 
 
+def cif_tail(alphas: torch.Tensor, hidden: torch.Tensor, lens, n_max: int, tail_threshold: float = 0.0, tail_mask: bool = True,
+             loop: bool = False):
+    """The scan and emit launches of the predictors on given weights (pf_k_cif_tail): alphas [B, T] (zero at t >= lens[b]),
+    hidden [B, T, D], lens [B] host integers; loop False: CifPredictorV2's prefix-sum form, True: CifPredictorV3's sequential
+    fp32 form. -> (alphas [B, T+1] with the tail in place, peaks [B, T+1], n_fires int32 [B], n_tok int32 [B] or None,
+    embeds [B, n_max, D])."""
+    lib = _lib.load()
+    _f32c(alphas, "alphas"), _f32c(hidden, "hidden")
+    B, T = alphas.shape
+    D = hidden.shape[2]
+    dev = alphas.device
+    lens_c = (C.c_int32 * B)(*[int(v) for v in lens])
+    al = torch.empty(B, T + 1, device=dev, dtype=torch.float32)
+    peaks = torch.empty(B, T + 1, device=dev, dtype=torch.float32)
+    nf = torch.empty(B, device=dev, dtype=torch.int32)
+    ntok = torch.empty(B, device=dev, dtype=torch.int32) if loop else None
+    emb = torch.empty(B, n_max, D, device=dev, dtype=torch.float32)
+    _lib.check(lib.pf_k_cif_tail(_ptr(alphas.contiguous()), _ptr(hidden.contiguous()), lens_c, B, T, D, n_max, float(tail_threshold),
+                                 int(bool(tail_mask)), int(bool(loop)), _ptr(al), _ptr(peaks), _ptr(nf), _ptr(ntok), _ptr(emb),
+                                 _stream()), "pf_k_cif_tail")
+    return al, peaks, nf, ntok, emb
+
+
+def argmax_rows(x: torch.Tensor) -> torch.Tensor:
+    """x [M, N] fp32 (a row-strided view is taken as it is) -> int32 [M]: the first column of each row's maximum."""
+    lib = _lib.load()
+    _f32c(x, "x")
+    M, N = x.shape
+    assert x.stride(1) == 1
+    ids = torch.empty(M, device=x.device, dtype=torch.int32)
+    _lib.check(lib.pf_k_argmax_rows(_ptr(x), x.stride(0), M, N, _ptr(ids), _stream()), "pf_k_argmax_rows")
+    return ids
+
+
 def gemm_time_ms(a, w, bias, out, iters: int = 20) -> float:
     lib = _lib.load()
     M, K = a.shape

@@ -764,6 +764,18 @@ int pf_k_lstm(const float* x, const float* w_ih, const float* w_hh, const float*
  * [B, T, D] -> peaks [B, T] (= "fires"), n_fires int32 [B], embeds [B, N, D] (rows >= n_fires[b] zero). */
 int pf_k_cif(const float* alphas, const float* hidden, int32_t B, int32_t T, int32_t D, int32_t N, float* peaks,
              int32_t* n_fires, float* embeds, void* stream);
+/* the same with the utterance lengths and the tail of the predictors (tail_process_fn, cif_predictor.py:414-446), through the
+ * launches the predictor handles make after their alpha kernel: alphas [B, T] with zeros at t >= lens_host[b] (host int32, 1 ..
+ * T), tail_threshold > 0 adds it at index lens[b] (tail_mask) or T. loop = 0: the prefix-sum scan of CifPredictorV2 (any T);
+ * loop = 1: the sequential fp32 `cif` of CifPredictorV3 (bicif_paraformer/cif_predictor.py:39-86; T <= 4095, refused beyond).
+ * -> alphas_out [B, T+1] as the scan leaves them, peaks [B, T+1], n_fires int32 [B], n_tok int32 [B] (loop form only:
+ * floor(sum alphas); may be NULL otherwise), embeds [B, N, D] (fires past N dropped, rows >= n_fires[b] zero). Synchronises. */
+int pf_k_cif_tail(const float* alphas, const float* hidden, const int32_t* lens_host, int32_t B, int32_t T, int32_t D, int32_t N,
+                  float tail_threshold, int32_t tail_mask, int32_t loop, float* alphas_out, float* peaks, int32_t* n_fires,
+                  int32_t* n_tok, float* embeds, void* stream);
+/* ids[row] = first column of the largest of x[row, 0 .. N) (row stride ldx >= N), as torch.argmax (a row of -inf only: 0; NaN
+ * unspecified): the arg-max of the streaming decoder and of the vocabulary projection when logits are requested */
+int pf_k_argmax_rows(const float* x, int32_t ldx, int32_t M, int32_t N, int32_t* ids, void* stream);
 /* average kernel time in milliseconds of `iters` back-to-back launches of the GEMM above, measured with
  * hipEvents on `stream` (used by bench.py for the roofline line) */
 int pf_k_gemm_f32_time(const float* A, int32_t lda, const float* W, int32_t ldw, const float* bias, float* C,

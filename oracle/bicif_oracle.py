@@ -109,10 +109,8 @@ def predictor_v3(hidden: Tensor, lens: Tensor, sd: SD, cfg: dict, prefix: str = 
     token_num = alphas.sum(-1)
     tail = cfg.get("tail_threshold", 0.0)
     if tail > 0.0:                                                   # tail_process_fn (:354-383), always with the mask
-        zeros = torch.zeros(B, 1)
-        tmask = torch.cat([torch.ones(B, 1), mask], 1) - torch.cat([mask, zeros], 1)
-        alphas = torch.cat([alphas, zeros], 1) + tmask * tail
-        hidden = torch.cat([hidden, torch.zeros(B, 1, D)], 1)
+        from oracle.paraformer_oracle import cif_tail
+        alphas, hidden = cif_tail(alphas, hidden, lens, tail, True)
         token_num = torch.floor(alphas.sum(-1))
     embeds, peaks = cif_loop(hidden, alphas, cfg.get("threshold", 1.0))
     if tail > 0.0:

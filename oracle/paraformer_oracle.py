@@ -380,6 +380,21 @@ def cif_frames(hidden: Tensor, alphas: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
     return out, fires, n_fired
 
 
+def cif_tail(alphas: Tensor, hidden: Tensor, lens: Tensor, tail: float, tail_mask: bool = True) -> Tuple[Tensor, Tensor]:
+    """tail_process_fn, funasr/models/paraformer/cif_predictor.py:414-446, on given weights: alphas [B, T] (zero beyond lens),
+    hidden [B, T, D] -> (alphas [B, T+1] with `tail` added at index lens[b] (tail_mask) or as the appended column T, hidden
+    [B, T+1, D] with a zero row appended)."""
+    B, T, D = hidden.shape
+    zeros = torch.zeros(B, 1)
+    if tail_mask:
+        mask = (torch.arange(T)[None, :] < lens[:, None].to(torch.int64)).float()
+        tmask = torch.cat([torch.ones(B, 1), mask], 1) - torch.cat([mask, zeros], 1)
+        alphas = torch.cat([alphas, zeros], 1) + tmask * tail
+    else:
+        alphas = torch.cat([alphas, torch.full((B, 1), tail)], 1)
+    return alphas, torch.cat([hidden, torch.zeros(B, 1, D)], 1)
+
+
 def cif_predictor(hidden: Tensor, lens: Tensor, sd: SD, cfg: dict, prefix: str = ""):
     """CifPredictorV2.forward at inference (target_label None), funasr/models/paraformer/cif_predictor.py:253-314
     + tail_process_fn :414-446. hidden [B, T, D], lens [B].
@@ -396,13 +411,7 @@ def cif_predictor(hidden: Tensor, lens: Tensor, sd: SD, cfg: dict, prefix: str =
     token_num = alphas.sum(-1)
     tail = cfg.get("tail_threshold", 0.0)
     if tail > 0.0:
-        zeros = torch.zeros(B, 1)
-        if cfg.get("tail_mask", True):
-            tmask = torch.cat([torch.ones(B, 1), mask], 1) - torch.cat([mask, zeros], 1)
-            alphas = torch.cat([alphas, zeros], 1) + tmask * tail
-        else:
-            alphas = torch.cat([alphas, torch.full((B, 1), tail)], 1)
-        hidden = torch.cat([hidden, torch.zeros(B, 1, D)], 1)
+        alphas, hidden = cif_tail(alphas, hidden, lens, tail, cfg.get("tail_mask", True))
         token_num = torch.floor(alphas.sum(-1))
     embeds, peaks, _ = cif_frames(hidden, alphas)
     if tail > 0.0:
