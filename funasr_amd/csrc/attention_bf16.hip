@@ -4,15 +4,11 @@
 //
 // Reference semantics: funasr/models/sanm/attention.py:270-306,322-327 (scores, key mask -inf, softmax, mask 0, .V).
 //
-// One workgroup = 4 waves = 128 queries of one (sequence, head); each wave owns 32 queries x d_k. Both products are
-// issued "swapped" so a lane owns ONE query (q = lane & 31):
-//   S^T[key][q] = sum_d K[key][d] Q[q][d]     A = K tile rows (LDS, 16-B chunks XOR-swizzled by key & 15), B = Q (regs)
-//   O^T[d][q]   = sum_key V[key][d] P[q][key] A = V^T (LDS, transposed while staging), B = P
-// The MFMA k index is only a pairing between A and B: for the second product the k slots of half-wave h are exactly
-// the keys whose scores that lane's accumulator registers already hold (key = (r&3) + 8(r>>2) + 4h), so P goes from
-// the S^T accumulator to the B operand with a register-local f32 -> bf16 pack, no cross-lane traffic, and V^T is read
-// as two 8-B LDS reads per MFMA.
-#include "common.h"
+// One workgroup = 4 waves = 128 queries of one (sequence, head); each wave owns 32 queries x d_k, in the mapping of
+// attention_tile.h: A = K tile rows (LDS, 16-B chunks XOR-swizzled by key & 15) for S^T and V^T (LDS, transposed while staging)
+// for O^T. P goes from the S^T accumulator to the B operand with a register-local f32 -> bf16 pack, and V^T is read as two
+// 8-B LDS reads per MFMA.
+#include "attention_tile.h"
 
 namespace pf {
 
@@ -53,10 +49,7 @@ __global__ __launch_bounds__(256, 2) void attention_bf16_kernel(AttnArgs p) {
     }
 
     floatx16 o[4];
-#pragma unroll
-    for (int d = 0; d < 4; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
+    tile_zero(o);
     float m_run = -INFINITY, l_run = 0.f;
 
     // tile loaders. K: chunk-fastest (coalesced 256-B rows); V: key-fastest (conflict-free transposed LDS writes)
@@ -103,30 +96,10 @@ __global__ __launch_bounds__(256, 2) void attention_bf16_kernel(AttnArgs p) {
             s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kv), qf[st], s, 0, 0, 0);
         }
 
-        // ---- online softmax for query (lane & 31); this lane holds keys k0 + (r&3) + 8(r>>2) + 4h
-        float mx = -INFINITY;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-            s[r] = key < klen ? s[r] * p.scale : -INFINITY;     // (q * d_k^-0.5) . k == (q . k) * d_k^-0.5
-            mx = fmaxf(mx, s[r]);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run, mx);
-        const float alpha = expf(m_run - m_new);
-        float psum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            s[r] = expf(s[r] - m_new);
-            psum += s[r];
-        }
-        psum += __shfl_xor(psum, 32, 64);
-        l_run = l_run * alpha + psum;
-        m_run = m_new;
-#pragma unroll
-        for (int d = 0; d < 4; ++d)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
+        for (int r = 0; r < 16; ++r)
+            s[r] = k0 + tile_key(r, hh) < klen ? s[r] * p.scale : -INFINITY;     // (q * d_k^-0.5) . k == (q . k) * d_k^-0.5
+        tile_softmax<4, false>(s, m_run, l_run, o);
 
         // ---- O^T += V^T P^T. step st uses this lane's registers r in [8st, 8st+8): keys 16st + 4h + {0..3, 8..11}
 #pragma unroll

@@ -5,18 +5,11 @@
 //   funasr/models/sanm/attention.py:760-813           (decoder cross-attention over the encoder memory)
 // The T x T score matrix (256 MB per layer at B=64, T=500) never reaches HBM.
 //
-// Mapping. One workgroup = 4 waves = 128 queries of one (sequence, head); each wave owns 32 queries and the
-// whole d_k = 128. Both MFMA products are issued "swapped" so that a lane always holds ONE query
-// (q = lane & 31) and the keys / output channels run over its accumulator registers:
-//     S^T[key][q] = sum_d K[key][d] * Q[q][d]      A = K tile (LDS), B = Q (64 registers per lane)
-//     O^T[d][q]   = sum_key V[key][d] * P[q][key]  A = V tile (LDS), B = P (= the S^T accumulator registers)
-// The 32x32x2 MFMA's k index is only a pairing between A and B, so the half-wave h = lane >> 5 takes
-// d in [64h, 64h+64) for S^T and, for O^T, exactly the key its own S^T register r already holds
-// (key = (r&3) + 8(r>>2) + 4h): P feeds the second product straight from registers, the online-softmax row
-// statistics are per lane (one xor-32 shuffle joins the two halves) and no LDS transpose is needed.
+// Mapping (attention_tile.h). One workgroup = 4 waves = 128 queries of one (sequence, head); each wave owns 32 queries and the
+// whole d_k = 128: half-wave h takes d in [64h, 64h+64) for S^T (64 Q registers per lane) and its own keys for O^T.
 // K rows are padded to 132 floats so the ds_read_b128 operand fetch is bank-conflict free; V rows are
 // read 32 consecutive floats per half-wave.
-#include "common.h"
+#include "attention_tile.h"
 
 namespace pf {
 
@@ -42,25 +35,10 @@ __global__ __launch_bounds__(256, 2) void attention_f32_kernel(AttnArgs p) {
     const int n1 = p.K2 ? p.n1_dev[b * p.n1_stride] : p.klens[b];
     const int klen = p.K2 ? n1 + p.n2 : n1;
 
-    // Q fragment: this lane's query row, d in [64h, 64h + 64), pre-scaled like the reference (q * d_k^-0.5)
-    float qreg[64];
-    {
-        const float* qp = p.Q + ((size_t)b * p.Tq + qc) * p.ldq + head * DK + hh * 64;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const float4 t = *reinterpret_cast<const float4*>(qp + 4 * i);
-            qreg[4 * i + 0] = t.x * p.scale;
-            qreg[4 * i + 1] = t.y * p.scale;
-            qreg[4 * i + 2] = t.z * p.scale;
-            qreg[4 * i + 3] = t.w * p.scale;
-        }
-    }
-
+    float qreg[64];      // this lane's query row, d in [64h, 64h + 64)
+    tile_load_q(p.Q + ((size_t)b * p.Tq + qc) * p.ldq + head * DK + hh * 64, p.scale, qreg);
     floatx16 o[4];
-#pragma unroll
-    for (int d = 0; d < 4; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
+    tile_zero(o);
     float m_run = -INFINITY, l_run = 0.f;
 
     const int lc4 = tid & 31, lr = tid >> 5;   // tile loader: 32 float4 per row, 8 rows per pass
@@ -94,69 +72,15 @@ __global__ __launch_bounds__(256, 2) void attention_f32_kernel(AttnArgs p) {
         }
         __syncthreads();
 
-        // ---- S^T tile (32 keys x 32 queries)
-        floatx16 s;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[r] = 0.f;
+        // ---- S^T tile (32 keys x 32 queries): this lane's K row idx, d in [64h, 64h + 64)
         const float* kp = &Ks[idx * KLD + hh * 64];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const float4 kf = *reinterpret_cast<const float4*>(kp + 4 * i);
-            s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, qreg[4 * i + 0], s, 0, 0, 0);
-            s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, qreg[4 * i + 1], s, 0, 0, 0);
-            s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, qreg[4 * i + 2], s, 0, 0, 0);
-            s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, qreg[4 * i + 3], s, 0, 0, 0);
-        }
-
-        // ---- online softmax for query (lane & 31); this lane holds keys k0 + (r&3) + 8(r>>2) + 4h
-        float mx = -INFINITY;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-            if (key >= klen) s[r] = -INFINITY;
-            mx = fmaxf(mx, s[r]);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run, mx);          // finite: every tile has >= 1 valid key
-        const float alpha = expf(m_run - m_new);       // exp(-inf) = 0 on the first tile
-        float psum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            s[r] = expf(s[r] - m_new);
-            psum += s[r];
-        }
-        psum += __shfl_xor(psum, 32, 64);
-        l_run = l_run * alpha + psum;
-        m_run = m_new;
-#pragma unroll
-        for (int d = 0; d < 4; ++d)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
-
-        // ---- O^T += V^T P^T
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int krow = (r & 3) + 8 * (r >> 2) + 4 * hh;
-            const float* vp = &Vs[krow * DK + idx];
-#pragma unroll
-            for (int d = 0; d < 4; ++d)
-                o[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(vp[32 * d], s[r], o[d], 0, 0, 0);
-        }
+        floatx16 s = tile_kq([&](int i) { return kp + 4 * i; }, qreg);
+        tile_mask(s, k0, hh, klen);
+        tile_softmax<4, false>(s, m_run, l_run, o);
+        tile_pv(Vs, hh, idx, s, o);
     }
 
-    if (q < p.Tq) {
-        const float inv = 1.0f / l_run;
-        const size_t orow = ((size_t)b * p.Tq + q) * p.ldo + head * DK;
-#pragma unroll
-        for (int d = 0; d < 4; ++d)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const float t[4] = {o[d][4 * g + 0] * inv, o[d][4 * g + 1] * inv, o[d][4 * g + 2] * inv, o[d][4 * g + 3] * inv};
-                const size_t off = orow + d * 32 + 8 * g + 4 * hh;
-                if (p.O3) store_split3x4(p.O3 + off, p.o_plane, t);      // the out-projection's operand planes (bf16x3 mode)
-                else *reinterpret_cast<float4*>(p.O + off) = make_float4(t[0], t[1], t[2], t[3]);
-            }
-    }
+    if (q < p.Tq) tile_store(o, l_run, hh, ((size_t)b * p.Tq + q) * p.ldo + head * DK, p.O, p.O3, p.o_plane);
 }
 
 // ---- offline variant: K/V tiles go HBM -> LDS with global_load_lds_dwordx4 (no staging registers), double buffered:
@@ -179,24 +103,10 @@ __global__ __launch_bounds__(256, 2) void attention_f32_dma_kernel(AttnArgs p) {
     const int qc = q < p.Tq ? q : p.Tq - 1;
     const int klen = p.klens[b];
 
-    float qreg[64];
-    {
-        const float* qp = p.Q + ((size_t)b * p.Tq + qc) * p.ldq + head * DK + hh * 64;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const float4 t = *reinterpret_cast<const float4*>(qp + 4 * i);
-            qreg[4 * i + 0] = t.x * p.scale;
-            qreg[4 * i + 1] = t.y * p.scale;
-            qreg[4 * i + 2] = t.z * p.scale;
-            qreg[4 * i + 3] = t.w * p.scale;
-        }
-    }
-
+    float qreg[64];      // this lane's query row, d in [64h, 64h + 64)
+    tile_load_q(p.Q + ((size_t)b * p.Tq + qc) * p.ldq + head * DK + hh * 64, p.scale, qreg);
     floatx16 o[4];
-#pragma unroll
-    for (int d = 0; d < 4; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
+    tile_zero(o);
     float m_run = -INFINITY, l_run = 0.f;
 
     // DMA pieces: a piece = 2 keys x 512 B; wave w stages pieces 4w .. 4w+3 of both tiles
@@ -230,66 +140,14 @@ __global__ __launch_bounds__(256, 2) void attention_f32_dma_kernel(AttnArgs p) {
         const float* Vs = Ks + TILE_F;
 
         // ---- S^T tile (32 keys x 32 queries); this lane's K row idx, d chunks [16h, 16h+16) permuted by idx & 15
-        floatx16 s;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[r] = 0.f;
         const float* kp = Ks + idx * DK;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const float4 kf = *reinterpret_cast<const float4*>(kp + (((hh * 16 + i) ^ (idx & 15)) * 4));
-            s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, qreg[4 * i + 0], s, 0, 0, 0);
-            s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, qreg[4 * i + 1], s, 0, 0, 0);
-            s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, qreg[4 * i + 2], s, 0, 0, 0);
-            s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, qreg[4 * i + 3], s, 0, 0, 0);
-        }
-
-        float mx = -INFINITY;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-            if (key >= klen) s[r] = -INFINITY;
-            mx = fmaxf(mx, s[r]);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run, mx);
-        const float alpha = expf(m_run - m_new);
-        float psum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            s[r] = expf(s[r] - m_new);
-            psum += s[r];
-        }
-        psum += __shfl_xor(psum, 32, 64);
-        l_run = l_run * alpha + psum;
-        m_run = m_new;
-#pragma unroll
-        for (int d = 0; d < 4; ++d)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
-
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int krow = (r & 3) + 8 * (r >> 2) + 4 * hh;
-            const float* vp = Vs + krow * DK + idx;
-#pragma unroll
-            for (int d = 0; d < 4; ++d)
-                o[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(vp[32 * d], s[r], o[d], 0, 0, 0);
-        }
+        floatx16 s = tile_kq([&](int i) { return kp + (((hh * 16 + i) ^ (idx & 15)) * 4); }, qreg);
+        tile_mask(s, k0, hh, klen);
+        tile_softmax<4, false>(s, m_run, l_run, o);
+        tile_pv(Vs, hh, idx, s, o);
     }
 
-    if (q < p.Tq) {
-        const float inv = 1.0f / l_run;
-        const size_t orow = ((size_t)b * p.Tq + q) * p.ldo + head * DK;
-#pragma unroll
-        for (int d = 0; d < 4; ++d)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const float t[4] = {o[d][4 * g + 0] * inv, o[d][4 * g + 1] * inv, o[d][4 * g + 2] * inv, o[d][4 * g + 3] * inv};
-                const size_t off = orow + d * 32 + 8 * g + 4 * hh;
-                if (p.O3) store_split3x4(p.O3 + off, p.o_plane, t);      // the out-projection's operand planes (bf16x3 mode)
-                else *reinterpret_cast<float4*>(p.O + off) = make_float4(t[0], t[1], t[2], t[3]);
-            }
-    }
+    if (q < p.Tq) tile_store(o, l_run, hh, ((size_t)b * p.Tq + q) * p.ldo + head * DK, p.O, p.O3, p.o_plane);
 }
 
 // ---- few-query variant: the streaming step attends 15 window rows (or <= 24 token rows) of one stream over a few dozen
@@ -518,7 +376,7 @@ int launch_attention_f32(const AttnArgs& a, hipStream_t stream) {
     PF_REQUIRE(!a.fs_in && !a.O2, "attention: the FSMN rider and the two-plane output exist in the few-query kernel only");
     dim3 grid(ceil_div(a.Tq, 128), a.H, a.B);
     // the K/V ring form of the streaming step (two sources, a few dozen keys) keeps the register-staged loader; the
-    // offline form (one source) takes the LDS-DMA double-buffered kernel. Both do the same arithmetic in the same order.
+    // offline form (one source) takes the LDS-DMA double-buffered kernel. Both run the tile step of attention_tile.h.
     const bool dma_ok = a.K2 == nullptr && ((uintptr_t)a.K & 15) == 0 && ((uintptr_t)a.V & 15) == 0;
     if (dma_ok) hipLaunchKernelGGL(attention_f32_dma_kernel, grid, dim3(256), 0, stream, a);
     else hipLaunchKernelGGL(attention_f32_kernel, grid, dim3(256), 0, stream, a);

@@ -2,9 +2,8 @@
 // LegacyRelPositionMultiHeadedAttention / RelPositionMultiHeadedAttention), d_k = 64, flash-style in exact fp32 on the matrix cores.
 // The reference materialises matrix_ac, matrix_bd (and its rel_shift copy) and the probabilities as [B, H, T, T]; here none exists.
 //
-// Mapping (that of attention_f32.hip): one workgroup = 4 waves = 128 queries of one (sequence, head); a wave owns 32 queries.
-// Every product is issued "swapped" so that a lane holds ONE query (column lane & 31) and the keys run over its accumulator
-// registers (register r of half-wave h = key (r & 3) + 8 (r >> 2) + 4 h of the tile):
+// Mapping (attention_tile.h): one workgroup = 4 waves = 128 queries of one (sequence, head); a wave owns 32 queries, a lane ONE
+// query (column lane & 31), and the keys run over its accumulator registers:
 //     S^T[key][q] = sum_d K[key][d] (q + u)[q][d]            A = K tile (LDS),       B = registers
 //     O^T[d][q]   = sum_key V[key][d] p[q][key]               A = V tile (LDS),       B = the probabilities in the S^T registers
 // The positional term bd(i, j) = qv_i . P[c - i + j] depends on j - i: for the wave's 32 queries and a tile's 32 keys the 63 rows
@@ -14,6 +13,7 @@
 // buffer (written [q][l] with row stride 66, read conflict-free). The legacy variant takes, right of the diagonal, the NEXT query's
 // qv against P[j - i - 2] (the wrapped rows of the reference's reshape): a second G with B = qv_{q + 1} and c = -2; which of the
 // two a row l of the buffer holds depends on l alone (j - i = l - 31 + k0 - qs), so one buffer serves both.
+#include "attention_tile.h"
 #include "conformer.h"
 
 namespace pf {
@@ -22,20 +22,9 @@ namespace {
 constexpr int DK = 64, KT = 32, KLD = DK + 4, GS = 66;
 
 __device__ __forceinline__ floatx16 band_product(const float* P, int ldp, int row, int nP, int col, const float (&qv)[32]) {
-    floatx16 g;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) g[r] = 0.f;
     const int rc = row < 0 ? 0 : (row >= nP ? nP - 1 : row);      // rows outside the table feed elements nothing reads
     const float* pp = P + (size_t)rc * ldp + col;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const float4 pf4 = *reinterpret_cast<const float4*>(pp + 4 * i);
-        g = __builtin_amdgcn_mfma_f32_32x32x2f32(pf4.x, qv[4 * i + 0], g, 0, 0, 0);
-        g = __builtin_amdgcn_mfma_f32_32x32x2f32(pf4.y, qv[4 * i + 1], g, 0, 0, 0);
-        g = __builtin_amdgcn_mfma_f32_32x32x2f32(pf4.z, qv[4 * i + 2], g, 0, 0, 0);
-        g = __builtin_amdgcn_mfma_f32_32x32x2f32(pf4.w, qv[4 * i + 3], g, 0, 0, 0);
-    }
-    return g;
+    return tile_kq([&](int i) { return pp + 4 * i; }, qv);
 }
 
 __global__ __launch_bounds__(256) void relpos_attention_kernel(const float* qkv, const float* P, const float* ub, const float* vb,
@@ -79,10 +68,7 @@ __global__ __launch_bounds__(256) void relpos_attention_kernel(const float* qkv,
     }
 
     floatx16 o[2];
-#pragma unroll
-    for (int d = 0; d < 2; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
+    tile_zero(o);
     float m_run = -INFINITY, l_run = 0.f;
 
     const int lc4 = (tid & 15) * 4, lr = tid >> 4;
@@ -105,20 +91,8 @@ __global__ __launch_bounds__(256) void relpos_attention_kernel(const float* qkv,
         __syncthreads();
 
         // ---- S^T = K (q + u)^T
-        floatx16 s;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[r] = 0.f;
-        {
-            const float* kp = &Ks[idx * KLD + hh * 32];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const float4 kf = *reinterpret_cast<const float4*>(kp + 4 * i);
-                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, qu[4 * i + 0], s, 0, 0, 0);
-                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, qu[4 * i + 1], s, 0, 0, 0);
-                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, qu[4 * i + 2], s, 0, 0, 0);
-                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, qu[4 * i + 3], s, 0, 0, 0);
-            }
-        }
+        const float* kp = &Ks[idx * KLD + hh * 32];
+        floatx16 s = tile_kq([&](int i) { return kp + 4 * i; }, qu);
 
         // ---- the band products, skewed through the wave's LDS buffer
         const int delta = k0 - qs;                   // j - i = l - 31 + delta for row l of the buffer
@@ -132,59 +106,23 @@ __global__ __launch_bounds__(256) void relpos_attention_kernel(const float* qkv,
             if (legacy && 32 * g + 31 >= 33 - delta) gu = band_product(P, D, delta - 33 + 32 * g + idx, nP, col, qn);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int l = 32 * g + (r & 3) + 8 * (r >> 2) + 4 * hh;
+                const int l = 32 * g + tile_key(r, hh);
                 Gw[idx * GS + l] = l <= last_lower ? gl[r] : (l == last_lower + 1 ? 0.f : gu[r]);
             }
         }
         __syncthreads();
 
         // ---- scores, online softmax for query (lane & 31)
-        float mx = -INFINITY;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int kr = (r & 3) + 8 * (r >> 2) + 4 * hh;
-            const float bd = Gw[idx * GS + kr - idx + 31];
-            s[r] = (s[r] + bd) * 0.125f;
-            if (k0 + kr >= klen) s[r] = -INFINITY;
-            mx = fmaxf(mx, s[r]);
+            s[r] = (s[r] + Gw[idx * GS + tile_key(r, hh) - idx + 31]) * 0.125f;
+            if (k0 + tile_key(r, hh) >= klen) s[r] = -INFINITY;
         }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run, mx);
-        const float alpha = expf(m_run - m_new);
-        float psum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            s[r] = expf(s[r] - m_new);
-            psum += s[r];
-        }
-        psum += __shfl_xor(psum, 32, 64);
-        l_run = l_run * alpha + psum;
-        m_run = m_new;
-#pragma unroll
-        for (int d = 0; d < 2; ++d)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
-
-        // ---- O^T += V^T p^T
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int krow = (r & 3) + 8 * (r >> 2) + 4 * hh;
-            const float* vp = &Vs[krow * DK + idx];
-#pragma unroll
-            for (int d = 0; d < 2; ++d) o[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(vp[32 * d], s[r], o[d], 0, 0, 0);
-        }
+        tile_softmax<2, false>(s, m_run, l_run, o);
+        tile_pv(Vs, hh, idx, s, o);
     }
 
-    if (qi < T) {
-        const float inv = 1.0f / l_run;
-        float* op = out + ((size_t)b * T + qi) * D + head * DK;
-#pragma unroll
-        for (int d = 0; d < 2; ++d)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-                *reinterpret_cast<float4*>(op + d * 32 + 8 * g + 4 * hh) =
-                    make_float4(o[d][4 * g + 0] * inv, o[d][4 * g + 1] * inv, o[d][4 * g + 2] * inv, o[d][4 * g + 3] * inv);
-    }
+    if (qi < T) tile_store(o, l_run, hh, ((size_t)b * T + qi) * D + head * DK, out, nullptr, 0);
 }
 
 }  // namespace

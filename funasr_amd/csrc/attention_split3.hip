@@ -6,7 +6,7 @@
 // Reference semantics: funasr/models/sanm/attention.py:270-306,322-327 (scores, key mask -inf, softmax, mask 0, .V).
 //
 // One workgroup = 8 waves = 256 queries of one (sequence, head); each wave owns 32 queries x d_k, a lane owns one
-// query (q = lane & 31). Per 32-key tile:
+// query (q = lane & 31): the mapping of attention_tile.h. Per 32-key tile:
 //   1. the fp32 K and V tiles arrive in LDS by asm-issued global_load_lds_dwordx4 (issued one tile ahead, in flight
 //      under the previous tile's MFMAs);
 //   2. split pass (all 512 threads, each element once): K -> three bf16 planes [32 keys][128 d], 16-B chunk c of key r
@@ -18,7 +18,7 @@
 //      O^T[d][q] += V^T[d][key] P[q][key]: the k slots of half-wave h are exactly the keys whose scores that lane's
 //      accumulator registers hold, so P goes from the S^T accumulator to the B operand without leaving the lane.
 // 96 MFMAs (3072 matrix-pipe cycles) per wave per tile against 8192 for the fp32 MFMA form.
-#include "common.h"
+#include "attention_tile.h"
 
 namespace pf {
 
@@ -66,10 +66,7 @@ __global__ __launch_bounds__(512, 2) void attention_split3_kernel(AttnArgs p) {
     }
 
     floatx16 o[4];
-#pragma unroll
-    for (int d = 0; d < 4; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
+    tile_zero(o);
     float m_run = -INFINITY, l_run = 0.f;
 
     // ---- DMA of one fp32 K/V tile: 32 pieces of 1 KB (2 keys x 512 B), K pieces 0..15 then V pieces 0..15; wave w issues
@@ -157,31 +154,10 @@ __global__ __launch_bounds__(512, 2) void attention_split3_kernel(AttnArgs p) {
             }
         }
 
-        // ---- online softmax for query (lane & 31); this lane holds keys k0 + (r&3) + 8(r>>2) + 4h
         float s[16];
-        float mx = -INFINITY;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-            s[r] = key < klen ? sa[r] + sb[r] : -INFINITY;
-            mx = fmaxf(mx, s[r]);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run, mx);
-        const float alpha = __expf(m_run - m_new);
-        float psum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            s[r] = __expf(s[r] - m_new);
-            psum += s[r];
-        }
-        psum += __shfl_xor(psum, 32, 64);
-        l_run = l_run * alpha + psum;
-        m_run = m_new;
-#pragma unroll
-        for (int d = 0; d < 4; ++d)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
+        for (int r = 0; r < 16; ++r) s[r] = k0 + tile_key(r, hh) < klen ? sa[r] + sb[r] : -INFINITY;
+        tile_softmax<4, true>(s, m_run, l_run, o);
 
         // ---- O^T += V^T P^T. step st uses this lane's registers r in [8st, 8st+8): keys 16st + 4h + {0..3, 8..11}
 #pragma unroll
@@ -217,19 +193,7 @@ __global__ __launch_bounds__(512, 2) void attention_split3_kernel(AttnArgs p) {
         }
     }
 
-    if (q < p.Tq) {
-        const float inv = 1.0f / l_run;
-        const size_t orow = ((size_t)b * p.Tq + q) * p.ldo + head * DK;
-#pragma unroll
-        for (int d = 0; d < 4; ++d)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const float t[4] = {o[d][4 * g + 0] * inv, o[d][4 * g + 1] * inv, o[d][4 * g + 2] * inv, o[d][4 * g + 3] * inv};
-                const size_t off = orow + d * 32 + 8 * g + 4 * hh;
-                if (p.O3) store_split3x4(p.O3 + off, p.o_plane, t);
-                else *reinterpret_cast<float4*>(p.O + off) = make_float4(t[0], t[1], t[2], t[3]);
-            }
-    }
+    if (q < p.Tq) tile_store(o, l_run, hh, ((size_t)b * p.Tq + q) * p.ldo + head * DK, p.O, p.O3, p.o_plane);
 }
 
 }  // namespace

@@ -343,6 +343,18 @@ int pf_k_attention_f32(const float* Q, int32_t ldq, const float* K, int32_t ldk,
     aa.klens = klens_dev; aa.B = B; aa.H = H; aa.Tq = Tq; aa.Tk = Tk; aa.scale = scale;
     return attention(aa, 4.0 * B * (double)Tq * Tk * H * 128, reinterpret_cast<hipStream_t>(stream));
 }
+/* the streaming step's two-source form: keys [0, n1_dev[b * n1_stride]) from (K, V; Tk rows per sequence), then n2 from (K2, V2; T2 rows) */
+int pf_k_attention_f32_two_source(const float* Q, int32_t ldq, const float* K, int32_t ldk, const float* V, int32_t ldv,
+                                  const float* K2, int32_t ldk2, const float* V2, int32_t ldv2, float* O, int32_t ldo,
+                                  const int32_t* n1_dev, int32_t n1_stride, int32_t B, int32_t H, int32_t Tq, int32_t Tk,
+                                  int32_t T2, int32_t n2, float scale, void* stream) {
+    PF_REQUIRE(K2 && V2 && n1_dev && n2 > 0 && n2 <= T2 && ldk2 % 4 == 0 && ldv2 % 4 == 0, "attention_two_source: bad second source");
+    AttnArgs aa{};
+    aa.Q = Q; aa.ldq = ldq; aa.K = K; aa.ldk = ldk; aa.V = V; aa.ldv = ldv; aa.O = O; aa.ldo = ldo;
+    aa.K2 = K2; aa.ldk2 = ldk2; aa.V2 = V2; aa.ldv2 = ldv2; aa.T2 = T2; aa.n2 = n2; aa.n1_dev = n1_dev; aa.n1_stride = n1_stride;
+    aa.B = B; aa.H = H; aa.Tq = Tq; aa.Tk = Tk; aa.scale = scale;
+    return attention(aa, 4.0 * B * (double)Tq * (Tk + n2) * H * 128, reinterpret_cast<hipStream_t>(stream));
+}
 /* fp32 Q/K/V -> fp32 O with both products on the bf16 MFMA from three-plane split operands (attention_split3.hip) */
 int pf_k_attention_split3(const float* Q, int32_t ldq, const float* K, int32_t ldk, const float* V, int32_t ldv, float* O,
                           int32_t ldo, const int32_t* klens_dev, int32_t B, int32_t H, int32_t Tq, int32_t Tk, float scale,

@@ -152,6 +152,20 @@ def attention(q, k, v, klens, n_heads: int, scale: float):
     return out
 
 
+def attention_two_source(q, k, v, k2, v2, n1, n2: int, n_heads: int, scale: float, n1_stride: int = 1):
+    """The streaming step's form of attention(): sequence b attends keys [0, n1[b * n1_stride]) of k/v [B, Tk, H*128] (the ring)
+    and then the first n2 rows of k2/v2 [B, T2, H*128]; n1 int32 on device."""
+    lib = _lib.load()
+    B, Tq, D = q.shape
+    assert all(t.stride(2) == 1 and t.stride(0) == t.shape[1] * t.stride(1) for t in (q, k, v, k2, v2))
+    out = torch.empty(B, Tq, D, device=q.device, dtype=torch.float32)
+    _lib.check(lib.pf_k_attention_f32_two_source(_ptr(q), q.stride(1), _ptr(k), k.stride(1), _ptr(v), v.stride(1), _ptr(k2),
+                                                 k2.stride(1), _ptr(v2), v2.stride(1), _ptr(out), D, _ptr(n1), n1_stride, B,
+                                                 n_heads, Tq, k.shape[1], k2.shape[1], n2, float(scale), _stream()),
+               "pf_k_attention_f32_two_source")
+    return out
+
+
 def attention_split3(q, k, v, klens, n_heads: int, scale: float, time_iters: int = 0):
     """Same contract as attention(); both products on the bf16 MFMA from three-plane split operands (fp32-class)."""
     lib = _lib.load()

@@ -740,6 +740,12 @@ int pf_k_fsmn(const float* in, int32_t ldin, const float* w, const float* R, int
 int pf_k_attention_f32(const float* Q, int32_t ldq, const float* K, int32_t ldk, const float* V, int32_t ldv,
                        float* O, int32_t ldo, const int32_t* klens_dev, int32_t B, int32_t H, int32_t Tq,
                        int32_t Tk, float scale, void* stream);
+/* the same with two key/value sources (the streaming step's [cached ring | this chunk]): sequence b takes keys
+ * [0, n1_dev[b * n1_stride]) from (K, V; Tk rows per sequence) and then n2 keys from (K2, V2; T2 rows per sequence) */
+int pf_k_attention_f32_two_source(const float* Q, int32_t ldq, const float* K, int32_t ldk, const float* V, int32_t ldv,
+                                  const float* K2, int32_t ldk2, const float* V2, int32_t ldv2, float* O, int32_t ldo,
+                                  const int32_t* n1_dev, int32_t n1_stride, int32_t B, int32_t H, int32_t Tq,
+                                  int32_t Tk, int32_t T2, int32_t n2, float scale, void* stream);
 /* small heads (d_k <= 64, multiple of 4; the CT-Transformer's 8 x 32), Tk <= 1024: rows hold H heads of d_k columns */
 int pf_k_attention_small(const float* Q, int32_t ldq, const float* K, int32_t ldk, const float* V, int32_t ldv,
                          float* O, int32_t ldo, const int32_t* klens_dev, int32_t B, int32_t H, int32_t d_k,

@@ -349,6 +349,63 @@ def test_attention_f32_few_query_kernel(cuda, B, Tq, Tk, lens):
     assert (few - tile).abs().max().item() < 2e-5
 
 
+def _two_source_case(cuda, Tq, n2, n1, few_query=False):
+    """Keys [0, n1[b]) of a 48-row ring, then n2 rows of a second source (the streaming step's [cache | chunk]). Returns the
+    two-source result, ops.attention on the physically concatenated keys (one aligned source: the LDS-DMA kernel) and the fp64
+    reference. Ring rows past n1[b] and one guard row behind each source are NaN: a loader that reads past its clamp, or takes
+    a key from the wrong source, turns the output into NaN."""
+    from funasr_amd import _lib, ops
+    H, dk, Tk = 2, 128, 48
+    D, B = H * dk, len(n1)
+    g = torch.Generator().manual_seed(Tq * 17 + n2)
+    q = torch.randn(B, Tq, D, generator=g)
+    ring = [torch.randn(B, Tk, D, generator=g) for _ in range(2)]
+    new = [torch.randn(B, n2, D, generator=g) for _ in range(2)]
+    scale = dk ** -0.5
+    lens = [n + n2 for n in n1]
+    Tc = max(lens)
+    cat = [torch.zeros(B, Tc, D) for _ in range(2)]
+    for b in range(B):
+        for c, r, n in zip(cat, ring, new):
+            c[b, :lens[b]] = torch.cat([r[b, :n1[b]], n[b]])
+            r[b, n1[b]:] = float("nan")
+    klens = torch.tensor(lens, dtype=torch.int32)
+    qh = q.double().view(B, Tq, H, dk).transpose(1, 2) * scale
+    kh, vh = [c.double().view(B, Tc, H, dk).transpose(1, 2) for c in cat]
+    m = (torch.arange(Tc)[None, :] >= klens[:, None])[:, None, None, :]
+    p = torch.softmax((qh @ kh.transpose(-1, -2)).masked_fill(m, float("-inf")), -1).masked_fill(m, 0.0)
+    ref = (p @ vh).transpose(1, 2).reshape(B, Tq, D)
+    guard = torch.full((1, D), float("nan"))
+    dev = lambda t: torch.cat([t.reshape(-1, D), guard]).to(cuda)[:-1].view(t.shape)
+    one = ops.attention(q.to(cuda), cat[0].to(cuda), cat[1].to(cuda), klens.to(cuda), H, scale).cpu()
+    lib = _lib.load()
+    lib.pf_set_skinny_max_m(1 << 30 if few_query else 0)
+    try:
+        two = ops.attention_two_source(q.to(cuda), dev(ring[0]), dev(ring[1]), dev(new[0]), dev(new[1]),
+                                       torch.tensor(n1, dtype=torch.int32).to(cuda), n2, H, scale).cpu()
+    finally:
+        lib.pf_set_skinny_max_m(0)
+    return two, one, ref
+
+
+@pytest.mark.parametrize("Tq,n2,n1", [(40, 40, [17, 0]), (130, 130, [48])])
+def test_attention_f32_two_source_register_staged_kernel(cuda, Tq, n2, n1):
+    """attention_f32_kernel (two sources, more than 32 queries) against fp64 softmax attention over the concatenated keys, and
+    bit for bit against the LDS-DMA kernel on the physically concatenated K/V: the two kernels differ in how a tile reaches LDS
+    only. 57 and 40 keys: partial second tiles, one sequence with no ring key; 130 queries over 48 + 130 keys: past the 128-query
+    workgroup, a full ring, five full tiles and an 18-key tail."""
+    two, one, ref = _two_source_case(cuda, Tq, n2, n1)
+    assert (two.double() - ref).abs().max().item() < 2e-5
+    assert torch.equal(two, one)
+
+
+def test_attention_f32_two_source_few_query_kernel(cuda):
+    """the few-query kernel's two-source path (what the streaming step runs): it sums in another order, so 2e-5 to both"""
+    two, one, ref = _two_source_case(cuda, 15, 40, [17, 0], few_query=True)
+    assert (two.double() - ref).abs().max().item() < 2e-5
+    assert (two - one).abs().max().item() < 2e-5
+
+
 @pytest.mark.parametrize("B,Tq,Tk,lens", [(2, 100, 100, [100, 37]), (1, 500, 500, [500]), (3, 40, 300, [300, 1, 129])])
 def test_attention_bf16(cuda, B, Tq, Tk, lens):
     """bf16-operand attention against fp64 softmax attention on the same bf16-rounded Q/K/V: the differences are the
