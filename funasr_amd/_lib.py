@@ -209,6 +209,15 @@ SIGNATURES = {
     "pf_ctc_missing": (C.c_int, [_vp]),
     "pf_ctc_greedy": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
     "pf_ctc_set_precision": (C.c_int, [_vp, _i32]),
+    "pf_posterior_embed_create": (_vp, [_i32, _i32, _i32]),
+    "pf_posterior_embed_destroy": (None, [_vp]),
+    "pf_posterior_embed_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),
+    "pf_posterior_embed_missing": (C.c_int, [_vp]),
+    "pf_posterior_embed_set_precision": (C.c_int, [_vp, _i32]),
+    "pf_posterior_embed_set_chunk_rows": (C.c_int, [_vp, _i32]),
+    "pf_posterior_embed_debug_poison": (C.c_int, [_vp, _i32]),
+    "pf_posterior_embed_runs": (C.c_int, [_vp, _vp, _vp, _pi32, _i32, _i32, _pi32, _vp, _vp]),
+    "pf_posterior_embed_embeds": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "pf_stream_create": (_vp, [_vp, _vp, _vp, C.POINTER(pf_stream_config)]),
     "pf_stream_destroy": (None, [_vp]),
     "pf_stream_set_pe": (C.c_int, [_vp, _vp, _i32]),
@@ -261,6 +270,7 @@ SIGNATURES = {
     "pf_k_lstm": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "pf_k_cif": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "pf_k_cif_tail": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pf_k_ctc_runs": (C.c_int, [_vp, _pi32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     "pf_k_argmax_rows": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
     "pf_k_gemm_f32_time": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_float), _vp]),
     # utterance data parallelism at the C ABI (dp_rccl.hip)

@@ -617,10 +617,11 @@ static pf_decoder* decoder_create_impl(const pf_decoder_config* cfg, bool contex
     if (!cfg) { set_error("decoder: null config"); return nullptr; }
     if (check_device()) return nullptr;
     const pf_decoder_config& c = *cfg;
-    if (c.d_model <= 0 || c.n_heads <= 0 || c.d_model % c.n_heads || c.d_model / c.n_heads != 128 ||
+    const int dk = (c.n_heads > 0 && c.d_model > 0) ? c.d_model / c.n_heads : 0;
+    if (c.d_model <= 0 || c.n_heads <= 0 || c.d_model % c.n_heads || !(dk == 128 || (dk <= 64 && dk % 4 == 0 && !contextual)) ||
         c.ffn_dim % 32 || c.d_model % 32 || c.n_blocks < 1 || (c.kernel_size != 11 && c.kernel_size != 21) ||
         (c.kernel_size == 21 && c.sanm_shift > 0) || c.vocab_size < 0) {
-        set_error("decoder: unsupported config (need d_model/n_heads == 128, kernel_size 11 or 21 (21: sanm_shfit 0), "
+        set_error("decoder: unsupported config (need d_model/n_heads == 128, or <= 64 for the small-head kernel in the fp32 mode of the plain decoder; kernel_size 11 or 21 (21: sanm_shfit 0), "
                   "dims % 32 == 0; vocab_size 0 = no output layer)");
         return nullptr;
     }
@@ -713,6 +714,7 @@ int pf_decoder_set_tensor(pf_decoder* dh, const char* name, const float* data, i
 int pf_decoder_set_precision(pf_decoder* dh, int32_t mode) {
     Decoder* d = reinterpret_cast<Decoder*>(dh);
     PF_REQUIRE(d && mode >= 0 && mode <= 3, "decoder_set_precision: mode must be 0 (fp32 MFMA), 1 (bf16 operands), 2 (fp32 via bf16x3) or 3 (fp32 via f16x2)");
+    PF_REQUIRE(mode == 0 || d->cfg.d_model / d->cfg.n_heads == 128, "decoder_set_precision: heads of d_k <= 64 exist in the fp32 mode only (attention_small.hip)");
     d->precision = mode;
     return 0;
 }
@@ -766,6 +768,7 @@ static int decoder_forward_impl(Decoder* d, const float* memory, const int32_t* 
         PF_REQUIRE(mem_lens[b] >= 1 && mem_lens[b] <= T, "decoder_forward: memory lens out of range");
         PF_REQUIRE(tok_lens[b] >= 0 && tok_lens[b] <= N, "decoder_forward: token lens out of range");
     }
+    PF_REQUIRE(d->precision == 0 || d->cfg.d_model / d->cfg.n_heads == 128, "decoder_forward: heads of d_k <= 64 exist in the fp32 mode only");
     int rc;
     if ((rc = decoder_prepare(d, d->precision == 3 && asf_layer < 0 && !cx, s))) return rc;
     const pf_decoder_config& c = d->cfg;
@@ -939,7 +942,8 @@ static int decoder_forward_impl(Decoder* d, const float* memory, const int32_t* 
         aa.scale = powf((float)(D / c.n_heads), -0.5f);
         // cross-attention keeps the fp32 MFMA kernel in every fp32-accurate mode: with Tq = tokens (~120) one 128-query
         // block per (utterance, head) is the better shape (102 us vs 111 us for the 256-query split kernel)
-        if ((rc = attention(aa, 4.0 * B * (double)N * T * D, s))) return rc;
+        // (heads of d_k <= 64: the small-head kernel, fp32 mode only)
+        if ((rc = attention(aa, 4.0 * B * (double)N * T * D, s, false, D / c.n_heads))) return rc;
         if (ctx_block) {
             float* xcat = d->xcat.as<float>();                   // [Mq, 2D]: x_src_attn | cx * clas_scale
             const float* xs = d->xself.as<float>();

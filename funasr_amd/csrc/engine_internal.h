@@ -2,7 +2,7 @@
 // share. The layer is split by family -- engine.hip (shared state: errors, profiling, staging ring, instrumented launch helpers,
 // ABI version), engine_frontend.hip, engine_encoder.hip, engine_decoder.hip (predictor, decoder, CTC), engine_stream.hip,
 // engine_vad.hip, engine_pipeline.hip, engine_campplus.hip, engine_emotion2vec.hip, engine_conformer.hip (Conformer encoder and
-// Transformer decoder step), engine_kernels.hip (the pf_k_* single-kernel hooks) -- so that a kernel change recompiles one family
+// Transformer decoder step), engine_posterior.hip (Paraformer-v2 posterior embedder), engine_kernels.hip (the pf_k_* single-kernel hooks) -- so that a kernel change recompiles one family
 // (round-3 review: engine.hip was one 3 400-line translation unit).
 //
 // Load-time weight preparation has ONE home, the TensorTable: what the library computes from the caller's weights (folded BatchNorms,

@@ -24,8 +24,8 @@ static int stream_prepare_x2(Stream* st, hipStream_t s) {
     const pf_decoder_config& dc = d->cfg;
     const int D = e->cfg.d_model;
     if (D / e->cfg.n_heads != 128 || D % 256 != 0 || e->cfg.ffn_dim % 256 != 0 || dc.ffn_dim % 256 != 0 || dc.d_model != D ||
-        dc.vocab_size <= 0) {
-        set_error("stream: gemm_mode 3 (f16x2) needs d_model / n_heads == 128, d_model % 256 == 0, ffn_dim % 256 == 0");
+        dc.n_heads <= 0 || dc.d_model / dc.n_heads != 128 || dc.vocab_size <= 0) {
+        set_error("stream: gemm_mode 3 (f16x2) needs d_model / n_heads == 128 (encoder and decoder), d_model % 256 == 0, ffn_dim % 256 == 0");
         return -1;
     }
     if ((rc = encoder_prepare(e, 3, s)) || (rc = decoder_prepare(d, true, s))) return rc;
@@ -464,6 +464,12 @@ pf_stream* pf_stream_create(pf_encoder* eh, pf_predictor* ph, pf_decoder* dh, co
         dec_left != K - 1 || d->n_blocks2 != 0) {
         set_error("stream: unsupported config (d_model 512, look_back >= 0 (finite), max_tokens <= 96, no decoders2, causal decoder "
                   "FSMN i.e. sanm_shfit == (kernel_size-1)/2 as in paraformer_streaming/template.yaml:62)");
+        return nullptr;
+    }
+    // the decoder step's cross-attention is the 128-wide few-query kernel (stream_step: attention(..., 128, ...)); pf_decoder_create
+    // also makes decoders with heads of d_k <= 64 for the offline fp32 forward, which this step cannot run
+    if (d->cfg.n_heads <= 0 || d->cfg.d_model / d->cfg.n_heads != 128) {
+        set_error("stream: the decoder needs d_model / n_heads == 128 (the streaming step has no small-head form)");
         return nullptr;
     }
     // CIF fires at most once per frame carrying weight (alpha < 1): a step's window has chunk_left + chunk_right + n frames,

@@ -263,6 +263,22 @@ def cif_tail(alphas: torch.Tensor, hidden: torch.Tensor, lens, n_max: int, tail_
     return al, peaks, nf, ntok, emb
 
 
+def ctc_runs(ids: torch.Tensor, lens, blank: int = 0, ld: int = None, fill: int = -1):
+    """The run scan of the Paraformer-v2 posterior embedder (pf_k_ctc_runs): greedy paths ids int32 [B, T], lens [B] host
+    integers (0 .. T) -> (counts int32 [B], ranges int32 [B, ld, 2]): first and one-past-last frame of each maximal run of one
+    non-blank label, in order; entries of runs the clip does not have keep `fill`."""
+    lib = _lib.load()
+    if not ids.is_cuda or ids.dtype != torch.int32:
+        raise TypeError("ids: expected an int32 tensor in GPU memory")
+    B, T = ids.shape
+    ld = T if ld is None else int(ld)
+    lens_c = (C.c_int32 * B)(*[int(v) for v in lens])
+    counts = torch.empty(B, device=ids.device, dtype=torch.int32)
+    ranges = torch.full((B, ld, 2), fill, device=ids.device, dtype=torch.int32)
+    _lib.check(lib.pf_k_ctc_runs(_ptr(ids.contiguous()), lens_c, B, T, int(blank), _ptr(counts), _ptr(ranges), ld, _stream()), "pf_k_ctc_runs")
+    return counts, ranges
+
+
 def argmax_rows(x: torch.Tensor) -> torch.Tensor:
     """x [M, N] fp32 (a row-strided view is taken as it is) -> int32 [M]: the first column of each row's maximum."""
     lib = _lib.load()

@@ -157,6 +157,45 @@ def paraformer_state_dict(cfg: dict = PARAFORMER_LARGE, seed: int = 0, cif_bias:
     return sd
 
 
+def paraformer_v2_conf(d_model: int = 256, heads: int = 2, ffn: int = 512, enc_blocks: int = 2, dec_blocks: int = 2, vocab: int = 261,
+                       kernel_size: int = 11, input_size: int = 560) -> dict:
+    """constructor arguments of a Paraformer_v2_community model (the layout of funasr/models/paraformer_v2_community/template.yaml)
+    at a chosen size"""
+    enc = {"output_size": d_model, "attention_heads": heads, "linear_units": ffn, "num_blocks": enc_blocks, "dropout_rate": 0.1,
+           "positional_dropout_rate": 0.1, "attention_dropout_rate": 0.1, "input_layer": "pe", "pos_enc_class": "SinusoidalPositionEncoder",
+           "normalize_before": True, "kernel_size": kernel_size, "sanm_shfit": 0, "selfattention_layer_type": "sanm"}
+    dec = {"attention_heads": heads, "linear_units": ffn, "num_blocks": dec_blocks, "dropout_rate": 0.1, "positional_dropout_rate": 0.1,
+           "self_attention_dropout_rate": 0.1, "src_attention_dropout_rate": 0.1, "att_layer_num": dec_blocks, "kernel_size": kernel_size,
+           "sanm_shfit": 0, "input_layer": "linear"}
+    return {"encoder": "SANMEncoder", "encoder_conf": enc, "decoder": "ParaformerSANMDecoder_v2_community", "decoder_conf": dec,
+            "ctc_conf": {"dropout_rate": 0.0, "ctc_type": "builtin", "reduce": True, "ignore_nan_grad": True}, "ctc_weight": 0.3,
+            "lsm_weight": 0.1, "length_normalized_loss": True, "input_size": input_size, "vocab_size": vocab, "blank_id": 0, "sos": 1, "eos": 2}
+
+
+def paraformer_v2_state_dict(cfg: dict, seed: int = 0, ctc_gain: float = 8.0, blank_bias: float = 0.0) -> Dict[str, torch.Tensor]:
+    """Keys of Paraformer_v2_community (paraformer_v2_community/model.py): encoder.*, decoder.* with the input layer
+    decoder.embed.{0,1}.{weight,bias}, ctc.ctc_lo.*. `cfg` in the layout of paraformer_v2_conf(). A CONFIDENT CTC head: logits of
+    order `ctc_gain` on unit-variance encoder output (a random head of order 1 has a flat density of top-2 gaps near zero, so a
+    greedy path on it cannot be compared id for id); `blank_bias` is added to the blank's bias and sets the share of blank frames.
+    The output layer gets the same gain."""
+    ec, dc, V, Din = cfg["encoder_conf"], cfg["decoder_conf"], cfg["vocab_size"], cfg["input_size"]
+    D = ec["output_size"]
+    enc_cfg = dict(output_size=D, linear_units=ec["linear_units"], input_size=Din, kernel_size=ec["kernel_size"], num_blocks=ec["num_blocks"])
+    dec_cfg = dict(encoder_output_size=D, linear_units=dc["linear_units"], kernel_size=dc["kernel_size"], vocab_size=V,
+                   att_layer_num=dc["att_layer_num"], num_blocks=dc["num_blocks"])
+    sd = {}
+    sd.update(encoder_state_dict(enc_cfg, seed * 4 + 0, "encoder."))
+    sd.update(decoder_state_dict(dec_cfg, seed * 4 + 1, "decoder."))
+    rng = _Rng(seed * 4 + 2)
+    sd["decoder.output_layer.weight"] = sd["decoder.output_layer.weight"] * ctc_gain
+    sd["decoder.embed.0.weight"] = rng.normal(D, V, std=1.0)
+    sd["decoder.embed.0.bias"] = rng.normal(D, std=0.02)
+    _ln(sd, rng, "decoder.embed.1", D)
+    _linear(sd, rng, "ctc.ctc_lo", V, D, gain=ctc_gain)
+    sd["ctc.ctc_lo.bias"][cfg.get("blank_id", 0)] += blank_bias
+    return sd
+
+
 def sensevoice_state_dict(cfg: dict = SENSEVOICE_SMALL, seed: int = 0) -> Dict[str, torch.Tensor]:
     """Keys of SenseVoiceSmall (sense_voice/model.py:702-737): encoder.*, embed.weight, ctc.ctc_lo.*"""
     sd = {}

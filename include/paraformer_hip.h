@@ -265,7 +265,7 @@ typedef struct pf_decoder pf_decoder;
 typedef struct pf_decoder_config {
     int32_t vocab_size;       /* 8404; 0 = no output layer (SeACo's bias decoder): forward returns hidden states only */
     int32_t d_model;          /* 512 */
-    int32_t n_heads;          /* 4 */
+    int32_t n_heads;          /* 4: d_model / n_heads == 128; heads of d_k <= 64 (a multiple of 4) run in the fp32 mode only, <= 1024 memory rows */
     int32_t ffn_dim;          /* 2048 */
     int32_t n_blocks;         /* 16 = att_layer_num (blocks with cross-attention; decoders2: pf_decoder_set_decoders2) */
     int32_t kernel_size;      /* 11; 21 (with sanm_shift 0) for SeACo's bias decoder */
@@ -531,6 +531,37 @@ int pf_ctc_greedy(pf_ctc* c, const float* hidden_dev, int32_t M, int32_t* ids_de
  * (fp32-class logits; the modes of pf_encoder_set_precision) */
 int pf_ctc_set_precision(pf_ctc* c, int32_t mode);
 
+/* ---- Paraformer-v2 posterior embedder (funasr/models/paraformer_v2_community/model.py:451-482,545-574, decoder.py:318-325): the
+ * decoder input made from the CTC head instead of a CIF predictor. Per clip: frame-wise softmax of the CTC logits, greedy path,
+ * maximal runs of one non-blank label over the clip's valid frames (the same label on both sides of a blank: two runs; sos / eos are
+ * ordinary labels), the mean posterior of each run, then the decoder's input layer Linear(V -> D), LayerNorm(eps 1e-5), ReLU,
+ * x * sqrt(D) + pe[token index]. Computed in the frame domain: E = probs . embed.0.weight^T per frame (row chunks whose logits /
+ * probabilities stay under 256 MB), then mean over the run + bias per token. The CTC weights are BORROWED from a pf_ctc handle of the
+ * same d_model / vocab. Tensor names: "embed.0.weight" [D, V], "embed.0.bias", "embed.1.weight", "embed.1.bias" [D] (the reference's
+ * keys below `decoder.`) and "pos_table" [5000, D] (row p = the sinusoid of position p, built on the host as the reference does). */
+typedef struct pf_posterior_embed pf_posterior_embed;
+pf_posterior_embed* pf_posterior_embed_create(int32_t vocab_size, int32_t d_model, int32_t blank_id);   /* d_model % 32 == 0, <= 2048 */
+void pf_posterior_embed_destroy(pf_posterior_embed* h);
+int pf_posterior_embed_set_tensor(pf_posterior_embed* h, const char* name, const float* data, int64_t numel);
+int pf_posterior_embed_missing(const pf_posterior_embed* h);
+/* 0 = both GEMMs on the exact-fp32 MFMA; 3 (default) = two-plane fp16 operands on the fp16 MFMA, fp32-class results (of the logits,
+ * the last vocab_size % 4 columns come from the fp32 MFMA). Other modes are refused with a message. */
+int pf_posterior_embed_set_precision(pf_posterior_embed* h, int32_t mode);
+/* rows of [B * T] per chunk; 0 (default) = as many as the 256 MB workspace cap admits. A row's result does not depend on it. */
+int pf_posterior_embed_set_chunk_rows(pf_posterior_embed* h, int32_t rows);
+/* test hook like pf_decoder_debug_poison: fills the handle's activation workspaces with `byte`; a pf_posterior_embed_embeds then
+ * needs a new pf_posterior_embed_runs. Synchronises. */
+int pf_posterior_embed_debug_poison(pf_posterior_embed* h, int32_t byte);
+/* hidden_dev [B, T, d_model] (encoder output), lens_host[b] in 1 .. T valid frames. Enqueues logits / softmax / arg-max / E and the
+ * run scan, then waits ONCE for the run counts: counts_host[b] = runs of clip b. path_dev (nullable): int32 [B, T] greedy path.
+ * Returns N = the largest count (0: every clip is blank), negative on error (pf_last_error). */
+int pf_posterior_embed_runs(pf_posterior_embed* h, pf_ctc* ctc, const float* hidden_dev, const int32_t* lens_host, int32_t B, int32_t T,
+                            int32_t* counts_host, int32_t* path_dev, void* stream);
+/* after pf_posterior_embed_runs with the same B / T: embeds_dev [B, N, d_model] (rows >= counts[b] zero; runs past N dropped),
+ * run_ranges_dev (nullable) int32 [B, N, 2] = first and one-past-last frame of each run (zero behind). N == 0 writes nothing. No sync. */
+int pf_posterior_embed_embeds(pf_posterior_embed* h, int32_t B, int32_t T, int32_t N, float* embeds_dev, int32_t* run_ranges_dev,
+                              void* stream);
+
 /* ----------------------------------------------------------------------------------------------- streaming
  * Chunked online decoding (ParaformerStreaming, funasr/models/paraformer_streaming/model.py:552-763): one handle =
  * a lock-step batch of n_streams independent streams (the reference: exactly 1) with all caches in HBM
@@ -779,6 +810,11 @@ int pf_k_cif(const float* alphas, const float* hidden, int32_t B, int32_t T, int
 int pf_k_cif_tail(const float* alphas, const float* hidden, const int32_t* lens_host, int32_t B, int32_t T, int32_t D, int32_t N,
                   float tail_threshold, int32_t tail_mask, int32_t loop, float* alphas_out, float* peaks, int32_t* n_fires,
                   int32_t* n_tok, float* embeds, void* stream);
+/* the run scan of the posterior embedder alone, on caller-provided greedy paths: ids_dev int32 [B, T], lens_host[b] in 0 .. T ->
+ * counts_dev int32 [B], ranges_dev int32 [B, ld, 2] (first and one-past-last frame of run j < min(count, ld); entries behind are
+ * left as they were). Synchronises. */
+int pf_k_ctc_runs(const int32_t* ids_dev, const int32_t* lens_host, int32_t B, int32_t T, int32_t blank, int32_t* counts_dev,
+                  int32_t* ranges_dev, int32_t ld, void* stream);
 /* ids[row] = first column of the largest of x[row, 0 .. N) (row stride ldx >= N), as torch.argmax (a row of -inf only: 0; NaN
  * unspecified): the arg-max of the streaming decoder and of the vocabulary projection when logits are requested */
 int pf_k_argmax_rows(const float* x, int32_t ldx, int32_t M, int32_t N, int32_t* ids, void* stream);
