@@ -272,6 +272,9 @@ SIGNATURES = {
     "pf_k_cif_tail": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pf_k_ctc_runs": (C.c_int, [_vp, _pi32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     "pf_k_argmax_rows": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    "pf_k_log_softmax_stats": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "pf_k_ctc_align_scratch_bytes": (_i64, [_i32, _i32, _i32]),
+    "pf_k_ctc_align": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _pi32, _pi32, _i32, _i32, _vp, _i32, _vp, _i64, _vp]),
     "pf_k_gemm_f32_time": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_float), _vp]),
     # utterance data parallelism at the C ABI (dp_rccl.hip)
     "pf_dp_unique_id": (C.c_int, [_vp, _i32]),

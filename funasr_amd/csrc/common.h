@@ -445,6 +445,8 @@ int launch_layernorm(const float* x, int ldx, const float* gamma, const float* b
 int launch_scale_cols(float* x, int ld, int M, int N, float sc, hipStream_t stream);
 // y[row] = x[row] - logsumexp(x[row]) over N columns (may run in place)
 int launch_log_softmax(const float* x, int ldx, float* y, int ldy, int M, int N, hipStream_t stream);
+// the same reduction without the output: lse[row] = logsumexp(x[row]), pred[row] = first column of the largest fl(x[row][j] - lse[row])
+int launch_log_softmax_stats(const float* x, int ldx, int M, int N, float* lse, int* pred, hipStream_t stream);
 // Tp > T: y is the padded layout [B, Tp, D] (rows t >= T zero)
 int launch_scale_add_pe(const float* x, const float* pe, float* y, int B, int T, int D, float scale,
                         hipStream_t stream, int Tp = 0);

@@ -1,4 +1,5 @@
 // C-ABI layer, single-kernel hooks pf_k_* (kernel tests and micro-benchmarks bind these; not part of the reference boundary).
+#include "ctc_align.h"
 #include "engine_internal.h"
 
 using namespace pf;
@@ -473,6 +474,49 @@ int pf_k_cif_tail(const float* alphas, const float* hidden, const int32_t* lens_
 int pf_k_argmax_rows(const float* x, int32_t ldx, int32_t M, int32_t N, int32_t* ids, void* stream) {
     PF_REQUIRE(x && ids && M > 0 && N > 0 && ldx >= N, "k_argmax_rows: null/empty");
     return launch_argmax_rows(x, ldx, M, N, ids, reinterpret_cast<hipStream_t>(stream));
+}
+/* lse[row] = logsumexp(x[row, 0 .. N)) with log_softmax_kernel's reduction, pred[row] = first column of the largest fl(x - lse) */
+int pf_k_log_softmax_stats(const float* x, int32_t ldx, int32_t M, int32_t N, float* lse, int32_t* pred, void* stream) {
+    return launch_log_softmax_stats(x, ldx, M, N, lse, pred, reinterpret_cast<hipStream_t>(stream));
+}
+/* bytes of scratch pf_k_ctc_align needs for B clips of at most T_max frames and L_max labels: the lengths, the gathered emissions
+ * [B, T_max, L_max + 1] and one back-pointer byte per frame and state [B, T_max, 2 L_max + 1] */
+int64_t pf_k_ctc_align_scratch_bytes(int32_t B, int32_t T_max, int32_t L_max) {
+    PF_REQUIRE(B > 0 && T_max >= 0 && T_max <= CTC_ALIGN_MAX_T && L_max >= 1 && L_max <= CTC_ALIGN_MAX_L,
+               "k_ctc_align_scratch_bytes: B > 0, T_max 0 .. 4096, L_max 1 .. 1024");
+    return (int64_t)(ctc_align_lens_bytes(B) + ctc_align_dense_bytes(B, T_max, L_max) + ctc_align_back_bytes(B, T_max, L_max));
+}
+/* batched CTC forced alignment (ctc_align.hip). Every argument is checked before the first launch; the host arrays are copied before the
+ * call returns, which does not synchronise. */
+int pf_k_ctc_align(const float* emis, int32_t ld, int32_t T, int32_t V, int32_t t0, const float* lse, const int32_t* pred,
+                   const int32_t* targets_dev, int32_t ldt, const int32_t* in_lens_host, const int32_t* tgt_lens_host, int32_t B,
+                   int32_t blank, int32_t* labels, int32_t T_out, void* scratch, int64_t scratch_bytes, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    PF_REQUIRE(emis && targets_dev && in_lens_host && tgt_lens_host && labels && scratch && B > 0 && T > 0 && V > 0 && ldt > 0 && T_out > 0,
+               "k_ctc_align: null/empty");
+    PF_REQUIRE(t0 >= 0 && t0 <= T && ld >= V && blank >= 0 && blank < V, "k_ctc_align: t0 outside the rows, ld < V, or blank outside the vocabulary");
+    int T_max = 0, L_max = 1;
+    std::vector<int32_t> lens(2 * (size_t)B);
+    for (int b = 0; b < B; ++b) {
+        const int Tb = in_lens_host[b], Lb = tgt_lens_host[b];
+        PF_REQUIRE(Tb >= 0 && Tb <= CTC_ALIGN_MAX_T, "k_ctc_align: a clip of more than 4096 frames (or a negative length)");
+        PF_REQUIRE(Tb <= T - t0 && Tb <= T_out, "k_ctc_align: a clip longer than the emissions behind t0, or than a row of the output");
+        PF_REQUIRE(Lb >= 1, "k_ctc_align: a clip without target labels");
+        PF_REQUIRE(Lb <= CTC_ALIGN_MAX_L && Lb <= ldt, "k_ctc_align: more than 1024 target labels, or more than a row of `targets`");
+        lens[b] = Tb; lens[(size_t)B + b] = Lb;
+        T_max = std::max(T_max, Tb); L_max = std::max(L_max, Lb);
+    }
+    const size_t nl = ctc_align_lens_bytes(B), nd = ctc_align_dense_bytes(B, T_max, L_max), nb = ctc_align_back_bytes(B, T_max, L_max);
+    PF_REQUIRE(scratch_bytes >= (int64_t)(nl + nd + nb), "k_ctc_align: scratch smaller than pf_k_ctc_align_scratch_bytes(B, max T_b, max L_b)");
+    PF_REQUIRE(((uintptr_t)scratch & 3) == 0, "k_ctc_align: scratch must be 4-byte aligned");
+    if (upload_h2d(scratch, lens.data(), sizeof(int32_t) * lens.size(), s)) return -2;
+    CtcAlignArgs a{};
+    a.emis = emis; a.ld = ld; a.T = T; a.V = V; a.t0 = t0; a.lse = lse; a.pred = pred; a.targets = targets_dev; a.ldt = ldt;
+    a.lens = reinterpret_cast<const int*>(scratch); a.blank = blank; a.B = B; a.T_max = T_max; a.L_max = L_max;
+    a.dense = reinterpret_cast<float*>(static_cast<char*>(scratch) + nl);
+    a.back = reinterpret_cast<unsigned char*>(scratch) + nl + nd;
+    a.labels = labels; a.T_out = T_out;
+    return launch_ctc_align(a, s);
 }
 int pf_k_gemm_f32_time(const float* A, int32_t lda, const float* W, int32_t ldw, const float* bias, float* C,
                        int32_t ldc, int32_t M, int32_t N, int32_t K, int32_t iters, float* ms_out, void* stream) {

@@ -220,21 +220,53 @@ __global__ __launch_bounds__(256) void scale_add_pe_kernel(const float* __restri
 
 // row-wise log-softmax over a vocabulary (decoder / CTC scores for the beam search, paraformer/model.py:345,
 // transformer/scorers/ctc.py:46): one wave per row, three sweeps (max, sum of exp, write), fp32, libm expf / logf
-__global__ __launch_bounds__(256) void log_softmax_kernel(const float* __restrict__ x, int ldx, float* __restrict__ y, int ldy,
-                                                          int M, int N) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= M) return;
-    const float* xr = x + (size_t)row * ldx;
+__device__ __forceinline__ float row_lse(const float* __restrict__ xr, int N, int lane) {
     float mx = -INFINITY;
     for (int j = lane; j < N; j += 64) mx = fmaxf(mx, xr[j]);
     mx = wave_max(mx);
     float sum = 0.f;
     for (int j = lane; j < N; j += 64) sum += expf(xr[j] - mx);
     sum = wave_sum(sum);
-    const float lse = mx + logf(sum);
+    return mx + logf(sum);
+}
+
+__global__ __launch_bounds__(256) void log_softmax_kernel(const float* __restrict__ x, int ldx, float* __restrict__ y, int ldy,
+                                                          int M, int N) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const float* xr = x + (size_t)row * ldx;
+    const float lse = row_lse(xr, N, lane);
     float* yr = y + (size_t)row * ldy;
     for (int j = lane; j < N; j += 64) yr[j] = xr[j] - lse;
+}
+
+// the row statistics of the same log-softmax without its [M, N] output: lse[row] (row_lse: the bits log_softmax_kernel subtracts) and
+// pred[row] = the first column of the largest fl(x[j] - lse), i.e. torch.argmax of the ROUNDED log-probabilities -- two logits one ulp
+// apart may round to one log-probability, and then the earlier column wins as it does on the stored tensor
+__global__ __launch_bounds__(256) void log_softmax_stats_kernel(const float* __restrict__ x, int ldx, int M, int N,
+                                                                float* __restrict__ lse_out, int* __restrict__ pred) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const float* xr = x + (size_t)row * ldx;
+    const float lse = row_lse(xr, N, lane);
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int j = lane; j < N; j += 64) {
+        const float v = xr[j] - lse;
+        if (v > bv) { bv = v; bi = j; }                          // ascending columns per lane: the first maximum stays
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    }
+    if (lane == 0) {
+        lse_out[row] = lse;
+        pred[row] = bi == 0x7fffffff ? 0 : bi;                   // no column above -inf: the first one, like argmax_rows_kernel
+    }
 }
 
 // the same into a padded layout: y is [B, Tp, D], rows t >= T are zero
@@ -453,6 +485,13 @@ int launch_scatter_i32(const int* in, const int* map, int* out, int n, hipStream
 int launch_log_softmax(const float* x, int ldx, float* y, int ldy, int M, int N, hipStream_t stream) {
     PF_REQUIRE(M > 0 && N > 0 && ldx >= N && ldy >= N, "log_softmax: bad shape");
     hipLaunchKernelGGL(log_softmax_kernel, dim3(ceil_div(M, 4)), dim3(256), 0, stream, x, ldx, y, ldy, M, N);
+    PF_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_log_softmax_stats(const float* x, int ldx, int M, int N, float* lse, int* pred, hipStream_t stream) {
+    PF_REQUIRE(x && lse && pred && M > 0 && N > 0 && ldx >= N, "log_softmax_stats: null/empty, or ldx < N");
+    hipLaunchKernelGGL(log_softmax_stats_kernel, dim3(ceil_div(M, 4)), dim3(256), 0, stream, x, ldx, M, N, lse, pred);
     PF_HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -54,6 +54,11 @@ class CTC(HipModule):
         _, logits = self._run(hs_pad, True)
         return ops.log_softmax(logits.contiguous(), inplace=True)          # row kernel, in place over the GEMM's output
 
+    def logits(self, hs_pad):
+        """the projection alone, fp32 [..., odim]: what `log_softmax` normalises in place -- for consumers that take the row
+        statistics (ops.log_softmax_stats) instead of the [.., odim] log-probabilities"""
+        return self._run(hs_pad, True)[1]
+
     def argmax(self, hs_pad, ban_ids=None):
         """frame-wise arg-max over the vocabulary, fused into the projection GEMM. `ban_ids`: classes that must not win (the
         reference writes -inf into their log-probabilities, sense_voice/model.py:1004-1005) -- here a sibling head with the

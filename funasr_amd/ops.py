@@ -290,6 +290,69 @@ def argmax_rows(x: torch.Tensor) -> torch.Tensor:
     return ids
 
 
+CTC_ALIGN_MAX_T, CTC_ALIGN_MAX_L = 4096, 1024      # csrc/ctc_align.h: frames and target labels of one clip of ctc_forced_align
+
+
+def log_softmax_stats(x: torch.Tensor):
+    """The row statistics of log_softmax(x) without its output (pf_k_log_softmax_stats): x fp32 [..., N] (rows contiguous, one
+    row stride) -> (lse fp32 [...], pred int32 [...]). x - lse[..., None] is bit for bit ops.log_softmax(x); pred is the first
+    column of its largest value, i.e. argmax_rows of the rounded log-probabilities."""
+    lib = _lib.load()
+    if not x.is_cuda or x.dtype != torch.float32:
+        raise TypeError("x: expected a float32 tensor in GPU memory")
+    N = x.shape[-1]
+    x2 = x if x.dim() == 2 else x.reshape(-1, N)
+    assert x2.stride(1) == 1
+    M = x2.shape[0]
+    lse = torch.empty(M, device=x.device, dtype=torch.float32)
+    pred = torch.empty(M, device=x.device, dtype=torch.int32)
+    _lib.check(lib.pf_k_log_softmax_stats(_ptr(x2), x2.stride(0), M, N, _ptr(lse), _ptr(pred), _stream()), "pf_k_log_softmax_stats")
+    return lse.view(x.shape[:-1]), pred.view(x.shape[:-1])
+
+
+def ctc_forced_align(log_probs: torch.Tensor, targets: torch.Tensor, input_lengths, target_lengths, blank: int = 0, t0: int = 0,
+                     pred: torch.Tensor = None, lse: torch.Tensor = None, scratch: torch.Tensor = None) -> torch.Tensor:
+    """Batched CTC forced alignment (pf_k_ctc_align), the arithmetic of the reference's `ctc_forced_align` (funasr/models/
+    sense_voice/utils/ctc_alignment.py) comparison by comparison. log_probs fp32 [B, T, V] (a row-strided view is taken as it is);
+    clip b aligns its target_lengths[b] (1 .. 1024) labels targets[b] (int32 [B, Lmax] on the device, ignore ids already mapped to
+    `blank`) to the input_lengths[b] (0 .. 4096, at most T - t0) rows log_probs[b, t0:]; both length lists are host integers.
+    pred (int32 [B, T], the row arg-max): rows with pred == blank take 0 as their blank emission (the reference's
+    `logits[pred == blank, blank] = 0`). lse (fp32 [B, T]): `log_probs` holds LOGITS and the emission is fl(x - lse), the value
+    log_softmax would have stored (ops.log_softmax_stats gives both). scratch (uint8 on the device, at least
+    pf_k_ctc_align_scratch_bytes bytes; contents irrelevant): taken instead of a fresh allocation.
+    -> int32 [B, T - t0]: the label or `blank` of every frame of the clip, -1 behind its frames. Two launches (gather, then
+    recurrence + back-trace, csrc/ctc_align.hip), enqueued, not synchronised."""
+    lib = _lib.load()
+    if not log_probs.is_cuda or log_probs.dtype != torch.float32:
+        raise TypeError("log_probs: expected a float32 tensor in GPU memory")
+    if not targets.is_cuda or targets.dtype != torch.int32:
+        raise TypeError("targets: expected an int32 tensor in GPU memory")
+    B, T, V = log_probs.shape
+    assert log_probs.stride(2) == 1 and (B == 1 or log_probs.stride(0) == T * log_probs.stride(1)), "one row stride over [B, T]"
+    assert targets.dim() == 2 and targets.shape[0] == B and targets.stride(1) == 1
+    dev = log_probs.device
+    for name, t, dt in (("pred", pred, torch.int32), ("lse", lse, torch.float32)):
+        if t is not None and (not t.is_cuda or t.dtype != dt or tuple(t.shape) != (B, T) or not t.is_contiguous()):
+            raise TypeError(f"{name}: expected a contiguous {dt} tensor [B, T] in GPU memory")
+    in_lens, tg_lens = [int(v) for v in input_lengths], [int(v) for v in target_lengths]
+    assert len(in_lens) == B and len(tg_lens) == B
+    T_out = T - int(t0)
+    if T_out <= 0:
+        return torch.empty(B, 0, device=dev, dtype=torch.int32)
+    in_c, tg_c = (C.c_int32 * B)(*in_lens), (C.c_int32 * B)(*tg_lens)
+    # (lengths outside the kernel's limits: a scratch of one byte, and pf_k_ctc_align refuses the call with its own message)
+    clamp = lambda v, lo, hi: max(lo, min(hi, v))
+    nbytes = int(lib.pf_k_ctc_align_scratch_bytes(B, clamp(max(in_lens), 0, CTC_ALIGN_MAX_T), clamp(max(tg_lens), 1, CTC_ALIGN_MAX_L)))
+    if scratch is None:
+        scratch = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
+    assert scratch.is_cuda and scratch.dtype == torch.uint8 and scratch.is_contiguous()
+    out = torch.empty(B, T_out, device=dev, dtype=torch.int32)
+    _lib.check(lib.pf_k_ctc_align(_ptr(log_probs), log_probs.stride(1), T, V, int(t0), _ptr(lse), _ptr(pred), _ptr(targets),
+                                  targets.stride(0), in_c, tg_c, B, int(blank), _ptr(out), T_out, _ptr(scratch), scratch.numel(),
+                                  _stream()), "pf_k_ctc_align")
+    return out
+
+
 def gemm_time_ms(a, w, bias, out, iters: int = 20) -> float:
     lib = _lib.load()
     M, K = a.shape

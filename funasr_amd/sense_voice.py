@@ -5,7 +5,10 @@ for the CTC-greedy inference path: same constructor keywords, state_dict layout 
 ctc.ctc_lo.*), the four query frames [language, event, emotion, textnorm] placed in front of the speech features
 (:971-995) and `inference(...) -> (results, meta_data)`. The [B, T, 25055] log-softmax is never materialised: the
 arg-max is fused into the CTC projection GEMM (`ban_emo_unk`: a -inf bias for <|EMO_UNKNOWN|> on a sibling head, same
-single launch); `output_timestamp` adds the reference's CTC forced alignment of the decoded pieces on the host (:1036-1078).
+single launch). `output_timestamp` adds the reference's CTC forced alignment of the decoded pieces (:1036-1078): on a GPU one batched
+device pass -- the logits GEMM, their row statistics (`ops.log_softmax_stats`: the log-probabilities are never stored) and
+`ops.ctc_forced_align` -- whose [B, T] frame labels are the only thing copied back; `ctc_timestamps` / `ctc_forced_align` below are
+the per-clip host form of the same arithmetic, kept for clips above the kernel's limits and as the tests' oracle.
 """
 from __future__ import annotations
 
@@ -172,14 +175,10 @@ class SenseVoiceSmall(nn.Module):
             prev = word
         return stamps, words
 
-    def ctc_timestamps(self, text: str, logp_speech, tokenizer):
-        """The `output_timestamp` branch of the reference for one utterance (model.py:1036-1078): the decoded text is cut
-        into pieces again (the four rich-tag pieces in front dropped), the pieces' ids are force-aligned to the CTC
-        log-probabilities of the speech frames (frames whose arg-max is blank get blank log-probability 0 first), every run
-        of a non-blank label becomes [piece, start, end] in seconds at 60 ms per frame, shifted by half a frame.
-        logp_speech: float [T - 4, V] (host). -> (timestamp, words) or None when the text has no pieces."""
-        from itertools import groupby
-        import numpy as np
+    def timestamp_targets(self, text: str, tokenizer):
+        """The alignment targets of one decoded text (model.py:1036-1050): the text cut into pieces again, the four rich-tag
+        pieces in front dropped, a piece without ids standing in as id 124, `ignore_id` mapped to blank.
+        -> (pieces, int64 ids) or None when the text has no pieces."""
         tokens = tokenizer.text2tokens(text)[4:]
         token_ids = []
         for ids in tokenizer.tokens2ids(tokens):
@@ -189,21 +188,85 @@ class SenseVoiceSmall(nn.Module):
                 token_ids.append(124)                            # the reference's stand-in for a piece without ids
         if len(token_ids) == 0:
             return None
-        lp = np.array(logp_speech, dtype=np.float32, copy=True)
-        pred = lp.argmax(-1)
-        lp[pred == self.blank_id, self.blank_id] = 0
         tg = np.asarray(token_ids, dtype=np.int64)
         tg[tg == self.ignore_id] = self.blank_id
-        align = ctc_forced_align(lp, tg, blank=self.blank_id)
-        ts_max = lp.shape[0]
+        return tokens, tg
+
+    def stamps_from_labels(self, tokens, labels):
+        """Frame labels of the speech frames (int [T - 4], host) -> (timestamp, words) (model.py:1060-1078): every run of a
+        non-blank label becomes [piece, start, end] in seconds at 60 ms per frame, shifted by half a frame, then `post`."""
+        from itertools import groupby
+        ts_max = len(labels)
         timestamp, start, k = [], 0, 0
-        for label, run in groupby(align.tolist()):
+        for label, run in groupby(labels):
             end = start + len(list(run))
             if label != 0:
                 timestamp.append([tokens[k], max((start * 60 - 30) / 1000, 0), min((end * 60 - 30) / 1000, (ts_max * 60 - 30) / 1000)])
                 k += 1
             start = end
         return self.post(timestamp)
+
+    def ctc_timestamps(self, text: str, logp_speech, tokenizer):
+        """The `output_timestamp` branch of the reference for one utterance (model.py:1036-1078) on the host: the pieces' ids
+        (`timestamp_targets`) are force-aligned to the CTC log-probabilities of the speech frames (frames whose arg-max is blank
+        get blank log-probability 0 first), the runs of the frame labels become the stamps (`stamps_from_labels`).
+        logp_speech: float [T - 4, V] (host). -> (timestamp, words) or None when the text has no pieces."""
+        targets = self.timestamp_targets(text, tokenizer)
+        if targets is None:
+            return None
+        tokens, tg = targets
+        lp = np.array(logp_speech, dtype=np.float32, copy=True)
+        pred = lp.argmax(-1)
+        lp[pred == self.blank_id, self.blank_id] = 0
+        align = ctc_forced_align(lp, tg, blank=self.blank_id)
+        return self.stamps_from_labels(tokens, align.tolist())
+
+    def enqueue_alignment(self, res: dict, texts, tokenizer) -> dict:
+        """`output_timestamp` for a whole batch on the device, ENQUEUED: targets from the decoded texts (host), one upload, the
+        logits GEMM, `log_softmax_stats`, one `ctc_forced_align` over the ragged batch and the copy of its [B, T - 4] labels
+        into pinned memory. A clip without pieces takes no frames (its row stays at the fill); a clip above the kernel's limits
+        is left to the host path by `collect_alignment`."""
+        from . import ops
+        CTC_ALIGN_MAX_T, CTC_ALIGN_MAX_L = ops.CTC_ALIGN_MAX_T, ops.CTC_ALIGN_MAX_L
+        enc = res["enc"]
+        B = enc.shape[0]
+        olens = [int(v) for v in torch.as_tensor(res["olens"]).tolist()]
+        targets = [self.timestamp_targets(t, tokenizer) for t in texts]
+        host = [i for i, tg in enumerate(targets)
+                if tg is not None and (len(tg[1]) > CTC_ALIGN_MAX_L or olens[i] - 4 > CTC_ALIGN_MAX_T)]
+        on_dev = [tg is not None and i not in host and olens[i] > 4 for i, tg in enumerate(targets)]
+        pending = dict(targets=targets, olens=olens, host=host, labels=None)
+        if any(on_dev) or host:
+            logits = self.ctc.logits(enc)                        # [B, T, V]; dropped when this call returns (stream-ordered)
+        if host:
+            pending["host_logp"] = {i: ops.log_softmax(logits[i, 4:olens[i]].contiguous()).cpu() for i in host}
+        if any(on_dev):
+            in_lens = [olens[i] - 4 if on_dev[i] else 0 for i in range(B)]
+            tg_lens = [len(targets[i][1]) if on_dev[i] else 1 for i in range(B)]     # (a clip that takes no frames: one blank)
+            tg = np.full((B, max(tg_lens)), self.blank_id, dtype=np.int32)
+            for i in range(B):
+                if on_dev[i]:
+                    tg[i, :tg_lens[i]] = targets[i][1]
+            lse, pred = ops.log_softmax_stats(logits)
+            labels = ops.ctc_forced_align(logits, torch.from_numpy(tg).to(enc.device), in_lens, tg_lens, blank=self.blank_id, t0=4,
+                                          pred=pred, lse=lse)
+            pending["labels"] = self.__dict__.setdefault("_host_ring", HostCopyRing()).start(labels)
+            pending["in_lens"] = in_lens
+        return pending
+
+    def collect_alignment(self, pending: dict, texts, tokenizer) -> list:
+        """-> per clip (timestamp, words) or None; waits for the labels' copy only"""
+        labels = HostCopyRing.wait(pending["labels"]).numpy() if pending["labels"] is not None else None
+        out = []
+        for i, tg in enumerate(pending["targets"]):
+            if tg is None:
+                out.append(None)
+            elif i in pending["host"]:
+                out.append(self.ctc_timestamps(texts[i], pending["host_logp"][i].numpy(), tokenizer))
+            else:
+                n = pending["in_lens"][i] if labels is not None else 0
+                out.append(self.stamps_from_labels(tg[0], labels[i, :n].tolist() if n else []))
+        return out
 
     # per-process staging objects (HIP streams, pinned buffers) are never copied or pickled with the module
     def __getstate__(self):
@@ -219,19 +282,28 @@ class SenseVoiceSmall(nn.Module):
         return self._records(res, key, tokenizer, meta_data, output_timestamp)
 
     # ---- the same call in parts for AutoModel.inference's loop over batches (see paraformer.py inference_begin): the encoder +
-    #      CTC arg-max of batch i + 1 are enqueued before batch i's frame ids are read and turned into text
+    #      CTC arg-max of batch i + 1 are enqueued before batch i's frame ids are read and turned into text -- and, with
+    #      `output_timestamp`, before batch i's alignment is enqueued (inference_launch), whose labels inference_end waits for
     def inference_begin(self, data_in, data_lengths=None, key: list = ["wav_file_tmp_name"], tokenizer=None, frontend=None, **kwargs):
-        if (kwargs.get("output_timestamp", False) or kwargs.get("data_type", "sound") == "fbank"
+        # (ready features without timestamps keep the plain loop they always had; with timestamps the split form is the point)
+        if ((kwargs.get("data_type", "sound") == "fbank" and not kwargs.get("output_timestamp", False))
                 or not str(kwargs.get("device", "")).startswith("cuda")):
             return None
-        args, ban, meta_data, _ = self._inference_inputs(data_in, data_lengths, tokenizer, frontend, kwargs, staged=True)
-        return dict(enq=self.enqueue_features(*args, ban_ids=ban), key=key, tokenizer=tokenizer, meta_data=meta_data)
+        args, ban, meta_data, output_timestamp = self._inference_inputs(data_in, data_lengths, tokenizer, frontend, kwargs, staged=True)
+        return dict(enq=self.enqueue_features(*args, ban_ids=ban, return_intermediate=output_timestamp), key=key, tokenizer=tokenizer,
+                    meta_data=meta_data, output_timestamp=output_timestamp)
 
     def inference_launch(self, pending: dict) -> None:
-        return None                                              # nothing waits for the host between the encoder and the ids
+        if pending.get("output_timestamp") and "res" not in pending:
+            pending["res"] = self.collect(pending.pop("enq"))
+            self._decode_texts(pending["res"], pending["tokenizer"])
+            self._enqueue_timestamps(pending["res"], pending["tokenizer"])
+        return None                                              # without timestamps nothing waits for the host between the encoder and the ids
 
     def inference_end(self, pending: dict):
-        return self._records(self.collect(pending.pop("enq")), pending["key"], pending["tokenizer"], pending["meta_data"], False)
+        self.inference_launch(pending)
+        res = pending.pop("res") if "res" in pending else self.collect(pending.pop("enq"))
+        return self._records(res, pending["key"], pending["tokenizer"], pending["meta_data"], pending.get("output_timestamp", False))
 
     def _inference_inputs(self, data_in, data_lengths, tokenizer, frontend, kwargs, staged):
         """-> ((speech, speech_lengths, language, textnorm) and ban_ids of recognize_features / enqueue_features, meta_data, output_timestamp)"""
@@ -245,11 +317,22 @@ class SenseVoiceSmall(nn.Module):
         ban = [self.emo_dict["unk"]] if kwargs.get("ban_emo_unk", False) else None          # model.py:1004-1005
         return (speech, speech_lengths, kwargs.get("language", "auto"), textnorm), ban, meta_data, output_timestamp
 
+    @staticmethod
+    def _decode_texts(res, tokenizer):
+        if tokenizer is not None and "texts" not in res:
+            res["texts"] = [tokenizer.decode(ids) for ids in res["ids"]]
+
+    def _enqueue_timestamps(self, res, tokenizer):
+        if "align" not in res:
+            res["align"] = self.enqueue_alignment(res, res["texts"], tokenizer)
+
     def _records(self, res, key, tokenizer, meta_data, output_timestamp):
         B = len(res["ids"])
-        logp = None
-        if output_timestamp:                                     # one D2H copy of the batch's log-probabilities (:1045)
-            logp = self.ctc.log_softmax(res["enc"]).cpu()
+        self._decode_texts(res, tokenizer)
+        stamps = None
+        if output_timestamp:                                     # one D2H copy of the batch's frame labels
+            self._enqueue_timestamps(res, tokenizer)
+            stamps = self.collect_alignment(res["align"], res["texts"], tokenizer)
         if isinstance(key[0], (list, tuple)):
             key = key[0]
         if len(key) < B:
@@ -259,11 +342,8 @@ class SenseVoiceSmall(nn.Module):
             if tokenizer is None:
                 results.append({"key": key[i], "token_int": res["ids"][i]})
                 continue
-            item = {"key": key[i], "text": tokenizer.decode(res["ids"][i])}
-            if output_timestamp:
-                n = int(res["olens"][i])
-                ts = self.ctc_timestamps(item["text"], logp[i, 4:n].numpy(), tokenizer)
-                if ts is not None:
-                    item["timestamp"], item["words"] = ts
+            item = {"key": key[i], "text": res["texts"][i]}
+            if stamps is not None and stamps[i] is not None:
+                item["timestamp"], item["words"] = stamps[i]
             results.append(item)
         return results, meta_data

@@ -818,6 +818,22 @@ int pf_k_ctc_runs(const int32_t* ids_dev, const int32_t* lens_host, int32_t B, i
 /* ids[row] = first column of the largest of x[row, 0 .. N) (row stride ldx >= N), as torch.argmax (a row of -inf only: 0; NaN
  * unspecified): the arg-max of the streaming decoder and of the vocabulary projection when logits are requested */
 int pf_k_argmax_rows(const float* x, int32_t ldx, int32_t M, int32_t N, int32_t* ids, void* stream);
+/* the row statistics of pf_k_log_softmax without its output: lse[row] = logsumexp(x[row, 0 .. N)) by the same reduction (x - lse is
+ * bit for bit what pf_k_log_softmax stores), pred[row] = first column of the largest fl(x[row][j] - lse[row]), i.e. torch.argmax of the
+ * rounded log-probabilities */
+int pf_k_log_softmax_stats(const float* x, int32_t ldx, int32_t M, int32_t N, float* lse, int32_t* pred, void* stream);
+/* batched CTC forced alignment, the arithmetic of funasr/models/sense_voice/utils/ctc_alignment.py comparison by comparison. Clip b
+ * of B reads the in_lens_host[b] (0 .. 4096) rows b * T + t0 + t of emis [B, T, V] (row stride ld) and its tgt_lens_host[b]
+ * (1 .. 1024) labels targets_dev[b * ldt + l] (device int32, ignore ids already mapped to `blank`; a label outside [0, V) emits
+ * -inf); labels [B, T_out] (device int32) receives the label or `blank` aligned to every frame, -1 behind the clip's frames.
+ * lse (may be NULL, device [B * T]): emis holds logits and the emission is fl(x - lse[row]). pred (may be NULL, device int32
+ * [B * T]): rows with pred == blank take 0 as their blank emission. scratch: device memory of at least
+ * pf_k_ctc_align_scratch_bytes(B, max in_lens, max tgt_lens) bytes, contents irrelevant. Anything outside these limits is refused
+ * before the first launch. The host arrays are copied before the call returns; it does not synchronise. */
+int64_t pf_k_ctc_align_scratch_bytes(int32_t B, int32_t T_max, int32_t L_max);
+int pf_k_ctc_align(const float* emis, int32_t ld, int32_t T, int32_t V, int32_t t0, const float* lse, const int32_t* pred,
+                   const int32_t* targets_dev, int32_t ldt, const int32_t* in_lens_host, const int32_t* tgt_lens_host, int32_t B,
+                   int32_t blank, int32_t* labels, int32_t T_out, void* scratch, int64_t scratch_bytes, void* stream);
 /* average kernel time in milliseconds of `iters` back-to-back launches of the GEMM above, measured with
  * hipEvents on `stream` (used by bench.py for the roofline line) */
 int pf_k_gemm_f32_time(const float* A, int32_t lda, const float* W, int32_t ldw, const float* bias, float* C,
