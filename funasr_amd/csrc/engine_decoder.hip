@@ -1,56 +1,108 @@
-// C-ABI layer, predictor / decoder / CTC family: pf_predictor_*, pf_decoder_*, pf_ctc_*.
+// C-ABI layer, decoder / CTC family: pf_decoder_*, pf_ctc_*.
 #include "engine_internal.h"
 
 namespace pf {
 
 // ContextualParaformerDecoder keeps its last attention block under "last_decoder." (contextual_paraformer/decoder.py:241)
-std::string dec_layer_prefix(bool contextual, int n_blocks, int i) {
+static std::string dec_layer_prefix(bool contextual, int n_blocks, int i) {
     return (contextual && i == n_blocks - 1) ? std::string("last_decoder.") : "decoders." + std::to_string(i) + ".";
 }
+static std::string dec2_layer_prefix(int i) { return "decoders2." + std::to_string(i) + "."; }
 
+// ---- THE description of a decoder layer (DecoderLayerSANM, paraformer/decoder.py:78-121): the tensors under its prefix, by kind
+// (DecLayerW.kind). These two functions are the only place that spells the names: a tensor added to a layer is added here, and a new
+// decoder variant adds a kind, not a copy of the list.
+static int dec_layer_add(TensorTable& tt, const pf_decoder_config& c, const std::string& p, int kind) {
+    const int D = c.d_model, F = c.ffn_dim;
+    int rc = 0;
+    rc |= tt.add(p + "norm1.weight", D);
+    rc |= tt.add(p + "norm1.bias", D);
+    rc |= tt.add(p + "feed_forward.w_1.weight", (int64_t)F * D);
+    rc |= tt.add(p + "feed_forward.w_1.bias", F);
+    rc |= tt.add(p + "feed_forward.norm.weight", F);
+    rc |= tt.add(p + "feed_forward.norm.bias", F);
+    rc |= tt.add(p + "feed_forward.w_2.weight", (int64_t)D * F);
+    if (kind >= DEC_FFN_FSMN) {
+        rc |= tt.add(p + "norm2.weight", D);
+        rc |= tt.add(p + "norm2.bias", D);
+        rc |= tt.add(p + "self_attn.fsmn_block.weight", (int64_t)D * c.kernel_size);
+    }
+    if (kind >= DEC_FFN_FSMN_ATTN) {
+        rc |= tt.add(p + "norm3.weight", D);
+        rc |= tt.add(p + "norm3.bias", D);
+        rc |= tt.add(p + "src_attn.linear_q.weight", (int64_t)D * D);
+        rc |= tt.add(p + "src_attn.linear_q.bias", D);
+        rc |= tt.add(p + "src_attn.linear_k_v.weight", (int64_t)2 * D * D);
+        rc |= tt.add(p + "src_attn.linear_k_v.bias", 2 * D);
+        rc |= tt.add(p + "src_attn.linear_out.weight", (int64_t)D * D);
+        rc |= tt.add(p + "src_attn.linear_out.bias", D);
+    }
+    return rc;
+}
+static DecLayerW dec_layer_resolve(const TensorTable& tt, const std::string& p, int kind) {
+    DecLayerW w;
+    w.prefix = p; w.kind = kind;
+    w.n1g = tt.get(p + "norm1.weight"); w.n1b = tt.get(p + "norm1.bias");
+    w.w1 = tt.get(p + "feed_forward.w_1.weight"); w.b1 = tt.get(p + "feed_forward.w_1.bias");
+    w.fng = tt.get(p + "feed_forward.norm.weight"); w.fnb = tt.get(p + "feed_forward.norm.bias");
+    w.w2 = tt.get(p + "feed_forward.w_2.weight");
+    if (kind >= DEC_FFN_FSMN) {
+        w.n2g = tt.get(p + "norm2.weight"); w.n2b = tt.get(p + "norm2.bias");
+        w.fsmn_w = tt.get(p + "self_attn.fsmn_block.weight");
+    }
+    if (kind >= DEC_FFN_FSMN_ATTN) {
+        w.n3g = tt.get(p + "norm3.weight"); w.n3b = tt.get(p + "norm3.bias");
+        w.q_w = tt.get(p + "src_attn.linear_q.weight"); w.q_b = tt.get(p + "src_attn.linear_q.bias");
+        w.kv_w = tt.get(p + "src_attn.linear_k_v.weight"); w.kv_b = tt.get(p + "src_attn.linear_k_v.bias");
+        w.o_w = tt.get(p + "src_attn.linear_out.weight"); w.o_b = tt.get(p + "src_attn.linear_out.bias");
+    }
+    return w;
+}
 
 static int decoder_resolve(Decoder* d) {
     if (d->tt.require_all("decoder")) return -3;
     d->layers.clear();
-    for (int i = 0; i < d->cfg.n_blocks; ++i) {
-        const std::string p = dec_layer_prefix(d->contextual, d->cfg.n_blocks, i);
-        DecLayerW w;
-        w.n1g = d->tt.get(p + "norm1.weight"); w.n1b = d->tt.get(p + "norm1.bias");
-        w.w1 = d->tt.get(p + "feed_forward.w_1.weight"); w.b1 = d->tt.get(p + "feed_forward.w_1.bias");
-        w.fng = d->tt.get(p + "feed_forward.norm.weight"); w.fnb = d->tt.get(p + "feed_forward.norm.bias");
-        w.w2 = d->tt.get(p + "feed_forward.w_2.weight");
-        w.n2g = d->tt.get(p + "norm2.weight"); w.n2b = d->tt.get(p + "norm2.bias");
-        w.fsmn_w = d->tt.get(p + "self_attn.fsmn_block.weight");
-        w.n3g = d->tt.get(p + "norm3.weight"); w.n3b = d->tt.get(p + "norm3.bias");
-        w.q_w = d->tt.get(p + "src_attn.linear_q.weight"); w.q_b = d->tt.get(p + "src_attn.linear_q.bias");
-        w.kv_w = d->tt.get(p + "src_attn.linear_k_v.weight"); w.kv_b = d->tt.get(p + "src_attn.linear_k_v.bias");
-        w.o_w = d->tt.get(p + "src_attn.linear_out.weight"); w.o_b = d->tt.get(p + "src_attn.linear_out.bias");
-        d->layers.push_back(w);
-    }
+    for (int i = 0; i < d->cfg.n_blocks; ++i)
+        d->layers.push_back(dec_layer_resolve(d->tt, dec_layer_prefix(d->contextual, d->cfg.n_blocks, i), DEC_FFN_FSMN_ATTN));
     d->layers2.clear();
-    for (int i = 0; i < d->n_blocks2; ++i) {
-        const std::string p = "decoders2." + std::to_string(i) + ".";
-        DecLayerW w{};
-        w.n1g = d->tt.get(p + "norm1.weight"); w.n1b = d->tt.get(p + "norm1.bias");
-        w.w1 = d->tt.get(p + "feed_forward.w_1.weight"); w.b1 = d->tt.get(p + "feed_forward.w_1.bias");
-        w.fng = d->tt.get(p + "feed_forward.norm.weight"); w.fnb = d->tt.get(p + "feed_forward.norm.bias");
-        w.w2 = d->tt.get(p + "feed_forward.w_2.weight");
-        w.n2g = d->tt.get(p + "norm2.weight"); w.n2b = d->tt.get(p + "norm2.bias");
-        w.fsmn_w = d->tt.get(p + "self_attn.fsmn_block.weight");
-        d->layers2.push_back(w);
-    }
-    {
-        const std::string p = "decoders3.0.";
-        DecLayerW w{};
-        w.n1g = d->tt.get(p + "norm1.weight"); w.n1b = d->tt.get(p + "norm1.bias");
-        w.w1 = d->tt.get(p + "feed_forward.w_1.weight"); w.b1 = d->tt.get(p + "feed_forward.w_1.bias");
-        w.fng = d->tt.get(p + "feed_forward.norm.weight"); w.fnb = d->tt.get(p + "feed_forward.norm.bias");
-        w.w2 = d->tt.get(p + "feed_forward.w_2.weight");
-        d->last = w;
-    }
+    for (int i = 0; i < d->n_blocks2; ++i) d->layers2.push_back(dec_layer_resolve(d->tt, dec2_layer_prefix(i), DEC_FFN_FSMN));
+    d->last = dec_layer_resolve(d->tt, "decoders3.0.", DEC_FFN);
     d->resolved_for = d->tt.version;
     d->x2_for = TensorTable::NOT_PREPARED;
     return 0;
+}
+
+// ---- the fused arg-max tails of the vocabulary / CTC projections, one per arithmetic: ids[row] = argmax_n (A W^T + bias)[row, n],
+// lowest index on ties, from the GEMM epilogue's partials sval / sidx [M, parts] (argmax_scratch) and one reduction; no [M, N] logits
+int argmax_scratch(DevBuf& pval, DevBuf& pidx, int M, int parts) {
+    return (pval.ensure(sizeof(float) * (size_t)M * parts) || pidx.ensure(sizeof(int) * (size_t)M * parts)) ? -2 : 0;
+}
+// fp32 MFMA tile from fp32 or (ab_bf16) bf16 operands; parts = argmax_f32_parts(N)
+int argmax_f32(const float* A, int lda, const float* W, int ldw, const float* bias, int M, int N, int K, int ab_bf16, float* sval,
+               int* sidx, int32_t* ids, hipStream_t s) {
+    const int parts = argmax_f32_parts(N);
+    GemmArgs g{};
+    g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.M = M; g.N = N; g.K = K; g.ab_bf16 = ab_bf16;
+    g.amax_val = sval; g.amax_idx = sidx; g.amax_ld = parts;
+    int rc;
+    if ((rc = gemm(g, s))) return rc;
+    return launch_argmax_reduce(sval, sidx, parts, parts, ids, nullptr, M, s);
+}
+// fp16 matrix cores from two-plane operands (gemm_f16x2.hip); the result scale is oscale (times *oscale_dev when the planes' scale
+// was chosen on the device); parts = gemm_f16x2_argmax_parts(M, N)
+int argmax_f16x2(const unsigned short* A2, int lda, size_t a_plane, const unsigned short* W2, int ldw, size_t w_plane, float oscale,
+                 const float* oscale_dev, const float* bias, int M, int N, int K, float* sval, int* sidx, int32_t* ids, hipStream_t s) {
+    const int parts = gemm_f16x2_argmax_parts(M, N);
+    Gemm2Args g{};
+    g.A = A2; g.lda = lda; g.a_plane = a_plane; g.W = W2; g.ldw = ldw; g.w_plane = w_plane;
+    g.oscale = oscale; g.oscale_dev = oscale_dev; g.bias = bias; g.M = M; g.N = N; g.K = K;
+    g.amax_val = sval; g.amax_idx = sidx; g.amax_ld = parts;
+    int rc;
+    {
+        ProfScope ps(PROF_GEMM3, 2.0 * M * (double)N * K, s);
+        if ((rc = launch_gemm_f16x2(g, s))) return rc;
+    }
+    return launch_argmax_reduce(sval, sidx, parts, parts, ids, nullptr, M, s);
 }
 
 // shared tail: logits / fused argmax of a [M, D] hidden against a [V, D] vocabulary projection
@@ -69,16 +121,9 @@ int vocab_project(const float* hidden, int M, int D, const float* W, const float
         if ((rc = gemm_simple(hidden, D, W, D, bias, pval.as<float>(), V, M, V, D, 0, nullptr, 0, nullptr, 0, s))) return rc;
         return launch_argmax_rows(pval.as<float>(), V, M, V, ids, s);
     }
-    const int nparts = 2 * ceil_div(V, 128);
-    if (pval.ensure(sizeof(float) * (size_t)M * nparts) || pidx.ensure(sizeof(int) * (size_t)M * nparts)) return -2;
-    GemmArgs g{};
-    g.A = hidden; g.lda = D; g.W = W; g.ldw = D; g.bias = bias; g.C = nullptr; g.ldc = 0; g.M = M; g.N = V; g.K = D;
-    g.amax_val = pval.as<float>(); g.amax_idx = pidx.as<int>(); g.amax_ld = nparts;
-    if ((rc = gemm(g, s))) return rc;
-    return launch_argmax_reduce(pval.as<float>(), pidx.as<int>(), nparts, nparts, ids, nullptr, M, s);
+    if (argmax_scratch(pval, pidx, M, argmax_f32_parts(V))) return -2;
+    return argmax_f32(hidden, D, W, D, bias, M, V, D, 0, pval.as<float>(), pidx.as<int>(), ids, s);
 }
-
-
 
 // PositionwiseFeedForwardDecoderSANM (sanm/positionwise_feed_forward.py:12-33): w_2(LN(relu(w_1 x))), w_2 bias-free
 int gemm3_simple(const unsigned short* A3, int lda, int M, const unsigned short* W3, const float* bias, float* C,
@@ -105,8 +150,9 @@ int gemm2_simple(const unsigned short* A2, int lda, int M, int ea, const unsigne
 }
 
 // f16x2 mode: exponents and weight planes of one decoder layer (the per-layer worker of decoder_prepare)
-static int dec_layer_x2(Decoder* d, DecLayerW& w, const std::string& p, bool attn, hipStream_t s) {
+static int dec_layer_x2(Decoder* d, DecLayerW& w, hipStream_t s) {
     const int D = d->cfg.d_model, F = d->cfg.ffn_dim;
+    const std::string& p = w.prefix;
     float b;
     if (TensorTable::dev_ln_bound(w.n1g, w.n1b, D, &b, s)) return -2;
     w.e_n1 = exp_for_bound(b);
@@ -115,7 +161,7 @@ static int dec_layer_x2(Decoder* d, DecLayerW& w, const std::string& p, bool att
     w.w1_2 = d->tt.get_split2(p + "feed_forward.w_1.weight", F, D, &w.ew_1, s);
     w.w2_2 = d->tt.get_split2(p + "feed_forward.w_2.weight", D, F, &w.ew_2, s);
     if (!w.w1_2 || !w.w2_2) return -2;
-    if (attn) {
+    if (w.kind == DEC_FFN_FSMN_ATTN) {
         if (TensorTable::dev_ln_bound(w.n3g, w.n3b, D, &b, s)) return -2;
         w.e_n3 = exp_for_bound(b);
         w.q_2 = d->tt.get_split2(p + "src_attn.linear_q.weight", D, D, &w.ew_q, s);
@@ -140,11 +186,9 @@ int decoder_prepare(Decoder* d, bool x2, hipStream_t s) {
     if (d->resolved_for != d->tt.version && (rc = decoder_resolve(d))) return rc;
     if (!x2 || d->x2_for == d->tt.version) return 0;
     const pf_decoder_config& c = d->cfg;
-    for (int l = 0; l < c.n_blocks; ++l)
-        if ((rc = dec_layer_x2(d, d->layers[l], dec_layer_prefix(d->contextual, c.n_blocks, l), true, s))) return rc;
-    for (int l = 0; l < d->n_blocks2; ++l)
-        if ((rc = dec_layer_x2(d, d->layers2[l], "decoders2." + std::to_string(l) + ".", false, s))) return rc;
-    if ((rc = dec_layer_x2(d, d->last, "decoders3.0.", false, s))) return rc;
+    for (DecLayerW& w : d->layers) if ((rc = dec_layer_x2(d, w, s))) return rc;
+    for (DecLayerW& w : d->layers2) if ((rc = dec_layer_x2(d, w, s))) return rc;
+    if ((rc = dec_layer_x2(d, d->last, s))) return rc;
     std::vector<float> lb((size_t)4 * c.n_blocks);
     for (int l = 0; l < c.n_blocks; ++l) for (int j = 0; j < 4; ++j) lb[4 * l + j] = d->layers[l].kv_l1b[j];
     if (d->dlb.ensure(sizeof(float) * lb.size())) return -2;
@@ -161,8 +205,7 @@ int decoder_prepare(Decoder* d, bool x2, hipStream_t s) {
 
 // f16x2 form of dec_ffn: both LayerNorms write two-plane fp16 operands, w_1 and w_2 run on the fp16 matrix cores
 // ln (streaming step, split-K w_2): the LayerNorm that follows the block rides in w_2's second launch (Gemm2Args.ln_*)
-// fold_fn (with splitk_part of 4 * M * ffn_dim floats): the FFN's inner norm rides in the second launch of a split-K w_1
-int dec_ffn_x2(Decoder* d, const DecLayerW& w, const float* x, float* out, int M, hipStream_t s, float* splitk_part, const FoldedLn* ln, bool fold_fn) {
+int dec_ffn_x2(Decoder* d, const DecLayerW& w, const float* x, float* out, int M, hipStream_t s, float* splitk_part, const FoldedLn* ln) {
     const int D = d->cfg.d_model, F = d->cfg.ffn_dim;
     float* ffn = d->ffn.as<float>();
     unsigned short* t2p = d->t16.as<unsigned short>();
@@ -218,12 +261,70 @@ int dec_ffn(Decoder* d, const DecLayerW& w, const float* x, float* out, int M, h
     return gemm_simple(ffn2, F, w.w2, F, nullptr, out, D, M, D, F, 0, nullptr, 0, nullptr, 0, s);
 }
 
+// bf16-operand GEMM (throughput mode): A and W bf16, fp32 accumulation, C fp32 or (c16) bf16
+static int gemm_bf16(const unsigned short* A, int lda, const unsigned short* W, int ldw, const float* bias, void* C, int ldc, int M,
+                     int N, int K, int relu, const float* R2, int ldr2, int c16, hipStream_t s) {
+    if (!W) return -2;
+    GemmArgs g{};
+    g.A = reinterpret_cast<const float*>(A); g.lda = lda; g.W = reinterpret_cast<const float*>(W); g.ldw = ldw;
+    g.bias = bias; g.R2 = R2; g.ldr2 = ldr2; g.C = reinterpret_cast<float*>(C); g.ldc = ldc;
+    g.M = M; g.N = N; g.K = K; g.relu = relu; g.ab_bf16 = 1; g.c_bf16 = c16;
+    ProfScope ps(PROF_GEMM, 2.0 * M * (double)N * K, s);
+    return launch_gemm_f32(g, s);
+}
+
+// bf16 form of dec_ffn: both LayerNorms write bf16 rows, w_1 and w_2 take bf16 operands (the copies are cached by the table)
+static int dec_ffn_bf16(Decoder* d, const DecLayerW& w, const float* x, float* out, int M, hipStream_t s) {
+    const int D = d->cfg.d_model, F = d->cfg.ffn_dim;
+    unsigned short* t16 = d->t16.as<unsigned short>();
+    unsigned short* ffn16 = d->ffn16.as<unsigned short>();
+    unsigned short* ffn2_16 = d->ffn2_16.as<unsigned short>();
+    int rc;
+    if ((rc = launch_layernorm(x, D, w.n1g, w.n1b, reinterpret_cast<float*>(t16), D, M, D, D, d->cfg.ln_eps, s, 1, 0))) return rc;
+    if ((rc = gemm_bf16(t16, D, d->tt.get_bf16(w.prefix + "feed_forward.w_1.weight", s), D, w.b1, ffn16, F, M, F, D, 1, nullptr, 0, 1, s)))
+        return rc;
+    if ((rc = launch_layernorm(reinterpret_cast<const float*>(ffn16), F, w.fng, w.fnb, reinterpret_cast<float*>(ffn2_16), F, M, F, F,
+                               d->cfg.ln_eps, s, 1, 1))) return rc;
+    return gemm_bf16(ffn2_16, F, d->tt.get_bf16(w.prefix + "feed_forward.w_2.weight", s), F, nullptr, out, D, M, D, F, 0, nullptr, 0, 0, s);
+}
+
+// ---- THE block step of the offline forwards. What a forward tells it about the token rows in flight:
+struct DecRows {
+    int mode;           // arithmetic of the FFN: 0 fp32, 1 bf16 operands, 2 bf16x3 (w_1 on three planes), 3 f16x2
+    int M;              // rows per token-side op: B * N, or the valid rows when they are packed
+    int B, N;           // sequences and padded tokens per sequence (the FSMN runs per sequence, along tokens)
+    const int* offs;    // packed rows: device offsets per sequence (FsmnArgs.offs); nullptr: the padded layout
+    int left_pad;       // FSMN taps left of the centre: (K - 1) / 2 + sanm_shfit in the attention blocks, (K - 1) / 2 in decoders2
+    hipStream_t s;
+};
+// out = FFN(norm1(x)) in the forward's arithmetic (decoders3 is this alone)
+static int dec_ffn_rows(Decoder* d, const DecLayerW& w, const float* x, float* out, const DecRows& r) {
+    if (r.mode == 3) return dec_ffn_x2(d, w, x, out, r.M, r.s);
+    if (r.mode == 1) return dec_ffn_bf16(d, w, x, out, r.M, r.s);
+    const unsigned short* w1_3 = nullptr;
+    if (r.mode == 2 && !(w1_3 = d->tt.get_split3(w.prefix + "feed_forward.w_1.weight", d->cfg.ffn_dim, d->cfg.d_model, r.s))) return -2;
+    return dec_ffn(d, w, x, out, r.M, r.s, w1_3);
+}
+// DecoderLayerSANM.forward up to its cross-attention (paraformer/decoder.py:78-107), all of it for a decoders2 block:
+// tgt = FFN(norm1(x)) -> norm2 -> x = x + fsmn(tgt), in place on x (d->t2 and d->t1 hold the two intermediates)
+static int dec_block_step(Decoder* d, const DecLayerW& w, float* x, const DecRows& r) {
+    const int D = d->cfg.d_model;
+    float* t1 = d->t1.as<float>();
+    float* t2 = d->t2.as<float>();
+    int rc;
+    if ((rc = dec_ffn_rows(d, w, x, t2, r))) return rc;
+    if ((rc = layernorm(t2, D, w.n2g, w.n2b, t1, D, r.M, D, D, d->cfg.ln_eps, r.s))) return rc;
+    FsmnArgs fa{};
+    fa.in = t1; fa.ldin = D; fa.w = w.fsmn_w; fa.R = x; fa.ldr = D; fa.out = x; fa.ldo = D;
+    fa.lens = d->tok_lens.as<int>(); fa.B = r.B; fa.T = r.N; fa.C = D; fa.K = d->cfg.kernel_size; fa.left_pad = r.left_pad;
+    fa.offs = r.offs;
+    return fsmn(fa, r.s);
+}
 
 // bf16-operand decoder (throughput mode): every GEMM and the cross-attention take bf16 operands with fp32
 // accumulation; the token stream x, the FSMN and the LayerNorm statistics stay fp32. Expects x = embeds and the
 // length arrays already staged by pf_decoder_forward.
-int decoder_forward_bf16(Decoder* d, const float* memory, int B, int T, int N, int32_t* ids, float* hidden_out,
-                                hipStream_t s) {
+static int decoder_forward_bf16(Decoder* d, const float* memory, int B, int T, int N, int32_t* ids, float* hidden_out, hipStream_t s) {
     const pf_decoder_config& c = d->cfg;
     const int D = c.d_model, F = c.ffn_dim, V = c.vocab_size, Mq = B * N, Mk = B * T;
     typedef unsigned short u16;
@@ -232,44 +333,19 @@ int decoder_forward_bf16(Decoder* d, const float* memory, int B, int T, int N, i
         d->kv16.ensure(sizeof(u16) * (size_t)Mk * 2 * D) || d->ctx16.ensure(sizeof(u16) * (size_t)Mq * D) ||
         d->mem16.ensure(sizeof(u16) * (size_t)Mk * D) || d->hid16.ensure(sizeof(u16) * (size_t)Mq * D))
         return -2;
-    u16* t16 = d->t16.as<u16>(); u16* ffn16 = d->ffn16.as<u16>(); u16* ffn2_16 = d->ffn2_16.as<u16>();
-    u16* q16 = d->q16.as<u16>(); u16* kv16 = d->kv16.as<u16>(); u16* ctx16 = d->ctx16.as<u16>();
+    u16* t16 = d->t16.as<u16>(); u16* q16 = d->q16.as<u16>(); u16* kv16 = d->kv16.as<u16>(); u16* ctx16 = d->ctx16.as<u16>();
     u16* mem16 = d->mem16.as<u16>();
-    float* x = d->x.as<float>(); float* t1 = d->t1.as<float>(); float* t2 = d->t2.as<float>();
+    float* x = d->x.as<float>(); float* t2 = d->t2.as<float>();
     int rc;
     if ((rc = launch_cast_bf16(memory, mem16, (size_t)Mk * D, s))) return rc;
     auto w16 = [&](const std::string& name) { return d->tt.get_bf16(name, s); };
-    auto gemm16 = [&](const u16* A, int lda, const u16* W, int ldw, const float* bias, void* C, int ldc, int M, int Nn, int K,
-                      int relu, const float* R2, int ldr2, int c16) {
-        if (!W) return -2;
-        GemmArgs g{};
-        g.A = reinterpret_cast<const float*>(A); g.lda = lda; g.W = reinterpret_cast<const float*>(W); g.ldw = ldw;
-        g.bias = bias; g.R2 = R2; g.ldr2 = ldr2; g.C = reinterpret_cast<float*>(C); g.ldc = ldc;
-        g.M = M; g.N = Nn; g.K = K; g.relu = relu; g.ab_bf16 = 1; g.c_bf16 = c16;
-        ProfScope ps(PROF_GEMM, 2.0 * M * (double)Nn * K, s);
-        return launch_gemm_f32(g, s);
-    };
-    auto ffn_bf16 = [&](const std::string& p, const DecLayerW& w, const float* xin, float* out) {
-        int r;
-        if ((r = launch_layernorm(xin, D, w.n1g, w.n1b, reinterpret_cast<float*>(t16), D, Mq, D, D, c.ln_eps, s, 1, 0))) return r;
-        if ((r = gemm16(t16, D, w16(p + "feed_forward.w_1.weight"), D, w.b1, ffn16, F, Mq, F, D, 1, nullptr, 0, 1))) return r;
-        if ((r = launch_layernorm(reinterpret_cast<const float*>(ffn16), F, w.fng, w.fnb, reinterpret_cast<float*>(ffn2_16), F,
-                                  Mq, F, F, c.ln_eps, s, 1, 1))) return r;
-        return gemm16(ffn2_16, F, w16(p + "feed_forward.w_2.weight"), F, nullptr, out, D, Mq, D, F, 0, nullptr, 0, 0);
-    };
-    const int left_pad = (c.kernel_size - 1) / 2 + (c.sanm_shift > 0 ? c.sanm_shift : 0);
-    for (int l = 0; l < c.n_blocks; ++l) {
-        const DecLayerW& w = d->layers[l];
-        const std::string p = "decoders." + std::to_string(l) + ".";
-        if ((rc = ffn_bf16(p, w, x, t2))) return rc;
-        if ((rc = layernorm(t2, D, w.n2g, w.n2b, t1, D, Mq, D, D, c.ln_eps, s))) return rc;
-        FsmnArgs fa{};
-        fa.in = t1; fa.ldin = D; fa.w = w.fsmn_w; fa.R = x; fa.ldr = D; fa.out = x; fa.ldo = D;
-        fa.lens = d->tok_lens.as<int>(); fa.B = B; fa.T = N; fa.C = D; fa.K = c.kernel_size; fa.left_pad = left_pad;
-        if ((rc = fsmn(fa, s))) return rc;
+    DecRows rows{1, Mq, B, N, nullptr, (c.kernel_size - 1) / 2 + (c.sanm_shift > 0 ? c.sanm_shift : 0), s};
+    for (const DecLayerW& w : d->layers) {
+        const std::string& p = w.prefix;
+        if ((rc = dec_block_step(d, w, x, rows))) return rc;
         if ((rc = launch_layernorm(x, D, w.n3g, w.n3b, reinterpret_cast<float*>(t16), D, Mq, D, D, c.ln_eps, s, 1, 0))) return rc;
-        if ((rc = gemm16(t16, D, w16(p + "src_attn.linear_q.weight"), D, w.q_b, q16, D, Mq, D, D, 0, nullptr, 0, 1))) return rc;
-        if ((rc = gemm16(mem16, D, w16(p + "src_attn.linear_k_v.weight"), D, w.kv_b, kv16, 2 * D, Mk, 2 * D, D, 0, nullptr, 0, 1)))
+        if ((rc = gemm_bf16(t16, D, w16(p + "src_attn.linear_q.weight"), D, w.q_b, q16, D, Mq, D, D, 0, nullptr, 0, 1, s))) return rc;
+        if ((rc = gemm_bf16(mem16, D, w16(p + "src_attn.linear_k_v.weight"), D, w.kv_b, kv16, 2 * D, Mk, 2 * D, D, 0, nullptr, 0, 1, s)))
             return rc;
         AttnArgs aa{};
         aa.Q = reinterpret_cast<const float*>(q16); aa.ldq = D; aa.K = reinterpret_cast<const float*>(kv16); aa.ldk = 2 * D;
@@ -280,18 +356,11 @@ int decoder_forward_bf16(Decoder* d, const float* memory, int B, int T, int N, i
             ProfScope ps(PROF_ATTN, 4.0 * B * (double)N * T * D, s);
             if ((rc = launch_attention_bf16(aa, s))) return rc;
         }
-        if ((rc = gemm16(ctx16, D, w16(p + "src_attn.linear_out.weight"), D, w.o_b, x, D, Mq, D, D, 0, x, D, 0))) return rc;
+        if ((rc = gemm_bf16(ctx16, D, w16(p + "src_attn.linear_out.weight"), D, w.o_b, x, D, Mq, D, D, 0, x, D, 0, s))) return rc;
     }
-    for (int l = 0; l < d->n_blocks2; ++l) {                       // decoders2 (decoder.py:363-380): no cross-attention, taps centred
-        const DecLayerW& w = d->layers2[l];
-        if ((rc = ffn_bf16("decoders2." + std::to_string(l) + ".", w, x, t2))) return rc;
-        if ((rc = layernorm(t2, D, w.n2g, w.n2b, t1, D, Mq, D, D, c.ln_eps, s))) return rc;
-        FsmnArgs fa{};
-        fa.in = t1; fa.ldin = D; fa.w = w.fsmn_w; fa.R = x; fa.ldr = D; fa.out = x; fa.ldo = D;
-        fa.lens = d->tok_lens.as<int>(); fa.B = B; fa.T = N; fa.C = D; fa.K = c.kernel_size; fa.left_pad = (c.kernel_size - 1) / 2;
-        if ((rc = fsmn(fa, s))) return rc;
-    }
-    if ((rc = ffn_bf16("decoders3.0.", d->last, x, t2))) return rc;
+    rows.left_pad = (c.kernel_size - 1) / 2;                       // decoders2 (decoder.py:363-380): no cross-attention, taps centred
+    for (const DecLayerW& w : d->layers2) if ((rc = dec_block_step(d, w, x, rows))) return rc;
+    if ((rc = dec_ffn_rows(d, d->last, x, t2, rows))) return rc;
     u16* hid16 = d->hid16.as<u16>();
     if (hidden_out) {
         if ((rc = layernorm(t2, D, d->tt.get("after_norm.weight"), d->tt.get("after_norm.bias"), hidden_out, D, Mq, D, D,
@@ -302,317 +371,11 @@ int decoder_forward_bf16(Decoder* d, const float* memory, int B, int T, int N, i
                                reinterpret_cast<float*>(hid16), D, Mq, D, D, c.ln_eps, s, 1, 0))) return rc;
     const u16* ow = w16("output_layer.weight");
     if (!ow) return -2;
-    const int nparts = 2 * ceil_div(V, 128);
-    if (d->pval.ensure(sizeof(float) * (size_t)Mq * nparts) || d->pidx.ensure(sizeof(int) * (size_t)Mq * nparts)) return -2;
-    GemmArgs g{};
-    g.A = reinterpret_cast<const float*>(hid16); g.lda = D; g.W = reinterpret_cast<const float*>(ow); g.ldw = D;
-    g.bias = d->tt.get("output_layer.bias"); g.M = Mq; g.N = V; g.K = D; g.ab_bf16 = 1;
-    g.amax_val = d->pval.as<float>(); g.amax_idx = d->pidx.as<int>(); g.amax_ld = nparts;
-    {
-        ProfScope ps(PROF_GEMM, 2.0 * Mq * (double)V * D, s);
-        if ((rc = launch_gemm_f32(g, s))) return rc;
-    }
-    return launch_argmax_reduce(d->pval.as<float>(), d->pidx.as<int>(), nparts, nparts, ids, nullptr, Mq, s);
+    if (argmax_scratch(d->pval, d->pidx, Mq, argmax_f32_parts(V))) return -2;
+    return argmax_f32(reinterpret_cast<const float*>(hid16), D, reinterpret_cast<const float*>(ow), D, d->tt.get("output_layer.bias"),
+                      Mq, V, D, 1, d->pval.as<float>(), d->pidx.as<int>(), ids, s);
 }
 
-}  // namespace pf
-
-using namespace pf;
-
-extern "C" {
-
-// ------------------------------------------------------------------------------------------------- predictor
-pf_predictor* pf_predictor_create(const pf_predictor_config* cfg) {
-    if (!cfg) { set_error("predictor: null config"); return nullptr; }
-    if (check_device()) return nullptr;
-    const pf_predictor_config& c = *cfg;
-    if (c.d_model <= 0 || c.d_model % 32 || c.l_order < 0 || c.r_order < 0 || c.threshold != 1.0f) {
-        set_error("predictor: unsupported config (d_model % 32 == 0; threshold must be 1.0: cif_wo_hidden_v1 "
-                  "detects fires with floor(), cif_predictor.py:838-846)");
-        return nullptr;
-    }
-    std::unique_ptr<Predictor> p(new Predictor());
-    p->cfg = c;
-    const int D = c.d_model, taps = c.l_order + c.r_order + 1;
-    int rc = 0;
-    rc |= p->tt.add_conv("cif_conv1d.weight", D, D, taps);
-    rc |= p->tt.add("cif_conv1d.bias", D);
-    rc |= p->tt.add("cif_output.weight", D);
-    rc |= p->tt.add("cif_output.bias", 1);
-    if (rc) return nullptr;
-    return reinterpret_cast<pf_predictor*>(p.release());
-}
-pf_predictor* pf_predictor_create_v3(const pf_predictor_config* cfg, const pf_predictor_v3_config* cfg3) {
-    if (!cfg3) { set_error("predictor_v3: null config"); return nullptr; }
-    const pf_predictor_v3_config& c3 = *cfg3;
-    if (c3.upsample_times < 1 || c3.upsample_times > 8 || (c3.upsample_type != 0 && c3.upsample_type != 1)) {
-        set_error("predictor_v3: unsupported config (upsample_times 1..8; upsample_type 0 = cnn, 1 = cnn_blstm)");
-        return nullptr;
-    }
-    if (cfg && !cfg->tail_mask && cfg->tail_threshold > 0.f) {
-        set_error("predictor_v3: the reference always applies the tail threshold through the mask (tail_mask = 1)");
-        return nullptr;
-    }
-    pf_predictor* ph = pf_predictor_create(cfg);
-    if (!ph) return nullptr;
-    Predictor* p = reinterpret_cast<Predictor*>(ph);
-    p->v3 = true;
-    p->c3 = c3;
-    const int D = p->cfg.d_model, U = c3.upsample_times;
-    int rc = 0;
-    rc |= p->tt.add_upsample("upsample_cnn.weight", D, D, U);
-    rc |= p->tt.add_tiled("upsample_cnn.bias", D, U);
-    if (c3.upsample_type == 1) {
-        for (const char* sfx : {"", "_reverse"}) {
-            const std::string s(sfx);
-            rc |= p->tt.add("blstm.weight_ih_l0" + s, (int64_t)4 * D * D);
-            rc |= p->tt.add_lstm_hh("blstm.weight_hh_l0" + s, D);
-            rc |= p->tt.add("blstm.bias_ih_l0" + s, (int64_t)4 * D);
-            rc |= p->tt.add("blstm.bias_hh_l0" + s, (int64_t)4 * D);
-        }
-        rc |= p->tt.add("cif_output2.weight", 2 * D);
-    } else {
-        rc |= p->tt.add("cif_output2.weight", D);
-    }
-    rc |= p->tt.add("cif_output2.bias", 1);
-    if (rc) { pf_predictor_destroy(ph); return nullptr; }
-    return ph;
-}
-void pf_predictor_destroy(pf_predictor* p) { delete reinterpret_cast<Predictor*>(p); }
-int pf_predictor_set_tensor(pf_predictor* ph, const char* name, const float* data, int64_t numel) {
-    Predictor* p = reinterpret_cast<Predictor*>(ph);
-    PF_REQUIRE(p && name && data, "predictor_set_tensor: null");
-    return p->tt.set(name, data, numel);
-}
-int pf_predictor_missing(const pf_predictor* ph) {
-    const Predictor* p = reinterpret_cast<const Predictor*>(ph);
-    return p ? p->tt.missing() : -1;
-}
-
-}  // extern "C"
-
-// relu(Conv1d(D, D, l + r + 1)(pad(hidden))) (cif_predictor.py:275-278) as ONE exact-fp32 GEMM whose A operand is gathered from the
-// row-shifted views of `hidden` by the DMA sources (gemm_f32.hip, GemmArgs.conv_*): the k order per output element is that of the
-// im2col GEMM of rounds 1-5, so alphas are bitwise unchanged, and the [M, taps D] column matrix (197 MB written + 196 MB read per
-// headline step) is gone
-static int predictor_conv(Predictor* p, const float* hidden, int B, int T, hipStream_t s) {
-    const pf_predictor_config& c = p->cfg;
-    const int D = c.d_model, taps = c.l_order + c.r_order + 1;
-    const size_t M = (size_t)B * T;
-    if (p->conv.ensure(sizeof(float) * M * D)) return -2;
-    if (!p->zero_row.p) {
-        if (p->zero_row.ensure(256)) return -2;
-        PF_HIP_TRY(hipMemsetAsync(p->zero_row.p, 0, 256, s));
-    }
-    GemmArgs g{};
-    g.A = hidden; g.lda = D; g.W = p->tt.get("cif_conv1d.weight"); g.ldw = taps * D; g.bias = p->tt.get("cif_conv1d.bias");
-    g.C = p->conv.as<float>(); g.ldc = D; g.M = (int)M; g.N = D; g.K = taps * D; g.relu = 1;
-    g.conv_taps = taps; g.conv_D = D; g.conv_T = T; g.conv_left = c.l_order; g.conv_zero = p->zero_row.as<float>();
-    ProfScope ps(PROF_GEMM, 2.0 * (double)M * D * (double)(taps * D), s);
-    return launch_gemm_f32(g, s);
-}
-
-namespace pf {
-// everything of pf_predictor_alphas up to the scan, ENQUEUED into scan-state slot `slot`; the token counts stay on the device
-// (predictor_counts_dev)
-int predictor_alphas_enqueue(Predictor* p, int slot, const float* hidden, const int32_t* lens_host, int B, int T, hipStream_t s) {
-    PF_REQUIRE(p && hidden && lens_host && B > 0 && T > 0 && (slot == 0 || slot == 1), "predictor_alphas: null/empty argument");
-    for (int b = 0; b < B; ++b) PF_REQUIRE(lens_host[b] >= 1 && lens_host[b] <= T, "predictor_alphas: lens out of range");
-    if (p->tt.require_all("predictor")) return -3;
-    const pf_predictor_config& c = p->cfg;
-    const int D = c.d_model, Te = T + 1;
-    Predictor::CifState& S = p->st[slot];
-    if (S.alphas.ensure(sizeof(float) * (size_t)B * Te) || S.peaks.ensure(sizeof(float) * (size_t)B * Te) ||
-        S.rems.ensure(sizeof(float) * (size_t)B * Te) || S.flags.ensure(sizeof(int) * (size_t)B * Te) ||
-        S.nfires.ensure(sizeof(int) * (size_t)B))
-        return -2;
-    int rc;
-    if ((rc = upload_lens(S.lens, lens_host, B, s))) return rc;
-    if ((rc = predictor_conv(p, hidden, B, T, s))) return rc;
-    AlphaArgs aa{};
-    aa.conv = p->conv.as<float>(); aa.w = p->tt.get("cif_output.weight"); aa.bias = p->tt.get("cif_output.bias");
-    aa.lens = S.lens.as<int>(); aa.alphas = S.alphas.as<float>(); aa.B = B; aa.T = T; aa.D = D; aa.T_ext = Te;
-    aa.smooth = c.smooth_factor; aa.noise = c.noise_threshold;
-    if ((rc = launch_alpha(aa, s))) return rc;
-    CifScanArgs sa{};
-    sa.alphas = S.alphas.as<float>(); sa.peaks = S.peaks.as<float>(); sa.rems = S.rems.as<float>();
-    sa.fire_flag = S.flags.as<int>(); sa.n_fires = S.nfires.as<int>(); sa.lens = S.lens.as<int>(); sa.B = B;
-    sa.T = T; sa.tail_threshold = c.tail_threshold; sa.tail_mask = c.tail_mask;
-    if (p->v3) {
-        if (S.curs.ensure(sizeof(float) * (size_t)B * Te) || S.ntok.ensure(sizeof(int) * (size_t)B)) return -2;
-        if ((rc = launch_cif_scan_loop(sa, S.curs.as<float>(), S.ntok.as<int>(), s))) return rc;
-    } else if ((rc = launch_cif_scan(sa, s))) {
-        return rc;
-    }
-    S.B = B; S.T = T;
-    return 0;
-}
-// V3 reports floor(sum alphas) (cif_predictor.py:383), V2's count of fires is the same number by construction
-const int32_t* predictor_counts_dev(Predictor* p, int slot) {
-    return reinterpret_cast<const int32_t*>(p->v3 ? p->st[slot].ntok.p : p->st[slot].nfires.p);
-}
-const float* predictor_alphas_dev(Predictor* p, int slot) { return p->st[slot].alphas.as<float>(); }
-const float* predictor_peaks_dev(Predictor* p, int slot) { return p->st[slot].peaks.as<float>(); }
-int predictor_embeds_slot(Predictor* p, int slot, const float* hidden, int B, int T, int N, float* embeds, hipStream_t s) {
-    PF_REQUIRE(p && hidden && embeds && N >= 0 && (slot == 0 || slot == 1), "predictor_embeds: null argument");
-    Predictor::CifState& S = p->st[slot];
-    PF_REQUIRE(B == S.B && T == S.T, "predictor_embeds: call pf_predictor_alphas with the same batch first");
-    CifEmitArgs ea{};
-    ea.hidden = hidden; ea.alphas = S.alphas.as<float>(); ea.rems = S.rems.as<float>();
-    ea.fire_flag = S.flags.as<int>(); ea.embeds = embeds; ea.B = B; ea.T = T; ea.D = p->cfg.d_model; ea.N = N;
-    if (p->v3) {
-        if (N <= 0) return 0;
-        ea.alphas = S.curs.as<float>();
-        return launch_cif_emit_loop(ea, s);
-    }
-    return launch_cif_emit(ea, s);
-}
-}  // namespace pf
-
-extern "C" {
-
-int pf_predictor_alphas(pf_predictor* ph, const float* hidden, const int32_t* lens_host, int32_t B, int32_t T,
-                        float* alphas, float* peaks, int32_t* token_num, void* stream) {
-    Predictor* p = reinterpret_cast<Predictor*>(ph);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    PF_REQUIRE(p && token_num, "predictor_alphas: null/empty argument");
-    int rc;
-    if ((rc = predictor_alphas_enqueue(p, 0, hidden, lens_host, B, T, s))) return rc;
-    const size_t Te = (size_t)T + 1;
-    if (alphas) PF_HIP_TRY(hipMemcpyAsync(alphas, p->st[0].alphas.p, sizeof(float) * (size_t)B * Te, hipMemcpyDeviceToDevice, s));
-    if (peaks) PF_HIP_TRY(hipMemcpyAsync(peaks, p->st[0].peaks.p, sizeof(float) * (size_t)B * Te, hipMemcpyDeviceToDevice, s));
-    PF_HIP_TRY(hipMemcpyAsync(token_num, predictor_counts_dev(p, 0), sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, s));
-    PF_HIP_TRY(hipStreamSynchronize(s));
-    return 0;
-}
-
-int pf_predictor_embeds(pf_predictor* ph, const float* hidden, int32_t B, int32_t T, int32_t N, float* embeds,
-                        void* stream) {
-    return predictor_embeds_slot(reinterpret_cast<Predictor*>(ph), 0, hidden, B, T, N, embeds, reinterpret_cast<hipStream_t>(stream));
-}
-
-// The two steps without the synchronisation between them, for callers that keep two batches in flight (include/paraformer_hip.h)
-int pf_predictor_alphas_begin(pf_predictor* ph, int32_t slot, const float* hidden, const int32_t* lens_host, int32_t B, int32_t T,
-                              float* alphas, float* peaks, int32_t* counts_pinned_host, void* stream) {
-    Predictor* p = reinterpret_cast<Predictor*>(ph);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    PF_REQUIRE(p && counts_pinned_host && (slot == 0 || slot == 1), "predictor_alphas_begin: null argument or slot not 0 / 1");
-    int rc;
-    if ((rc = predictor_alphas_enqueue(p, slot, hidden, lens_host, B, T, s))) return rc;
-    const size_t Te = (size_t)T + 1;
-    if (alphas) PF_HIP_TRY(hipMemcpyAsync(alphas, p->st[slot].alphas.p, sizeof(float) * (size_t)B * Te, hipMemcpyDeviceToDevice, s));
-    if (peaks) PF_HIP_TRY(hipMemcpyAsync(peaks, p->st[slot].peaks.p, sizeof(float) * (size_t)B * Te, hipMemcpyDeviceToDevice, s));
-    PF_HIP_TRY(hipMemcpyAsync(counts_pinned_host, predictor_counts_dev(p, slot), sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, s));
-    return 0;
-}
-
-int pf_predictor_embeds_slot(pf_predictor* ph, int32_t slot, const float* hidden, int32_t B, int32_t T, int32_t N, float* embeds,
-                             void* stream) {
-    return predictor_embeds_slot(reinterpret_cast<Predictor*>(ph), slot, hidden, B, T, N, embeds, reinterpret_cast<hipStream_t>(stream));
-}
-
-// one direction-pair of torch.nn.LSTM on a time-major input: gates-major input projections by the fp32 MFMA GEMM
-// (W_ih . X_tm^T, one GEMM per direction), then the per-step recurrence (lstm.hip)
-}  // extern "C"
-namespace pf {
-int lstm_forward(const LstmW& w, const float* x_tm, int T, int B, int D, int H, int ndir, float* out, int out_layout,
-                        DevBuf& pre, DevBuf& h_a, DevBuf& h_b, DevBuf& cell, hipStream_t s) {
-    const size_t cols = (size_t)T * B, ldp = (cols + 3) / 4 * 4;
-    const int Bs = (B + 63) / 64 * 64;
-    const size_t state = sizeof(float) * (size_t)ndir * H * Bs;
-    if (pre.ensure(sizeof(float) * (size_t)ndir * 4 * H * ldp) || h_a.ensure(state) || h_b.ensure(state) || cell.ensure(state))
-        return -2;
-    int rc;
-    for (int d = 0; d < ndir; ++d)
-        if ((rc = gemm_simple(w.w_ih[d], D, x_tm, D, nullptr, pre.as<float>() + (size_t)d * 4 * H * ldp, (int)ldp, 4 * H,
-                              (int)cols, D, 0, nullptr, 0, nullptr, 0, s))) return rc;
-    LstmStepArgs a{};
-    a.pre = pre.as<float>(); a.whh = w.w_hh; a.b_ih = w.b_ih; a.b_hh = w.b_hh; a.h_a = h_a.as<float>();
-    a.h_b = h_b.as<float>(); a.c = cell.as<float>(); a.out = out; a.ld_pre = ldp; a.T = T; a.B = B; a.Bs = Bs; a.H = H;
-    a.ndir = ndir; a.out_layout = out_layout;
-    return launch_lstm_steps(a, s);
-}
-}  // namespace pf
-extern "C" {
-
-
-int pf_predictor_timestamp(pf_predictor* ph, const float* hidden, const int32_t* lens_host, const int32_t* token_num_host,
-                           int32_t B, int32_t T, float* us_alphas, float* us_peaks, void* stream) {
-    Predictor* p = reinterpret_cast<Predictor*>(ph);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    PF_REQUIRE(p && hidden && lens_host && token_num_host && us_alphas && us_peaks && B > 0 && T > 0,
-               "predictor_timestamp: null/empty argument");
-    PF_REQUIRE(p->v3, "predictor_timestamp: the handle was not made by pf_predictor_create_v3");
-    for (int b = 0; b < B; ++b) PF_REQUIRE(lens_host[b] >= 1 && lens_host[b] <= T, "predictor_timestamp: lens out of range");
-    if (p->tt.require_all("predictor")) return -3;
-    const pf_predictor_config& c = p->cfg;
-    const int D = c.d_model, U = p->c3.upsample_times, taps = c.l_order + c.r_order + 1, Tu = T * U;
-    const size_t M = (size_t)B * T;
-    int rc;
-    if ((rc = upload_lens(p->ts_lens, lens_host, B, s))) return rc;        // (its own buffer: both scan-state slots may be in flight)
-    if (p->tok_dev.ensure(sizeof(int) * (size_t)B)) return -2;
-    if (upload_h2d(p->tok_dev.p, token_num_host, sizeof(int32_t) * (size_t)B, s)) return -2;
-    const float* src = hidden;
-    if (p->c3.use_cif1_cnn) {                                   // the head sees relu(cif_conv1d(hidden)) instead (:317-320)
-        if ((rc = predictor_conv(p, hidden, B, T, s))) return rc;
-        src = p->conv.as<float>();
-    }
-    // ConvTranspose1d(k = stride = U) == one GEMM: row (b, t) of the output holds frames U t .. U t + U - 1
-    if (p->up.ensure(sizeof(float) * M * U * D)) return -2;
-    if ((rc = gemm_simple(src, D, p->tt.get("upsample_cnn.weight"), D, p->tt.get("upsample_cnn.bias"), p->up.as<float>(),
-                          U * D, (int)M, U * D, D, 0, nullptr, 0, nullptr, 0, s))) return rc;
-    if (p->c3.upsample_type == 1) {
-        const int Bs = (B + 63) / 64 * 64;
-        if (p->x_tm.ensure(sizeof(float) * (size_t)Tu * B * D) || p->lstm_out.ensure(sizeof(float) * (size_t)Tu * 2 * D * Bs))
-            return -2;
-        if ((rc = launch_rows_bt_to_tb(p->up.as<float>(), p->x_tm.as<float>(), B, Tu, D, s))) return rc;
-        // the two directions' recurrent weights / biases live back to back so that one launch serves both
-        LstmW w{};
-        w.w_ih[0] = p->tt.get("blstm.weight_ih_l0"); w.w_ih[1] = p->tt.get("blstm.weight_ih_l0_reverse");
-        const size_t hh = (size_t)4 * D * D, bb = (size_t)4 * D;
-        if (p->pack.ensure(sizeof(float) * (2 * hh + 4 * bb))) return -2;
-        float* pack = p->pack.as<float>();
-        float* bi = pack + 2 * hh;
-        float* bh = bi + 2 * bb;
-        if (p->packed_for != p->tt.version) {
-            PF_HIP_TRY(hipMemcpyAsync(pack, p->tt.get("blstm.weight_hh_l0"), sizeof(float) * hh, hipMemcpyDeviceToDevice, s));
-            PF_HIP_TRY(hipMemcpyAsync(pack + hh, p->tt.get("blstm.weight_hh_l0_reverse"), sizeof(float) * hh, hipMemcpyDeviceToDevice, s));
-            PF_HIP_TRY(hipMemcpyAsync(bi, p->tt.get("blstm.bias_ih_l0"), sizeof(float) * bb, hipMemcpyDeviceToDevice, s));
-            PF_HIP_TRY(hipMemcpyAsync(bi + bb, p->tt.get("blstm.bias_ih_l0_reverse"), sizeof(float) * bb, hipMemcpyDeviceToDevice, s));
-            PF_HIP_TRY(hipMemcpyAsync(bh, p->tt.get("blstm.bias_hh_l0"), sizeof(float) * bb, hipMemcpyDeviceToDevice, s));
-            PF_HIP_TRY(hipMemcpyAsync(bh + bb, p->tt.get("blstm.bias_hh_l0_reverse"), sizeof(float) * bb, hipMemcpyDeviceToDevice, s));
-            p->packed_for = p->tt.version;
-        }
-        w.w_hh = pack; w.b_ih = bi; w.b_hh = bh;
-        if ((rc = lstm_forward(w, p->x_tm.as<float>(), Tu, B, D, D, 2, p->lstm_out.as<float>(), 1, p->pre, p->h_a, p->h_b,
-                               p->cell, s))) return rc;
-        UsAlphaArgs ua{};
-        ua.out_t = p->lstm_out.as<float>(); ua.w = p->tt.get("cif_output2.weight"); ua.bias = p->tt.get("cif_output2.bias");
-        ua.lens = p->ts_lens.as<int>(); ua.alphas = us_alphas; ua.B = B; ua.Bs = Bs; ua.T = Tu; ua.C = 2 * D; ua.U = U;
-        ua.smooth = p->c3.smooth_factor2; ua.noise = p->c3.noise_threshold2;
-        if ((rc = launch_us_alpha_t(ua, s))) return rc;
-    } else {
-        // plain `cnn` head: the row-major upsampled frames go straight through the one-wave-per-row dot kernel
-        p->ul_host.resize(B);
-        for (int b = 0; b < B; ++b) p->ul_host[b] = lens_host[b] * U;
-        DevBuf& ulens = p->ulens;
-        if ((rc = upload_lens(ulens, p->ul_host.data(), B, s))) return rc;
-        AlphaArgs aa{};
-        aa.conv = p->up.as<float>(); aa.w = p->tt.get("cif_output2.weight"); aa.bias = p->tt.get("cif_output2.bias");
-        aa.lens = ulens.as<int>(); aa.alphas = us_alphas; aa.B = B; aa.T = Tu; aa.D = D; aa.T_ext = Tu;
-        aa.smooth = p->c3.smooth_factor2; aa.noise = p->c3.noise_threshold2;
-        if ((rc = launch_alpha(aa, s))) return rc;
-    }
-    return launch_us_scale_scan(us_alphas, us_peaks, p->tok_dev.as<int>(), B, Tu, (float)((double)c.threshold - 1e-4), s);
-}
-
-// --------------------------------------------------------------------------------------------------- decoder
-static pf_decoder* decoder_create_impl(const pf_decoder_config* cfg, bool contextual);
-pf_decoder* pf_decoder_create(const pf_decoder_config* cfg) { return decoder_create_impl(cfg, false); }
-/* ContextualParaformerDecoder (funasr/models/contextual_paraformer/decoder.py:133-352): n_blocks - 1 standard blocks
- * ("decoders.{i}."), the last block under "last_decoder.", plus the hotword branch "bias_decoder.norm3.*",
- * "bias_decoder.src_attn.linear_{q,k_v,out}.*" and the 1x1 fusion "bias_output.weight" [D, 2D, 1] */
-pf_decoder* pf_decoder_create_contextual(const pf_decoder_config* cfg) { return decoder_create_impl(cfg, true); }
 static pf_decoder* decoder_create_impl(const pf_decoder_config* cfg, bool contextual) {
     if (!cfg) { set_error("decoder: null config"); return nullptr; }
     if (check_device()) return nullptr;
@@ -629,32 +392,9 @@ static pf_decoder* decoder_create_impl(const pf_decoder_config* cfg, bool contex
     d->cfg = c;
     d->precision = (c.n_heads > 0 && c.d_model / c.n_heads == 128 && c.d_model % 256 == 0 && c.ffn_dim % 256 == 0) ? 3 : 0;
     d->contextual = contextual;
-    const int D = c.d_model, F = c.ffn_dim;
+    const int D = c.d_model;
     int rc = 0;
-    auto add_ffn = [&](const std::string& p) {
-        rc |= d->tt.add(p + "norm1.weight", D);
-        rc |= d->tt.add(p + "norm1.bias", D);
-        rc |= d->tt.add(p + "feed_forward.w_1.weight", (int64_t)F * D);
-        rc |= d->tt.add(p + "feed_forward.w_1.bias", F);
-        rc |= d->tt.add(p + "feed_forward.norm.weight", F);
-        rc |= d->tt.add(p + "feed_forward.norm.bias", F);
-        rc |= d->tt.add(p + "feed_forward.w_2.weight", (int64_t)D * F);
-    };
-    for (int i = 0; i < c.n_blocks; ++i) {
-        const std::string p = dec_layer_prefix(contextual, c.n_blocks, i);
-        add_ffn(p);
-        rc |= d->tt.add(p + "norm2.weight", D);
-        rc |= d->tt.add(p + "norm2.bias", D);
-        rc |= d->tt.add(p + "self_attn.fsmn_block.weight", (int64_t)D * c.kernel_size);
-        rc |= d->tt.add(p + "norm3.weight", D);
-        rc |= d->tt.add(p + "norm3.bias", D);
-        rc |= d->tt.add(p + "src_attn.linear_q.weight", (int64_t)D * D);
-        rc |= d->tt.add(p + "src_attn.linear_q.bias", D);
-        rc |= d->tt.add(p + "src_attn.linear_k_v.weight", (int64_t)2 * D * D);
-        rc |= d->tt.add(p + "src_attn.linear_k_v.bias", 2 * D);
-        rc |= d->tt.add(p + "src_attn.linear_out.weight", (int64_t)D * D);
-        rc |= d->tt.add(p + "src_attn.linear_out.bias", D);
-    }
+    for (int i = 0; i < c.n_blocks; ++i) rc |= dec_layer_add(d->tt, c, dec_layer_prefix(contextual, c.n_blocks, i), DEC_FFN_FSMN_ATTN);
     if (contextual) {
         rc |= d->tt.add("bias_decoder.norm3.weight", D);
         rc |= d->tt.add("bias_decoder.norm3.bias", D);
@@ -666,7 +406,7 @@ static pf_decoder* decoder_create_impl(const pf_decoder_config* cfg, bool contex
         rc |= d->tt.add("bias_decoder.src_attn.linear_out.bias", D);
         rc |= d->tt.add("bias_output.weight", (int64_t)D * 2 * D);
     }
-    add_ffn("decoders3.0.");
+    rc |= dec_layer_add(d->tt, c, "decoders3.0.", DEC_FFN);
     rc |= d->tt.add("after_norm.weight", D);
     rc |= d->tt.add("after_norm.bias", D);
     if (c.vocab_size > 0) {          // SeACo's bias decoder has no output layer (use_output_layer: false)
@@ -676,93 +416,12 @@ static pf_decoder* decoder_create_impl(const pf_decoder_config* cfg, bool contex
     if (rc) return nullptr;
     return reinterpret_cast<pf_decoder*>(d.release());
 }
-void pf_decoder_destroy(pf_decoder* d) { delete reinterpret_cast<Decoder*>(d); }
-/* decoders2 (paraformer/decoder.py:363-380, :436-437): n_layers = num_blocks - att_layer_num blocks of FFN + FSMN memory (built with
- * sanm_shfit 0: the taps centred) and NO cross-attention, run between `decoders` and `decoders3`. Tensors "decoders2.<i>.norm1|norm2.*",
- * "decoders2.<i>.feed_forward.*", "decoders2.<i>.self_attn.fsmn_block.weight". Call once, before the first set_tensor. */
-int pf_decoder_set_decoders2(pf_decoder* dh, int32_t n_layers) {
-    Decoder* d = reinterpret_cast<Decoder*>(dh);
-    PF_REQUIRE(d && n_layers >= 0 && n_layers <= 64, "decoder_set_decoders2: null handle or layer count out of range");
-    PF_REQUIRE(d->n_blocks2 == 0 || d->n_blocks2 == n_layers, "decoder_set_decoders2: already set");
-    if (d->n_blocks2 == n_layers) return 0;
-    const int D = d->cfg.d_model, F = d->cfg.ffn_dim;
-    int rc = 0;
-    for (int i = 0; i < n_layers; ++i) {
-        const std::string p = "decoders2." + std::to_string(i) + ".";
-        rc |= d->tt.add(p + "norm1.weight", D);
-        rc |= d->tt.add(p + "norm1.bias", D);
-        rc |= d->tt.add(p + "feed_forward.w_1.weight", (int64_t)F * D);
-        rc |= d->tt.add(p + "feed_forward.w_1.bias", F);
-        rc |= d->tt.add(p + "feed_forward.norm.weight", F);
-        rc |= d->tt.add(p + "feed_forward.norm.bias", F);
-        rc |= d->tt.add(p + "feed_forward.w_2.weight", (int64_t)D * F);
-        rc |= d->tt.add(p + "norm2.weight", D);
-        rc |= d->tt.add(p + "norm2.bias", D);
-        rc |= d->tt.add(p + "self_attn.fsmn_block.weight", (int64_t)D * d->cfg.kernel_size);
-    }
-    if (rc) return -2;
-    d->n_blocks2 = n_layers;
-    ++d->tt.version;         // the table's structure changed: what was resolved and prepared before is stale
-    return 0;
-}
-int pf_decoder_set_tensor(pf_decoder* dh, const char* name, const float* data, int64_t numel) {
-    Decoder* d = reinterpret_cast<Decoder*>(dh);
-    PF_REQUIRE(d && name && data, "decoder_set_tensor: null");
-    return d->tt.set(name, data, numel);
-}
-/* same modes as pf_encoder_set_precision; the bf16 mode serves the fused arg-max route (logits_dev == NULL) */
-int pf_decoder_set_precision(pf_decoder* dh, int32_t mode) {
-    Decoder* d = reinterpret_cast<Decoder*>(dh);
-    PF_REQUIRE(d && mode >= 0 && mode <= 3, "decoder_set_precision: mode must be 0 (fp32 MFMA), 1 (bf16 operands), 2 (fp32 via bf16x3) or 3 (fp32 via f16x2)");
-    PF_REQUIRE(mode == 0 || d->cfg.d_model / d->cfg.n_heads == 128, "decoder_set_precision: heads of d_k <= 64 exist in the fp32 mode only (attention_small.hip)");
-    d->precision = mode;
-    return 0;
-}
-int pf_decoder_missing(const pf_decoder* dh) {
-    const Decoder* d = reinterpret_cast<const Decoder*>(dh);
-    return d ? d->tt.missing() : -1;
-}
 
 // asf_layer >= 0: run blocks 0 .. asf_layer - 1, then block asf_layer up to its cross-attention SCORES and return the
 // attention-score filter of sequence 0 in asf_scores [T] (decoder.py:485-513 forward_asf6 / :696-714 get_attn_mat)
 static int decoder_forward_impl(Decoder* d, const float* memory, const int32_t* mem_lens, const float* embeds,
                                 const int32_t* tok_lens, int32_t B, int32_t T, int32_t N, float* logits, int32_t* ids,
-                                float* hidden_out, hipStream_t s, int asf_layer, float* asf_scores, const DecCtxArgs* cx = nullptr);
-
-int pf_decoder_forward(pf_decoder* dh, const float* memory, const int32_t* mem_lens, const float* embeds,
-                       const int32_t* tok_lens, int32_t B, int32_t T, int32_t N, float* logits, int32_t* ids,
-                       float* hidden_out, void* stream) {
-    return decoder_forward_impl(reinterpret_cast<Decoder*>(dh), memory, mem_lens, embeds, tok_lens, B, T, N, logits, ids,
-                                hidden_out, reinterpret_cast<hipStream_t>(stream), -1, nullptr);
-}
-/* SeACo attention-score filter (seaco_paraformer/model.py:323-335): the bias decoder's blocks 0 .. n_blocks_before - 1 in
- * full, then block n_blocks_before up to its cross-attention probabilities over the T memory rows (= hotword embeddings);
- * scores_dev [T] receives their sum over heads and token positions for sequence 0 (attn[0].sum(0).sum(0)). fp32 kernels. */
-int pf_decoder_asf_scores(pf_decoder* dh, const float* memory, const int32_t* mem_lens, const float* embeds,
-                          const int32_t* tok_lens, int32_t B, int32_t T, int32_t N, int32_t n_blocks_before,
-                          float* scores_dev, void* stream) {
-    Decoder* d = reinterpret_cast<Decoder*>(dh);
-    PF_REQUIRE(d && scores_dev && n_blocks_before >= 0 && n_blocks_before < d->cfg.n_blocks, "decoder_asf_scores: bad block index");
-    return decoder_forward_impl(d, memory, mem_lens, embeds, tok_lens, B, T, N, nullptr, nullptr, nullptr,
-                                reinterpret_cast<hipStream_t>(stream), n_blocks_before, scores_dev);
-}
-
-/* ContextualParaformerDecoder.forward (contextual_paraformer/decoder.py:293-352): the last attention block's FSMN-side state
- * x_self_attn also queries the hotword embeddings `contextual_dev` [B, n_hot, D] through bias_decoder; its output (times
- * clas_scale) and the block's own cross-attention output are fused by the 1x1 bias_output: x = x_self_attn + W [x_src | cx]. */
-int pf_decoder_forward_contextual(pf_decoder* dh, const float* memory, const int32_t* mem_lens, const float* embeds,
-                                  const int32_t* tok_lens, const float* contextual_dev, int32_t n_hot, float clas_scale,
-                                  int32_t B, int32_t T, int32_t N, float* logits, int32_t* ids, float* hidden_out, void* stream) {
-    Decoder* d = reinterpret_cast<Decoder*>(dh);
-    PF_REQUIRE(d && d->contextual && contextual_dev && n_hot >= 1, "decoder_forward_contextual: needs a contextual decoder and >= 1 hotword row");
-    DecCtxArgs cx{contextual_dev, n_hot, clas_scale};
-    return decoder_forward_impl(d, memory, mem_lens, embeds, tok_lens, B, T, N, logits, ids, hidden_out,
-                                reinterpret_cast<hipStream_t>(stream), -1, nullptr, &cx);
-}
-
-static int decoder_forward_impl(Decoder* d, const float* memory, const int32_t* mem_lens, const float* embeds,
-                                const int32_t* tok_lens, int32_t B, int32_t T, int32_t N, float* logits, int32_t* ids,
-                                float* hidden_out, hipStream_t s, int asf_layer, float* asf_scores, const DecCtxArgs* cx) {
+                                float* hidden_out, hipStream_t s, int asf_layer, float* asf_scores, const DecCtxArgs* cx = nullptr) {
     PF_REQUIRE(d && memory && mem_lens && embeds && tok_lens && B > 0 && T > 0 && N > 0, "decoder_forward: null/empty");
     for (int b = 0; b < B; ++b) {
         PF_REQUIRE(mem_lens[b] >= 1 && mem_lens[b] <= T, "decoder_forward: memory lens out of range");
@@ -789,13 +448,12 @@ static int decoder_forward_impl(Decoder* d, const float* memory, const int32_t* 
     // the f16x2 greedy route may pack the token rows instead (below); every other route starts from the padded embeddings
     const bool may_pack = d->precision == 3 && asf_layer < 0 && !cx && ids && !logits && !hidden_out && V > 0;
     if (!may_pack) PF_HIP_TRY(hipMemcpyAsync(x, embeds, sizeof(float) * (size_t)Mq * D, hipMemcpyDeviceToDevice, s));
-    const int left_pad = (c.kernel_size - 1) / 2 + (c.sanm_shift > 0 ? c.sanm_shift : 0);
     if (V == 0 && asf_layer < 0) PF_REQUIRE(!logits && !ids && hidden_out && d->precision != 1,
                            "decoder_forward: a decoder without output layer returns hidden states only (fp32 / bf16x3)");
+    PF_REQUIRE(d->contextual == (cx != nullptr) || asf_layer >= 0, "decoder_forward: a contextual decoder runs through pf_decoder_forward_contextual");
     if (d->precision == 1 && !logits && asf_layer < 0 && !cx) return decoder_forward_bf16(d, memory, B, T, N, ids, hidden_out, s);
     // bf16x3 mode: the two GEMMs that are large at every batch size (w_1: N = ffn_dim; linear_k_v: M = B * T) take
     // three-plane operands on the bf16 matrix cores; the D x D projections and w_2 keep the fp32 MFMA tiles
-    PF_REQUIRE(d->contextual == (cx != nullptr) || asf_layer >= 0, "decoder_forward: a contextual decoder runs through pf_decoder_forward_contextual");
     const bool x3 = d->precision == 2 && asf_layer < 0 && !cx;
     const bool x2 = d->precision == 3 && asf_layer < 0 && !cx;      // the score filter / hotword branch run on the fp32 kernels
     const int Tp = round_up(T, 16), Mkp = B * Tp;           // f16x2: padded key rows per sequence
@@ -856,22 +514,11 @@ static int decoder_forward_impl(Decoder* d, const float* memory, const int32_t* 
         if ((rc = launch_split3(memory, D, d->mem16.as<unsigned short>(), D, (size_t)Mk * D, Mk, D, s))) return rc;
         mem3 = d->mem16.as<unsigned short>();
     }
-    auto w3 = [&](const std::string& name, int rows, int cols) { return x3 ? d->tt.get_split3(name, rows, cols, s) : nullptr; };
+    DecRows rows{x2 ? 3 : x3 ? 2 : 0, Mq, B, N, offs_dev, (c.kernel_size - 1) / 2 + (c.sanm_shift > 0 ? c.sanm_shift : 0), s};
     for (int l = 0; l < c.n_blocks; ++l) {
         const DecLayerW& w = d->layers[l];
-        const std::string lp = dec_layer_prefix(d->contextual, c.n_blocks, l);
         // DecoderLayerSANM.forward (paraformer/decoder.py:78-121)
-        const unsigned short* w1_3 = w3(lp + "feed_forward.w_1.weight", F, D);
-        if (x3 && !w1_3) return -2;
-        if (x2) rc = dec_ffn_x2(d, w, x, t2, Mq, s);
-        else rc = dec_ffn(d, w, x, t2, Mq, s, w1_3);                                          // tgt = FFN(norm1(tgt))
-        if (rc) return rc;
-        if ((rc = layernorm(t2, D, w.n2g, w.n2b, t1, D, Mq, D, D, c.ln_eps, s))) return rc;   // norm2
-        FsmnArgs fa{};                                                                        // x = residual + fsmn
-        fa.in = t1; fa.ldin = D; fa.w = w.fsmn_w; fa.R = x; fa.ldr = D; fa.out = x; fa.ldo = D;
-        fa.lens = d->tok_lens.as<int>(); fa.B = B; fa.T = N; fa.C = D; fa.K = c.kernel_size; fa.left_pad = left_pad;
-        fa.offs = offs_dev;
-        if ((rc = fsmn(fa, s))) return rc;
+        if ((rc = dec_block_step(d, w, x, rows))) return rc;                                  // FFN, norm2, x = residual + fsmn
         if (x2) {                                                                             // norm3 -> linear_q
             unsigned short* t2p = d->t16.as<unsigned short>();
             {
@@ -920,8 +567,8 @@ static int decoder_forward_impl(Decoder* d, const float* memory, const int32_t* 
                 return rc;                                                                        // x = residual + att
             continue;
         } else if (x3) {
-            if ((rc = gemm3_simple(mem3, D, Mk, w3(lp + "src_attn.linear_k_v.weight", 2 * D, D), w.kv_b, d->kv.as<float>(),
-                                   2 * D, 2 * D, D, 0, s))) return rc;
+            if ((rc = gemm3_simple(mem3, D, Mk, d->tt.get_split3(w.prefix + "src_attn.linear_k_v.weight", 2 * D, D, s), w.kv_b,
+                                   d->kv.as<float>(), 2 * D, 2 * D, D, 0, s))) return rc;
         } else if ((rc = gemm_simple(memory, D, w.kv_w, D, w.kv_b, d->kv.as<float>(), 2 * D, Mk, 2 * D, D, 0, nullptr, 0,
                                      nullptr, 0, s))) return rc;
         const bool ctx_block = cx && l == c.n_blocks - 1;
@@ -981,28 +628,10 @@ static int decoder_forward_impl(Decoder* d, const float* memory, const int32_t* 
     }
     // decoders2: FFN -> norm2 -> FSMN memory + residual, no cross-attention; the blocks are built with sanm_shfit 0 whatever the
     // attention blocks use (decoder.py:363-380, DecoderLayerSANM.forward :97-107 with src_attn None)
-    for (int l = 0; l < d->n_blocks2; ++l) {
-        const DecLayerW& w = d->layers2[l];
-        const unsigned short* w1_3 = w3("decoders2." + std::to_string(l) + ".feed_forward.w_1.weight", F, D);
-        if (x3 && !w1_3) return -2;
-        if (x2) rc = dec_ffn_x2(d, w, x, t2, Mq, s);
-        else rc = dec_ffn(d, w, x, t2, Mq, s, w1_3);
-        if (rc) return rc;
-        if ((rc = layernorm(t2, D, w.n2g, w.n2b, t1, D, Mq, D, D, c.ln_eps, s))) return rc;
-        FsmnArgs fa{};
-        fa.in = t1; fa.ldin = D; fa.w = w.fsmn_w; fa.R = x; fa.ldr = D; fa.out = x; fa.ldo = D;
-        fa.lens = d->tok_lens.as<int>(); fa.B = B; fa.T = N; fa.C = D; fa.K = c.kernel_size; fa.left_pad = (c.kernel_size - 1) / 2;
-        fa.offs = offs_dev;
-        if ((rc = fsmn(fa, s))) return rc;
-    }
+    rows.left_pad = (c.kernel_size - 1) / 2;
+    for (const DecLayerW& w : d->layers2) if ((rc = dec_block_step(d, w, x, rows))) return rc;
     // decoders3: FFN only, no residual (decoder.py:438, DecoderLayerSANM with self_attn = src_attn = None)
-    {
-        const unsigned short* w1_3 = w3("decoders3.0.feed_forward.w_1.weight", F, D);
-        if (x3 && !w1_3) return -2;
-        if (x2) rc = dec_ffn_x2(d, d->last, x, t2, Mq, s);
-        else rc = dec_ffn(d, d->last, x, t2, Mq, s, w1_3);
-        if (rc) return rc;
-    }
+    if ((rc = dec_ffn_rows(d, d->last, x, t2, rows))) return rc;
     float* hid = hidden_out ? hidden_out : d->hid.as<float>();
     if (x2 && V > 0 && ids && !logits && !hidden_out) {
         // greedy route in the f16x2 mode: after_norm writes two-plane operands, the vocabulary projection runs on the fp16
@@ -1016,18 +645,10 @@ static int decoder_forward_impl(Decoder* d, const float* memory, const int32_t* 
             if ((rc = launch_layernorm(t2, D, d->tt.get("after_norm.weight"), d->tt.get("after_norm.bias"), reinterpret_cast<float*>(h2), D,
                                        Mq, D, D, c.ln_eps, s, 3, 0, (size_t)Mq * D, pow2f(d->e_an)))) return rc;
         }
-        const int nparts = gemm_f16x2_argmax_parts(Mq, V);
-        if (d->pval.ensure(sizeof(float) * (size_t)Mq * nparts) || d->pidx.ensure(sizeof(int) * (size_t)Mq * nparts)) return -2;
-        Gemm2Args g{};
-        g.A = h2; g.lda = D; g.a_plane = (size_t)Mq * D; g.W = wv2; g.ldw = D; g.w_plane = (size_t)V * D;
-        g.oscale = pow2f(-(d->e_an + ew_v)); g.bias = d->tt.get("output_layer.bias"); g.M = Mq; g.N = V; g.K = D;
-        g.amax_val = d->pval.as<float>(); g.amax_idx = d->pidx.as<int>(); g.amax_ld = nparts;
-        {
-            ProfScope ps(PROF_GEMM3, 2.0 * Mq * (double)V * D, s);
-            if ((rc = launch_gemm_f16x2(g, s))) return rc;
-        }
-        if (!pack) return launch_argmax_reduce(d->pval.as<float>(), d->pidx.as<int>(), nparts, nparts, ids, nullptr, Mq, s);
-        if ((rc = launch_argmax_reduce(d->pval.as<float>(), d->pidx.as<int>(), nparts, nparts, d->ids_packed.as<int>(), nullptr, Mq, s))) return rc;
+        if (argmax_scratch(d->pval, d->pidx, Mq, gemm_f16x2_argmax_parts(Mq, V))) return -2;
+        rc = argmax_f16x2(h2, D, (size_t)Mq * D, wv2, D, (size_t)V * D, pow2f(-(d->e_an + ew_v)), nullptr, d->tt.get("output_layer.bias"),
+                          Mq, V, D, d->pval.as<float>(), d->pidx.as<int>(), pack ? d->ids_packed.as<int>() : ids, s);
+        if (rc || !pack) return rc;
         PF_HIP_TRY(hipMemsetAsync(ids, 0, sizeof(int32_t) * (size_t)Mq_pad, s));       // padding positions: id 0, like an untouched row
         return launch_scatter_i32(d->ids_packed.as<int>(), d->map_dev.as<int>(), ids, Mq, s);
     }
@@ -1036,6 +657,83 @@ static int decoder_forward_impl(Decoder* d, const float* memory, const int32_t* 
     if (V == 0) return 0;
     return vocab_project(hid, Mq, D, d->tt.get("output_layer.weight"), d->tt.get("output_layer.bias"), V, logits, ids,
                          d->pval, d->pidx, s);
+}
+
+}  // namespace pf
+
+using namespace pf;
+
+extern "C" {
+
+// --------------------------------------------------------------------------------------------------- decoder
+pf_decoder* pf_decoder_create(const pf_decoder_config* cfg) { return decoder_create_impl(cfg, false); }
+/* ContextualParaformerDecoder (funasr/models/contextual_paraformer/decoder.py:133-352): n_blocks - 1 standard blocks
+ * ("decoders.{i}."), the last block under "last_decoder.", plus the hotword branch "bias_decoder.norm3.*",
+ * "bias_decoder.src_attn.linear_{q,k_v,out}.*" and the 1x1 fusion "bias_output.weight" [D, 2D, 1] */
+pf_decoder* pf_decoder_create_contextual(const pf_decoder_config* cfg) { return decoder_create_impl(cfg, true); }
+void pf_decoder_destroy(pf_decoder* d) { delete reinterpret_cast<Decoder*>(d); }
+/* decoders2 (paraformer/decoder.py:363-380, :436-437): n_layers = num_blocks - att_layer_num blocks of FFN + FSMN memory (built with
+ * sanm_shfit 0: the taps centred) and NO cross-attention, run between `decoders` and `decoders3`. Tensors "decoders2.<i>.norm1|norm2.*",
+ * "decoders2.<i>.feed_forward.*", "decoders2.<i>.self_attn.fsmn_block.weight". Call once, before the first set_tensor. */
+int pf_decoder_set_decoders2(pf_decoder* dh, int32_t n_layers) {
+    Decoder* d = reinterpret_cast<Decoder*>(dh);
+    PF_REQUIRE(d && n_layers >= 0 && n_layers <= 64, "decoder_set_decoders2: null handle or layer count out of range");
+    PF_REQUIRE(d->n_blocks2 == 0 || d->n_blocks2 == n_layers, "decoder_set_decoders2: already set");
+    if (d->n_blocks2 == n_layers) return 0;
+    int rc = 0;
+    for (int i = 0; i < n_layers; ++i) rc |= dec_layer_add(d->tt, d->cfg, dec2_layer_prefix(i), DEC_FFN_FSMN);
+    if (rc) return -2;
+    d->n_blocks2 = n_layers;
+    ++d->tt.version;         // the table's structure changed: what was resolved and prepared before is stale
+    return 0;
+}
+int pf_decoder_set_tensor(pf_decoder* dh, const char* name, const float* data, int64_t numel) {
+    Decoder* d = reinterpret_cast<Decoder*>(dh);
+    PF_REQUIRE(d && name && data, "decoder_set_tensor: null");
+    return d->tt.set(name, data, numel);
+}
+/* same modes as pf_encoder_set_precision; the bf16 mode serves the fused arg-max route (logits_dev == NULL) */
+int pf_decoder_set_precision(pf_decoder* dh, int32_t mode) {
+    Decoder* d = reinterpret_cast<Decoder*>(dh);
+    PF_REQUIRE(d && mode >= 0 && mode <= 3, "decoder_set_precision: mode must be 0 (fp32 MFMA), 1 (bf16 operands), 2 (fp32 via bf16x3) or 3 (fp32 via f16x2)");
+    PF_REQUIRE(mode == 0 || d->cfg.d_model / d->cfg.n_heads == 128, "decoder_set_precision: heads of d_k <= 64 exist in the fp32 mode only (attention_small.hip)");
+    d->precision = mode;
+    return 0;
+}
+int pf_decoder_missing(const pf_decoder* dh) {
+    const Decoder* d = reinterpret_cast<const Decoder*>(dh);
+    return d ? d->tt.missing() : -1;
+}
+
+int pf_decoder_forward(pf_decoder* dh, const float* memory, const int32_t* mem_lens, const float* embeds,
+                       const int32_t* tok_lens, int32_t B, int32_t T, int32_t N, float* logits, int32_t* ids,
+                       float* hidden_out, void* stream) {
+    return decoder_forward_impl(reinterpret_cast<Decoder*>(dh), memory, mem_lens, embeds, tok_lens, B, T, N, logits, ids,
+                                hidden_out, reinterpret_cast<hipStream_t>(stream), -1, nullptr);
+}
+/* SeACo attention-score filter (seaco_paraformer/model.py:323-335): the bias decoder's blocks 0 .. n_blocks_before - 1 in
+ * full, then block n_blocks_before up to its cross-attention probabilities over the T memory rows (= hotword embeddings);
+ * scores_dev [T] receives their sum over heads and token positions for sequence 0 (attn[0].sum(0).sum(0)). fp32 kernels. */
+int pf_decoder_asf_scores(pf_decoder* dh, const float* memory, const int32_t* mem_lens, const float* embeds,
+                          const int32_t* tok_lens, int32_t B, int32_t T, int32_t N, int32_t n_blocks_before,
+                          float* scores_dev, void* stream) {
+    Decoder* d = reinterpret_cast<Decoder*>(dh);
+    PF_REQUIRE(d && scores_dev && n_blocks_before >= 0 && n_blocks_before < d->cfg.n_blocks, "decoder_asf_scores: bad block index");
+    return decoder_forward_impl(d, memory, mem_lens, embeds, tok_lens, B, T, N, nullptr, nullptr, nullptr,
+                                reinterpret_cast<hipStream_t>(stream), n_blocks_before, scores_dev);
+}
+
+/* ContextualParaformerDecoder.forward (contextual_paraformer/decoder.py:293-352): the last attention block's FSMN-side state
+ * x_self_attn also queries the hotword embeddings `contextual_dev` [B, n_hot, D] through bias_decoder; its output (times
+ * clas_scale) and the block's own cross-attention output are fused by the 1x1 bias_output: x = x_self_attn + W [x_src | cx]. */
+int pf_decoder_forward_contextual(pf_decoder* dh, const float* memory, const int32_t* mem_lens, const float* embeds,
+                                  const int32_t* tok_lens, const float* contextual_dev, int32_t n_hot, float clas_scale,
+                                  int32_t B, int32_t T, int32_t N, float* logits, int32_t* ids, float* hidden_out, void* stream) {
+    Decoder* d = reinterpret_cast<Decoder*>(dh);
+    PF_REQUIRE(d && d->contextual && contextual_dev && n_hot >= 1, "decoder_forward_contextual: needs a contextual decoder and >= 1 hotword row");
+    DecCtxArgs cx{contextual_dev, n_hot, clas_scale};
+    return decoder_forward_impl(d, memory, mem_lens, embeds, tok_lens, B, T, N, logits, ids, hidden_out,
+                                reinterpret_cast<hipStream_t>(stream), -1, nullptr, &cx);
 }
 
 // ------------------------------------------------------------------------------------------------------- ctc
@@ -1076,26 +774,17 @@ int pf_ctc_greedy(pf_ctc* ch, const float* hidden, int32_t M, int32_t* ids, floa
         int ew = 0, rc;
         const unsigned short* w2 = c->tt.get_split2("ctc_lo.weight", V, D, &ew, s);
         if (!w2) return -2;
-        const int nparts = gemm_f16x2_argmax_parts(M, V);
         if (c->h2.ensure(sizeof(unsigned short) * 2 * (size_t)M * D) || c->dsc.ensure(sizeof(float) * 4) ||
-            c->pval.ensure(sizeof(float) * (size_t)M * nparts) || c->pidx.ensure(sizeof(int) * (size_t)M * nparts)) return -2;
+            argmax_scratch(c->pval, c->pidx, M, gemm_f16x2_argmax_parts(M, V))) return -2;
         float* dsc = c->dsc.as<float>();
         if ((rc = launch_absmax(hidden, (size_t)M * D, dsc, s))) return rc;
         if ((rc = launch_pow2_scale(dsc, dsc + 1, s))) return rc;
         if ((rc = launch_split2(hidden, D, c->h2.as<unsigned short>(), D, (size_t)M * D, M, D, 1.f, s, dsc + 1))) return rc;
-        Gemm2Args g{};
-        g.A = c->h2.as<unsigned short>(); g.lda = D; g.a_plane = (size_t)M * D; g.W = w2; g.ldw = D; g.w_plane = (size_t)V * D;
-        g.oscale = pow2f(-ew); g.oscale_dev = dsc + 2; g.bias = c->tt.get("ctc_lo.bias"); g.M = M; g.N = V; g.K = D;
-        g.amax_val = c->pval.as<float>(); g.amax_idx = c->pidx.as<int>(); g.amax_ld = nparts;
-        {
-            ProfScope ps(PROF_GEMM3, 2.0 * M * (double)V * D, s);
-            if ((rc = launch_gemm_f16x2(g, s))) return rc;
-        }
-        return launch_argmax_reduce(c->pval.as<float>(), c->pidx.as<int>(), nparts, nparts, ids, nullptr, M, s);
+        return argmax_f16x2(c->h2.as<unsigned short>(), D, (size_t)M * D, w2, D, (size_t)V * D, pow2f(-ew), dsc + 2, c->tt.get("ctc_lo.bias"),
+                            M, V, D, c->pval.as<float>(), c->pidx.as<int>(), ids, s);
     }
     return vocab_project(hidden, M, c->d_model, c->tt.get("ctc_lo.weight"), c->tt.get("ctc_lo.bias"), c->vocab, logits,
                          ids, c->pval, c->pidx, s);
 }
-
 
 }  // extern "C"

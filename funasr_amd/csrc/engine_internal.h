@@ -1,6 +1,6 @@
 // Internal header of the C-ABI layer (include/paraformer_hip.h): the handle types of every module family and the helpers they
 // share. The layer is split by family -- engine.hip (shared state: errors, profiling, staging ring, instrumented launch helpers,
-// ABI version), engine_frontend.hip, engine_encoder.hip, engine_decoder.hip (predictor, decoder, CTC), engine_stream.hip,
+// ABI version), engine_frontend.hip, engine_encoder.hip, engine_predictor.hip, engine_decoder.hip (decoder, CTC), engine_stream.hip,
 // engine_vad.hip, engine_pipeline.hip, engine_campplus.hip, engine_emotion2vec.hip, engine_conformer.hip (Conformer encoder and
 // Transformer decoder step), engine_posterior.hip (Paraformer-v2 posterior embedder), engine_kernels.hip (the pf_k_* single-kernel hooks) -- so that a kernel change recompiles one family
 // (round-3 review: engine.hip was one 3 400-line translation unit).
@@ -545,7 +545,7 @@ struct Predictor {
     std::vector<int32_t> ul_host;
 };
 
-// the predictor's two phases without the host synchronisation between them (engine_decoder.hip; engine_pipeline.hip drives them)
+// the predictor's two phases without the host synchronisation between them (engine_predictor.hip; engine_pipeline.hip drives them)
 int predictor_alphas_enqueue(Predictor* p, int slot, const float* hidden, const int32_t* lens_host, int B, int T, hipStream_t s);
 const int32_t* predictor_counts_dev(Predictor* p, int slot);
 const float* predictor_alphas_dev(Predictor* p, int slot);
@@ -553,9 +553,17 @@ const float* predictor_peaks_dev(Predictor* p, int slot);
 int predictor_embeds_slot(Predictor* p, int slot, const float* hidden, int B, int T, int N, float* embeds, hipStream_t s);
 
 // ================================================================================================= decoder
+// What a layer holds, by kind: decoders3.0 is the FFN alone, a decoders2 block adds norm2 + the FSMN memory, a block of `decoders` (and
+// the contextual decoder's last_decoder) adds norm3 + the cross-attention. The tensor names of each kind are spelled once, in
+// dec_layer_add / dec_layer_resolve (engine_decoder.hip), under the layer's `prefix`.
+enum { DEC_FFN = 0, DEC_FFN_FSMN = 1, DEC_FFN_FSMN_ATTN = 2 };
 struct DecLayerW {
-    const float *n1g, *n1b, *w1, *b1, *fng, *fnb, *w2, *n2g, *n2b, *fsmn_w, *n3g, *n3b, *q_w, *q_b, *kv_w, *kv_b,
-        *o_w, *o_b;
+    std::string prefix;      // "decoders.<i>." / "last_decoder." / "decoders2.<i>." / "decoders3.0."
+    int kind = DEC_FFN;
+    const float *n1g = nullptr, *n1b = nullptr, *w1 = nullptr, *b1 = nullptr, *fng = nullptr, *fnb = nullptr, *w2 = nullptr;
+    const float *n2g = nullptr, *n2b = nullptr, *fsmn_w = nullptr;                                       // kind >= DEC_FFN_FSMN
+    const float *n3g = nullptr, *n3b = nullptr, *q_w = nullptr, *q_b = nullptr, *kv_w = nullptr, *kv_b = nullptr, *o_w = nullptr,
+        *o_b = nullptr;                                                                                   // DEC_FFN_FSMN_ATTN
     // f16x2 mode: weight planes + exponents, and the exponents of the LayerNorm-output planes (from gamma / beta)
     const unsigned short *w1_2 = nullptr, *w2_2 = nullptr, *q_2 = nullptr, *kv_2 = nullptr, *o_2 = nullptr;
     int ew_1 = 0, ew_2 = 0, ew_q = 0, ew_kv = 0, ew_o = 0, e_n1 = 0, e_fn = 0, e_n3 = 0, e_q = 0;
@@ -695,11 +703,17 @@ int encoder_prepare(Encoder* e, int mode, hipStream_t s);
 int encoder_default_pe(Encoder* e, int T, hipStream_t s);
 int encoder_block(Encoder* e, const EncLayerW& w, float* x_in, int ld_in, float* x, int B, int T,
                          hipStream_t s, const EncChunkCtx* cc = nullptr, bool xn_ready = false, const EncLayerW* next = nullptr);
-std::string dec_layer_prefix(bool contextual, int n_blocks, int i);
 // resolve the weights and, with x2, prepare the f16x2 state; a no-op while the stamps match
 int decoder_prepare(Decoder* d, bool x2, hipStream_t s);
 int vocab_project(const float* hidden, int M, int D, const float* W, const float* bias, int V, float* logits,
                          int32_t* ids, DevBuf& pval, DevBuf& pidx, hipStream_t s);
+// the fused arg-max tails, one per arithmetic (engine_decoder.hip): scratch [M, parts] for the epilogue's partials, then GEMM + reduction
+static inline int argmax_f32_parts(int N) { return 2 * ceil_div(N, 128); }
+int argmax_scratch(DevBuf& pval, DevBuf& pidx, int M, int parts);
+int argmax_f32(const float* A, int lda, const float* W, int ldw, const float* bias, int M, int N, int K, int ab_bf16, float* sval,
+               int* sidx, int32_t* ids, hipStream_t s);
+int argmax_f16x2(const unsigned short* A2, int lda, size_t a_plane, const unsigned short* W2, int ldw, size_t w_plane, float oscale,
+                 const float* oscale_dev, const float* bias, int M, int N, int K, float* sval, int* sidx, int32_t* ids, hipStream_t s);
 // C[M, N] = A W^T + bias (+ R1) (ReLU before the addend) in one of two modes. A is a_rows physical rows of `width` floats, viewed as M
 // rows of K columns at row stride lda (an overlapping view where lda < K). x2 = false: the exact-fp32 MFMA GEMM. x2 = true: A's rows
 // are split into two fp16 planes at the a-priori exponent e_a (into `planes`), the weight's cached planes are fetched, and the GEMM
@@ -713,11 +727,9 @@ int gemm2_simple(const unsigned short* A2, int lda, int M, int ea, const unsigne
                         const float* oscale_dev = nullptr, float* splitk_part = nullptr);
 struct FoldedLn { const float* g; const float* b; float* y; int out; float oscale; };   // out: 0 fp32 rows, 3 two fp16 planes of y * oscale
 int dec_ffn_x2(Decoder* d, const DecLayerW& w, const float* x, float* out, int M, hipStream_t s, float* splitk_part = nullptr,
-               const FoldedLn* ln = nullptr, bool fold_fn = false);
+               const FoldedLn* ln = nullptr);
 int dec_ffn(Decoder* d, const DecLayerW& w, const float* x, float* out, int M, hipStream_t s,
                    const unsigned short* w1_3 = nullptr);
-int decoder_forward_bf16(Decoder* d, const float* memory, int B, int T, int N, int32_t* ids, float* hidden_out,
-                                hipStream_t s);
 int lstm_forward(const LstmW& w, const float* x_tm, int T, int B, int D, int H, int ndir, float* out, int out_layout,
                         DevBuf& pre, DevBuf& h_a, DevBuf& h_b, DevBuf& cell, hipStream_t s);
 

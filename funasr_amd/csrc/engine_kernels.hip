@@ -297,13 +297,8 @@ int pf_k_gemm_f16x2_argmax(const void* A2, int32_t lda, int64_t a_plane, const v
                            void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     PF_REQUIRE(ids && sval && sidx, "gemm_f16x2_argmax: scratch required");
-    Gemm2Args g{};
-    g.A = reinterpret_cast<const unsigned short*>(A2); g.lda = lda; g.a_plane = (size_t)a_plane;
-    g.W = reinterpret_cast<const unsigned short*>(W2); g.ldw = ldw; g.w_plane = (size_t)w_plane; g.oscale = oscale; g.bias = bias;
-    g.M = M; g.N = N; g.K = K; g.amax_val = sval; g.amax_idx = sidx; g.amax_ld = gemm_f16x2_argmax_parts(M, N);
-    int rc;
-    if ((rc = launch_gemm_f16x2(g, s))) return rc;
-    return launch_argmax_reduce(sval, sidx, g.amax_ld, g.amax_ld, ids, nullptr, M, s);
+    return argmax_f16x2(reinterpret_cast<const unsigned short*>(A2), lda, (size_t)a_plane, reinterpret_cast<const unsigned short*>(W2), ldw,
+                        (size_t)w_plane, oscale, nullptr, bias, M, N, K, sval, sidx, ids, s);
 }
 /* fp32 -> bf16 (round to nearest even), n elements */
 int pf_k_cast_bf16(const float* x, void* y, int64_t n, void* stream) {
@@ -313,13 +308,7 @@ int pf_k_gemm_argmax_f32(const float* A, int32_t lda, const float* W, int32_t ld
                          int32_t N, int32_t K, int32_t* ids, float* sval, int32_t* sidx, void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     PF_REQUIRE(ids && sval && sidx, "gemm_argmax: scratch [M, 2*ceil(N/128)] required");
-    const int nparts = 2 * ceil_div(N, 128);
-    GemmArgs g{};
-    g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.M = M; g.N = N; g.K = K;
-    g.amax_val = sval; g.amax_idx = sidx; g.amax_ld = nparts;
-    int rc;
-    if ((rc = gemm(g, s))) return rc;
-    return launch_argmax_reduce(sval, sidx, nparts, nparts, ids, nullptr, M, s);
+    return argmax_f32(A, lda, W, ldw, bias, M, N, K, 0, sval, sidx, ids, s);
 }
 /* y[row] = x[row] - logsumexp(x[row]) over N columns, fp32 (may run in place) */
 int pf_k_log_softmax(const float* x, int32_t ldx, float* y, int32_t ldy, int32_t M, int32_t N, void* stream) {

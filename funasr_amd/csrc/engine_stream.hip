@@ -89,11 +89,6 @@ static int stream_prepare_ln_consts(Stream* st, hipStream_t s) {
     return 0;
 }
 
-// f16x2 step: the decoder FFN's inner LayerNorm (ffn_dim wide) in the second launch of a split-K w_1 -- replaces a launch, for
-// handles small enough that the extra blocks find idle CUs (the rule of short_k)
-static bool stream_short_k(const Stream* st);
-static bool x2_fold_fn(const Stream* st) { return st->ln_folded && stream_short_k(st); }
-
 static int stream_token_rows(const Stream* st, int W, int is_final) {
     const int fires = W + 1 + (is_final ? 1 : 0);
     return fires < st->Nmax ? fires : st->Nmax;
@@ -231,8 +226,7 @@ static int stream_enqueue(Stream* st, int n, int is_final, int tail, hipStream_t
         if (d->t16.ensure(sizeof(unsigned short) * 2 * (size_t)Mq * D) || d->ffn16.ensure(sizeof(unsigned short) * 2 * (size_t)Mq * dc.ffn_dim) ||
             d->ctx16.ensure(sizeof(unsigned short) * 2 * (size_t)Mq * D))
             return -2;
-        // (the decoder FFN's inner norm folded into a split-K w_1 needs ffn_dim-wide slices: small handles only, like short_k)
-        if (d->splitk.ensure(sizeof(float) * 4 * (size_t)Mq * (x2_fold_fn(st) ? dc.ffn_dim : D))) return -2;
+        if (d->splitk.ensure(sizeof(float) * 4 * (size_t)Mq * D)) return -2;       // w_2's four K slices [4][Mq][d_model]
         t2p = d->t16.as<unsigned short>(); c2p = d->ctx16.as<unsigned short>();
         if ((rc = launch_split2(enc_out, D, st->mem2.as<unsigned short>(), D, (size_t)Mk * D, Mk, D, pow2f(st->e_mem), s))) return rc;
         mem2 = st->mem2.as<unsigned short>();
@@ -315,7 +309,7 @@ static int stream_enqueue(Stream* st, int n, int is_final, int tail, hipStream_t
         } else {
             const bool fold = x2 && st->ln_folded && dc.ffn_dim % 128 == 0;       // norm2 in the second launch of the split-K w_2
             const FoldedLn n2{w.n2g, w.n2b, t1, 0, 1.f};
-            if ((rc = x2 ? dec_ffn_x2(d, w, dx, t2, Mq, s, d->splitk.as<float>(), fold ? &n2 : nullptr, x2_fold_fn(st)) : dec_ffn(d, w, dx, t2, Mq, s))) return rc;
+            if ((rc = x2 ? dec_ffn_x2(d, w, dx, t2, Mq, s, d->splitk.as<float>(), fold ? &n2 : nullptr) : dec_ffn(d, w, dx, t2, Mq, s))) return rc;
             if (!fold && (rc = layernorm(t2, D, w.n2g, w.n2b, t1, D, Mq, D, D, dc.ln_eps, s))) return rc;
             if ((rc = launch_dec_fsmn_chunk(fa, s))) return rc;
         }
@@ -395,32 +389,26 @@ static int stream_enqueue(Stream* st, int n, int is_final, int tail, hipStream_t
         // decoders3's FFN; after_norm's planes (the vocabulary projection's operand) from the second launch of its split-K w_2
         const bool fold = st->ln_folded && dc.ffn_dim % 128 == 0;
         const FoldedLn an{d->tt.get("after_norm.weight"), d->tt.get("after_norm.bias"), reinterpret_cast<float*>(t2p), 3, pow2f(d->e_an)};
-        if ((rc = dec_ffn_x2(d, d->last, dx, t2, Mq, s, d->splitk.as<float>(), fold ? &an : nullptr, x2_fold_fn(st)))) return rc;
+        if ((rc = dec_ffn_x2(d, d->last, dx, t2, Mq, s, d->splitk.as<float>(), fold ? &an : nullptr))) return rc;
         an_folded = fold;
     } else if ((rc = dec_ffn(d, d->last, dx, t2, Mq, s))) return rc;
     if (dcarry) {                          // (after_norm + the vocabulary projection: above)
     } else if (x2) {
         // after_norm writes two-plane operands, the vocabulary projection runs with the row arg-max fused into its epilogue
         // (the offline greedy route of decoder_forward_impl)
-        auto wv = d->tt.b16.find("output_layer.weight#split2");
-        if (wv == d->tt.b16.end()) { set_error("stream: f16x2 step without prepared vocabulary planes"); return -1; }
-        const int ew_v = d->tt.exp2.at("output_layer.weight#split2");
+        // (decoder_prepare made the planes: checked by its stamp, so that get_split2 only looks them up -- nothing is computed in a capture)
+        if (d->x2_for != d->tt.version) { set_error("stream: f16x2 step without prepared vocabulary planes"); return -1; }
+        int ew_v = 0;
+        const unsigned short* wv2 = d->tt.get_split2("output_layer.weight", V, D, &ew_v, s);
+        if (!wv2) return -2;
         if (!an_folded) {
             ProfScope ps(PROF_LN, 8.0 * Mq * (double)D, s);
             if ((rc = launch_layernorm(t2, D, d->tt.get("after_norm.weight"), d->tt.get("after_norm.bias"), reinterpret_cast<float*>(t2p), D,
                                        Mq, D, D, dc.ln_eps, s, 3, 0, (size_t)Mq * D, pow2f(d->e_an)))) return rc;
         }
-        const int nparts = gemm_f16x2_argmax_parts(Mq, V);
-        if (d->pval.ensure(sizeof(float) * (size_t)Mq * nparts) || d->pidx.ensure(sizeof(int) * (size_t)Mq * nparts)) return -2;
-        Gemm2Args g{};
-        g.A = t2p; g.lda = D; g.a_plane = (size_t)Mq * D; g.W = wv->second; g.ldw = D; g.w_plane = (size_t)V * D;
-        g.oscale = pow2f(-(d->e_an + ew_v)); g.bias = d->tt.get("output_layer.bias"); g.M = Mq; g.N = V; g.K = D;
-        g.amax_val = d->pval.as<float>(); g.amax_idx = d->pidx.as<int>(); g.amax_ld = nparts;
-        {
-            ProfScope ps(PROF_GEMM3, 2.0 * Mq * (double)V * D, s);
-            if ((rc = launch_gemm_f16x2(g, s))) return rc;
-        }
-        if ((rc = launch_argmax_reduce(d->pval.as<float>(), d->pidx.as<int>(), nparts, nparts, st->ids.as<int32_t>(), nullptr, Mq, s))) return rc;
+        if (argmax_scratch(d->pval, d->pidx, Mq, gemm_f16x2_argmax_parts(Mq, V))) return -2;
+        if ((rc = argmax_f16x2(t2p, D, (size_t)Mq * D, wv2, D, (size_t)V * D, pow2f(-(d->e_an + ew_v)), nullptr, d->tt.get("output_layer.bias"),
+                               Mq, V, D, d->pval.as<float>(), d->pidx.as<int>(), st->ids.as<int32_t>(), s))) return rc;
     } else {
         if ((rc = layernorm(t2, D, d->tt.get("after_norm.weight"), d->tt.get("after_norm.bias"), d->hid.as<float>(), D, Mq,
                             D, D, dc.ln_eps, s))) return rc;

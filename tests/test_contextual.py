@@ -153,3 +153,32 @@ def test_contextual_decoder_on_the_gpu_equals_reference_logits(cuda, tag):
     ids, _ = d.greedy(*args, contextual_info=t("hot").to(cuda), clas_scale=scale)
     for b, n in enumerate(t("tok_lens").tolist()):
         assert ids[b, :n].cpu().tolist() == ref[b, :n].argmax(-1).tolist()
+
+
+@pytest.mark.gpu
+def test_plain_forward_on_a_contextual_handle_is_refused_in_the_bf16_mode(cuda):
+    """pf_decoder_forward (no hotword rows) on a handle of pf_decoder_create_contextual returns a status and names the entry point to
+    use, in the bf16 mode like in every other: the bf16 forward would look for "decoders.<last>.*", which a contextual table keeps
+    under "last_decoder.". The handle stays usable: back in the fp32 mode the contextual forward gives the reference logits."""
+    from funasr_amd import _lib
+    from funasr_amd.contextual_paraformer import ContextualParaformerDecoder
+    from funasr_amd.hip_module import host_i32, stream_ptr
+    dc, sd, t, scale = _decoder_case("a")
+    d = ContextualParaformerDecoder(**dc)
+    d.load_state_dict(sd, strict=False)
+    d = d.to(cuda)
+    lib, h = d._ensure_handle()
+    mem, emb = t("memory").to(cuda).contiguous(), t("embeds").to(cuda).contiguous()
+    (B, T, _), N = mem.shape, emb.shape[1]
+    mlen_c, _ = host_i32(t("mem_lens"), B)
+    tlen_c, _ = host_i32(t("tok_lens"), B)
+    ids = torch.zeros(B, N, device=cuda, dtype=torch.int32)
+    assert lib.pf_decoder_set_precision(h, 1) == 0, _lib.last_error()
+    with torch.cuda.device(cuda):
+        rc = lib.pf_decoder_forward(h, mem.data_ptr(), mlen_c, emb.data_ptr(), tlen_c, B, T, N, None, ids.data_ptr(), None, stream_ptr())
+    assert rc != 0 and "pf_decoder_forward_contextual" in _lib.last_error(), (rc, _lib.last_error())
+    assert lib.pf_decoder_set_precision(h, 0) == 0, _lib.last_error()
+    logits, _ = d(mem, t("mem_lens"), emb, t("tok_lens"), contextual_info=t("hot").to(cuda), clas_scale=scale)
+    ref = t("logits")
+    for b, n in enumerate(t("tok_lens").tolist()):
+        assert (logits[b, :n].cpu() - ref[b, :n]).abs().max().item() < 2e-4, b

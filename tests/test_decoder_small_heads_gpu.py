@@ -50,3 +50,29 @@ def test_the_streaming_handle_refuses_a_small_head_decoder(cuda):
         lib.pf_decoder_destroy(plain)
         lib.pf_predictor_destroy(p)
         lib.pf_encoder_destroy(e)
+
+
+def test_a_fresh_decoder_handle_registers_every_tensor_of_each_layer_kind_once(cuda):
+    """pf_decoder_missing on handles that carry no weights counts the names the library registered. With n_blocks = 2: 18 per
+    attention block (7 of the feed-forward, norm2 x 2 and fsmn_block, norm3 x 2, 6 projection tensors), 7 for decoders3.0, 2 for
+    after_norm, 2 for output_layer, 9 for the contextual decoder's hotword branch, 10 per decoders2 block (an attention block less
+    norm3 and the projections)."""
+    lib = _lib.load()
+
+    def make(vocab, contextual=False):
+        cfg = _lib.pf_decoder_config(vocab, 256, 2, 256, 2, 11, 5, 1e-12)
+        h = (lib.pf_decoder_create_contextual if contextual else lib.pf_decoder_create)(C.byref(cfg))
+        assert h, _lib.last_error()
+        return h
+
+    plain, bare, ctx = make(300), make(0), make(300, contextual=True)
+    try:
+        assert lib.pf_decoder_missing(plain) == 2 * 18 + 7 + 2 + 2 == 47
+        assert lib.pf_decoder_missing(bare) == 2 * 18 + 7 + 2 == 45
+        assert lib.pf_decoder_missing(ctx) == 47 + 9 == 56
+        for h, before in ((plain, 47), (ctx, 56)):
+            assert lib.pf_decoder_set_decoders2(h, 1) == 0, _lib.last_error()
+            assert lib.pf_decoder_missing(h) == before + 10
+    finally:
+        for h in (plain, bare, ctx):
+            lib.pf_decoder_destroy(h)
