@@ -95,6 +95,10 @@ class pf_conformer_config(C.Structure):
                                           "precision")] + [("ln_eps", C.c_float)]
 
 
+class pf_tfencoder_config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("input_dim", "d_model", "n_heads", "ffn_dim", "n_blocks", "precision")] + [("ln_eps", C.c_float)]
+
+
 class pf_tdecoder_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("vocab_size", "d_model", "n_heads", "ffn_dim", "n_blocks")] + [("ln_eps", C.c_float)]
 
@@ -194,6 +198,15 @@ SIGNATURES = {
     "pf_conformer_set_precision": (C.c_int, [_vp, _i32]),
     "pf_conformer_num_frames": (_i32, [_vp, _i32, _i32]),
     "pf_conformer_forward": (C.c_int, [_vp, _vp, _pi32, _i32, _i32, _vp, _pi32, _vp]),
+    "pf_tfencoder_create": (_vp, [C.POINTER(pf_tfencoder_config)]),
+    "pf_tfencoder_destroy": (None, [_vp]),
+    "pf_tfencoder_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),
+    "pf_tfencoder_missing": (C.c_int, [_vp]),
+    "pf_tfencoder_set_precision": (C.c_int, [_vp, _i32]),
+    "pf_tfencoder_num_frames": (_i32, [_vp, _i32, _i32]),
+    "pf_tfencoder_forward": (C.c_int, [_vp, _vp, _pi32, _i32, _i32, _vp, _pi32, _vp]),
+    "pf_k_tf_attention": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "pf_k_tf_embed_rows": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _f32, _vp, _vp]),
     "pf_tdecoder_create": (_vp, [C.POINTER(pf_tdecoder_config)]),
     "pf_tdecoder_destroy": (None, [_vp]),
     "pf_tdecoder_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),

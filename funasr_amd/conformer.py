@@ -15,6 +15,9 @@ frames (and, through the mask rule, its output length) depend on the longest cli
 the padded-batch result is the contract, every row of the batch is computed. A batch of equal-length clips has no padding and
 there a clip's result is bitwise what it is alone.
 
+`Conv2dSubsampledEncoder` (the forward over the padded batch) and `AttentionEncoderDecoder` (the model: everything but the encoder)
+are the bases this module shares with funasr_amd/transformer.py, the plain-Transformer sibling.
+
 All modules hold the reference's parameters under the reference's state_dict keys (BatchNorm's running statistics included);
 the positional tables are built on the host exactly as the reference builds them (float32 torch ops) and uploaded.
 """
@@ -101,8 +104,52 @@ def _ffn(D: int, units: int) -> Holder:
     return f
 
 
+class Conv2dSubsampledEncoder(HipModule):
+    """what the two encoders behind Conv2dSubsampling share: the precision switch and the forward over the zero-padded batch (the C
+    entry points `<_prefix>_set_precision` / `<_prefix>_forward` have one signature). A subclass holds the parameters, `pos_table`,
+    `precision` and `_output_size`."""
+
+    def output_size(self) -> int:
+        return self._output_size
+
+    def _extra_tensors(self):
+        return (("pos_table", self.pos_table),)
+
+    def set_precision(self, mode=None):
+        mode = mode or "f16x2"
+        if mode not in _PRECISIONS:
+            raise NotImplementedError(f"{type(self).__name__}(HIP): precision {mode!r}: built are {sorted(_PRECISIONS)}")
+        self.precision = mode
+        if self._handle is not None:
+            _lib.check(getattr(_lib.load(), self._prefix + "_set_precision")(self._handle, _PRECISIONS[mode]), self._prefix + "_set_precision")
+        return self
+
+    def forward(self, xs_pad: torch.Tensor, ilens, prev_states=None, ctc=None):
+        """xs_pad [B, L, input_size] zero-padded features, ilens [B] -> (out [B, T, D], olens [B] int64 on the device, None): every
+        row of the padded batch, lengths by the reference's mask rule (funasr/models/conformer/encoder.py:559-636)"""
+        lens = [int(v) for v in (ilens.tolist() if isinstance(ilens, torch.Tensor) else ilens)]
+        B, L = int(xs_pad.shape[0]), int(xs_pad.shape[1])
+        if L < 7:
+            raise TooShortUttError(f"has {L} frames and is too short for subsampling (it needs more than 7 frames), return empty results", L, 7)
+        T = subsampled_length(L, L)
+        if T > MAX_LEN:
+            raise ValueError(f"{type(self).__name__}: {T} encoder frames in one batch; the positional tables hold {MAX_LEN} (200 s of audio). "
+                             "Split the input (the reference's result beyond that depends on the process's call history)")
+        lib, h = self._ensure_handle()
+        dev = self._handle_device
+        x = xs_pad.to(device=dev, dtype=torch.float32).contiguous()
+        out = torch.empty(B, T, self._output_size, device=dev)
+        ln = (_lib.C.c_int32 * B)(*lens)
+        ol = (_lib.C.c_int32 * B)()
+        with torch.cuda.device(dev):
+            _lib.check(getattr(lib, self._prefix + "_forward")(h, x.data_ptr(), ln, B, L, out.data_ptr(), ol, stream_ptr()), self._prefix + "_forward")
+            torch.cuda.current_stream(dev).synchronize()           # the lengths are staged asynchronously
+        olens = torch.tensor(list(ol), dtype=torch.int64, device=dev)
+        return out, olens, None
+
+
 @tables.register("encoder_classes", "ConformerEncoder")
-class ConformerEncoder(HipModule):
+class ConformerEncoder(Conv2dSubsampledEncoder):
     _prefix = "pf_conformer"
     _push_buffers = True
 
@@ -182,12 +229,6 @@ class ConformerEncoder(HipModule):
         # div_term -- a sinusoid of position ~5000 moves by up to 5e-4 with it -- exactly as the reference's own table does.
         self.pos_table = legacy_rel_pos_table(D) if self.legacy else latest_rel_pos_table(D)
 
-    def output_size(self) -> int:
-        return self._output_size
-
-    def _extra_tensors(self):
-        return (("pos_table", self.pos_table),)
-
     def pos_rows(self, T: int) -> torch.Tensor:
         """the rows of the table a forward over T encoder frames reads (a view)"""
         return self.pos_table[:T] if self.legacy else self.pos_table[MAX_LEN - T: MAX_LEN + T - 1]
@@ -198,38 +239,6 @@ class ConformerEncoder(HipModule):
         c.n_blocks, c.kernel_size, c.macaron, c.legacy = self.num_blocks, self.kernel, int(self.macaron), int(self.legacy)
         c.precision, c.ln_eps = _PRECISIONS[self.precision], 1e-12
         return c
-
-    def set_precision(self, mode=None):
-        mode = mode or "f16x2"
-        if mode not in _PRECISIONS:
-            raise NotImplementedError(f"ConformerEncoder(HIP): precision {mode!r}: built are {sorted(_PRECISIONS)}")
-        self.precision = mode
-        if self._handle is not None:
-            _lib.check(_lib.load().pf_conformer_set_precision(self._handle, _PRECISIONS[mode]), "pf_conformer_set_precision")
-        return self
-
-    def forward(self, xs_pad: torch.Tensor, ilens, prev_states=None, ctc=None):
-        """xs_pad [B, L, input_size] zero-padded features, ilens [B] -> (out [B, T, D], olens [B] int64 on the device, None): every
-        row of the padded batch, lengths by the reference's mask rule (funasr/models/conformer/encoder.py:559-636)"""
-        lens = [int(v) for v in (ilens.tolist() if isinstance(ilens, torch.Tensor) else ilens)]
-        B, L = int(xs_pad.shape[0]), int(xs_pad.shape[1])
-        if L < 7:
-            raise TooShortUttError(f"has {L} frames and is too short for subsampling (it needs more than 7 frames), return empty results", L, 7)
-        T = subsampled_length(L, L)
-        if T > MAX_LEN:
-            raise ValueError(f"ConformerEncoder: {T} encoder frames in one batch; the positional tables hold {MAX_LEN} (200 s of audio). "
-                             "Split the input (the reference's result beyond that depends on the process's call history)")
-        lib, h = self._ensure_handle()
-        dev = self._handle_device
-        x = xs_pad.to(device=dev, dtype=torch.float32).contiguous()
-        out = torch.empty(B, T, self._output_size, device=dev)
-        ln = (_lib.C.c_int32 * B)(*lens)
-        ol = (_lib.C.c_int32 * B)()
-        with torch.cuda.device(dev):
-            _lib.check(lib.pf_conformer_forward(h, x.data_ptr(), ln, B, L, out.data_ptr(), ol, stream_ptr()), "pf_conformer_forward")
-            torch.cuda.current_stream(dev).synchronize()           # the lengths are staged asynchronously
-        olens = torch.tensor(list(ol), dtype=torch.int64, device=dev)
-        return out, olens, None
 
 
 @tables.register("decoder_classes", "TransformerDecoder")
@@ -319,9 +328,12 @@ class TransformerDecoder(HipModule):
             torch.cuda.current_stream(self._handle_device).synchronize()
 
 
-@tables.register("model_classes", "Conformer")
-class Conformer(nn.Module):
-    """funasr/models/conformer/model.py Conformer(Transformer)"""
+class AttentionEncoderDecoder(nn.Module):
+    """funasr/models/transformer/model.py Transformer, the CTC / attention encoder-decoder the reference's `Conformer` subclasses
+    with nothing added: everything but the encoder. A model class names the one encoder it accepts (`_encoder`) and what its
+    refusal of another says (`_other_encoders`); funasr_amd.transformer.Transformer is the other one."""
+    _encoder = None                # the encoder_classes key
+    _other_encoders = ""
 
     def __init__(self, specaug: Optional[str] = None, specaug_conf: Optional[Dict] = None, normalize: str = None,
                  normalize_conf: Optional[Dict] = None, encoder: str = None, encoder_conf: Optional[Dict] = None, decoder: str = None,
@@ -330,20 +342,20 @@ class Conformer(nn.Module):
                  sos: int = 1, eos: int = 2, lsm_weight: float = 0.0, length_normalized_loss: bool = False, report_cer: bool = True,
                  report_wer: bool = True, sym_space: str = "<space>", sym_blank: str = "<blank>", share_embedding: bool = False, **kwargs):
         super().__init__()
-        if encoder != "ConformerEncoder":
-            raise NotImplementedError(f"Conformer(HIP): encoder: {encoder} is not built (only ConformerEncoder; the Transformer / "
-                                      "Branchformer families are other models)")
+        me = type(self).__name__
+        if encoder != self._encoder:
+            raise NotImplementedError(f"{me}(HIP): encoder: {encoder} is not built (only {self._encoder}; {self._other_encoders})")
         if decoder is None or float(ctc_weight) == 1.0:
-            raise NotImplementedError("Conformer(HIP): a model without decoder (decoder: null or ctc_weight: 1.0) is not built")
+            raise NotImplementedError(f"{me}(HIP): a model without decoder (decoder: null or ctc_weight: 1.0) is not built")
         if decoder != "TransformerDecoder":
-            raise NotImplementedError(f"Conformer(HIP): decoder: {decoder} is not built (only TransformerDecoder)")
+            raise NotImplementedError(f"{me}(HIP): decoder: {decoder} is not built (only TransformerDecoder)")
         if float(interctc_weight) != 0.0:
-            raise NotImplementedError("Conformer(HIP): interctc_weight is not built")
+            raise NotImplementedError(f"{me}(HIP): interctc_weight is not built")
         if _truthy(share_embedding):
-            raise NotImplementedError("Conformer(HIP): share_embedding: true is not built")
+            raise NotImplementedError(f"{me}(HIP): share_embedding: true is not built")
         enc_conf = dict(encoder_conf or {})
         enc_conf.pop("input_size", None)
-        self.encoder = ConformerEncoder(input_size=input_size, **enc_conf)
+        self.encoder = tables.encoder_classes[self._encoder](input_size=input_size, **enc_conf)
         d = self.encoder.output_size()
         dec_conf = dict(decoder_conf or {})
         dec_conf.pop("vocab_size", None)
@@ -442,7 +454,7 @@ class Conformer(nn.Module):
         from .tokenizer import sentence_postprocess
 
         if self.ctc is None:
-            raise RuntimeError("Conformer.inference(batch_size > 1) decodes the CTC head; this model has none (ctc_weight 0)")
+            raise RuntimeError(f"{type(self).__name__}.inference(batch_size > 1) decodes the CTC head; this model has none (ctc_weight 0)")
         speech, lens, meta = self._features(data_in, data_lengths, frontend, kwargs)
         encoder_out, olens = self.encode(speech, lens)
         ids = self.ctc_greedy(encoder_out, olens)
@@ -489,3 +501,10 @@ class Conformer(nn.Module):
                     writer["token"][key[i]] = " ".join(token)
                     writer["text"][key[i]] = text
         return results, meta
+
+
+@tables.register("model_classes", "Conformer")
+class Conformer(AttentionEncoderDecoder):
+    """funasr/models/conformer/model.py Conformer(Transformer)"""
+    _encoder = "ConformerEncoder"
+    _other_encoders = "the Transformer / Branchformer families are other models"

@@ -1,5 +1,5 @@
-// Kernel launchers of the Conformer encoder and the Transformer decoder step (conformer.hip, attention_relpos.hip; driven by
-// engine_conformer.hip). Activations are rows of a [B * T, D] buffer (T = the BATCH's encoder length: the reference computes every
+// Kernel launchers of the Conformer encoder, the Transformer encoder and the Transformer decoder step (conformer.hip,
+// attention_relpos.hip, attention_abs.hip; driven by engine_conformer.hip). Activations are rows of a [B * T, D] buffer (T = the BATCH's encoder length: the reference computes every
 // row of the zero-padded batch and so does this path). Every kernel computes a row in a fixed order and without atomics.
 #pragma once
 #include "common.h"
@@ -16,8 +16,9 @@ int launch_cf_conv0(const float* feats, int B, int Tin, int F, const float* w, c
 // in place over n floats: mode 0 = ReLU, 1 = Swish (x * sigmoid(x)); n % 4 == 0
 int launch_cf_act(float* x, size_t n, int mode, hipStream_t stream);
 
-// y[b * T + t] = x[b * NE + t] * scale for t < T (the embed linear's rows without the waste row per sequence, times sqrt(D))
-int launch_cf_scale_rows(const float* x, int NE, float* y, int B, int T, int D, float scale, hipStream_t stream);
+// y[b * T + t] = x[b * NE + t] * scale for t < T (the embed linear's rows without the waste row per sequence, times sqrt(D));
+// with pe [>= T, D] (the Transformer encoder's PositionalEncoding): ... + pe[t], the product rounded before the sum
+int launch_cf_scale_rows(const float* x, int NE, float* y, int B, int T, int D, float scale, const float* pe, hipStream_t stream);
 
 // The Conformer convolution module between its two pointwise convs: g [B * T, 2 D] (value | gate) -> GLU -> depthwise Conv1d over
 // time (taps odd <= 31, zero padding at the edges of each sequence's T rows) + bias -> eval-mode BatchNorm as y * bn_scale +
@@ -34,6 +35,12 @@ int launch_cf_glu_dw(const float* g, const float* dw, const float* dw_bias, cons
 // on the matrix cores in exact fp32 (v_mfma_f32_32x32x2_f32); fp32 online softmax -> out [B * T, D].
 int launch_cf_relpos_attention(const float* qkv, const float* P, const float* u, const float* v, const int* klens, int B, int T,
                                int H, int legacy, float* out, hipStream_t stream);
+
+// Plain masked self-attention (MultiHeadedAttention), head dim 64, flash-style, the tile mapping of the kernel above without its
+// positional half: qkv [B * T, 3 D] (q | k | v, head h at column 64 h of each), score(i, j) = q_i . k_j / 8, keys j >= klens[b]
+// masked (klens[b] == 0: zero rows; no K / V row at or past klens[b] is read). q . k and p . v on the matrix cores in exact fp32
+// (v_mfma_f32_32x32x2_f32); fp32 online softmax -> out [B * T, D].
+int launch_tf_attention(const float* qkv, const int* klens, int B, int T, int H, float* out, hipStream_t stream);
 
 // ---- Transformer decoder step
 // x[r] = table[ids[r]] * scale + pe[pos] (r < n; ids on the device)

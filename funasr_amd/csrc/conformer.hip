@@ -54,14 +54,21 @@ __global__ void __launch_bounds__(256) cf_act_kernel(float* x, size_t n4, int mo
     reinterpret_cast<float4*>(x)[i] = v;
 }
 
-__global__ void __launch_bounds__(256) cf_scale_rows_kernel(const float* x, int NE, float* y, int T, int D4, float scale, size_t total) {
+__global__ void __launch_bounds__(256) cf_scale_rows_kernel(const float* x, int NE, float* y, int T, int D4, float scale, const float* pe,
+                                                           size_t total) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     const size_t row = i / D4;
     const int c = (int)(i - row * D4);
     const int b = (int)(row / T), t = (int)(row - (size_t)b * T);
     const float4 v = reinterpret_cast<const float4*>(x)[((size_t)b * NE + t) * D4 + c];
-    reinterpret_cast<float4*>(y)[i] = make_float4(v.x * scale, v.y * scale, v.z * scale, v.w * scale);
+    float4 r = make_float4(v.x * scale, v.y * scale, v.z * scale, v.w * scale);
+    if (pe) {      // PositionalEncoding.forward: the product is rounded, then the table row is added (no fma)
+        const float4 p = reinterpret_cast<const float4*>(pe)[(size_t)t * D4 + c];
+        r = make_float4(__fadd_rn(__fmul_rn(v.x, scale), p.x), __fadd_rn(__fmul_rn(v.y, scale), p.y), __fadd_rn(__fmul_rn(v.z, scale), p.z),
+                        __fadd_rn(__fmul_rn(v.w, scale), p.w));
+    }
+    reinterpret_cast<float4*>(y)[i] = r;
 }
 
 constexpr int DW_TT = 32;      // output rows per workgroup
@@ -166,10 +173,12 @@ int launch_cf_act(float* x, size_t n, int mode, hipStream_t stream) {
     return 0;
 }
 
-int launch_cf_scale_rows(const float* x, int NE, float* y, int B, int T, int D, float scale, hipStream_t stream) {
-    PF_REQUIRE(B > 0 && T > 0 && NE >= T && D % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0, "cf_scale_rows: bad shape");
+int launch_cf_scale_rows(const float* x, int NE, float* y, int B, int T, int D, float scale, const float* pe, hipStream_t stream) {
+    PF_REQUIRE(B > 0 && T > 0 && NE >= T && D > 0 && D % 4 == 0 && x && y && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 &&
+                   ((uintptr_t)pe & 15) == 0,
+               "cf_scale_rows: bad shape");
     const size_t total = (size_t)B * T * (D / 4);
-    hipLaunchKernelGGL(cf_scale_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, x, NE, y, T, D / 4, scale, total);
+    hipLaunchKernelGGL(cf_scale_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, x, NE, y, T, D / 4, scale, pe, total);
     PF_HIP_TRY(hipGetLastError());
     return 0;
 }

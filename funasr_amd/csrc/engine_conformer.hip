@@ -1,5 +1,6 @@
-// C-ABI layer, Conformer ASR: pf_conformer_* (the encoder) and pf_tdecoder_* (the autoregressive Transformer decoder step);
-// kernels in conformer.hip and attention_relpos.hip, GEMMs through the shared launchers.
+// C-ABI layer, Conformer / Transformer ASR: pf_conformer_* and pf_tfencoder_* (the two encoders over one Conv2dSubsampling front)
+// and pf_tdecoder_* (the autoregressive Transformer decoder step); kernels in conformer.hip, attention_relpos.hip and
+// attention_abs.hip, GEMMs through the shared launchers.
 //
 // Encoder forward over the zero-padded batch [B, Tin, F] (the reference runs Conv2dSubsampling and the convolution module over
 // the padded tensor without masking, so every row of the batch is computed and a clip's frames depend on the batch's length):
@@ -29,6 +30,77 @@ namespace {
 
 constexpr int LIN_K_SLICE = 1024;      // K extent of one launch of the subsampling's output linear (a multiple of the GEMM's 32)
 
+// Conv2dSubsampling up to its output linear, shared by the Conformer and the Transformer encoder handles: the buffers, what is
+// derived from the weights at prepare(), and the launches.
+struct CfSub {
+    DevBuf even, odd, ya, yb, lin, lin2;
+    static int F1(int F) { return (F - 3) / 2 + 1; }
+    static int F2(int F) { return (F1(F) - 3) / 2 + 1; }
+    static int prepare(TensorTable& tt, int C, int D, int f2, const char* who);
+    // feats [B, Tin, F] -> *rows: [B, NE = T + 1, D] rows of the output linear (row T of each sequence is waste)
+    int forward(TensorTable& tt, DevBuf& planes, const float* feats, int B, int Tin, int F, int C, int D, const float** rows, hipStream_t s);
+};
+
+int CfSub::prepare(TensorTable& tt, int C, int D, int f2, const char* who) {
+    // conv1 [C, C, 3, 3] -> per time tap dt the [C, 3 C] matrix W_dt[co][df C + ci]
+    std::vector<float> w = tt.host("embed.conv.2.weight");
+    if (w.empty()) { set_error(std::string(who) + ": weight copy failed"); return -2; }
+    for (int dt = 0; dt < 3; ++dt) {
+        std::vector<float> m((size_t)C * 3 * C);
+        for (int co = 0; co < C; ++co)
+            for (int df = 0; df < 3; ++df)
+                for (int ci = 0; ci < C; ++ci) m[((size_t)co * 3 + df) * C + ci] = w[(((size_t)co * C + ci) * 3 + dt) * 3 + df];
+        if (tt.put_derived("#conv1.tap" + std::to_string(dt), m)) return -2;
+    }
+    // output linear [D, C F2] (feature c F2 + f) -> [D, (F2 + 1) C] (feature f C + c, zero for the waste column)
+    std::vector<float> l = tt.host("embed.out.0.weight");
+    std::vector<float> m((size_t)D * (f2 + 1) * C, 0.f);
+    for (int d = 0; d < D; ++d)
+        for (int c = 0; c < C; ++c)
+            for (int f = 0; f < f2; ++f) m[((size_t)d * (f2 + 1) + f) * C + c] = l[((size_t)d * C + c) * f2 + f];
+    return tt.put_derived("#embed.out", m) ? -2 : 0;
+}
+
+int CfSub::forward(TensorTable& tt, DevBuf& planes, const float* feats, int B, int Tin, int F, int C, int D, const float** rows,
+                   hipStream_t s) {
+    const int f1 = F1(F), f2 = F2(F), FP = 2 * (f2 + 1);
+    const int T1 = (Tin - 3) / 2 + 1, T = (T1 - 3) / 2 + 1, NE = T + 1;
+    const size_t Mc = (size_t)B * NE * (f2 + 1), EO = (size_t)B * NE * FP * C, SL = (size_t)2 * FP * C;
+    if (even.ensure(sizeof(float) * (EO + SL)) || odd.ensure(sizeof(float) * (EO + SL)) || ya.ensure(sizeof(float) * Mc * C) ||
+        yb.ensure(sizeof(float) * Mc * C) || lin.ensure(sizeof(float) * (size_t)B * NE * D) || lin2.ensure(sizeof(float) * (size_t)B * NE * D))
+        return -2;
+    int rc;
+    // C[M, N] = A[M, K] (row stride lda = 2 C, K = 3 C: overlapping views) W^T + bias (+ R1); fp32 only
+    auto gm = [&](const float* A, const std::string& w, const float* bias, const float* R1, float* Cc) {
+        return gemm_two_mode(tt, planes, false, A, 3 * C, Mc, 2 * C, (int)Mc, 3 * C, w, C, bias, R1, Cc, C, 0, 0, s);
+    };
+    float *ev = even.as<float>(), *od = odd.as<float>(), *a = ya.as<float>(), *b = yb.as<float>();
+    PF_HIP_TRY(hipMemsetAsync(ev + EO, 0, sizeof(float) * SL, s));
+    PF_HIP_TRY(hipMemsetAsync(od + EO, 0, sizeof(float) * SL, s));
+    if ((rc = launch_cf_conv0(feats, B, Tin, F, tt.get("embed.conv.0.weight"), tt.get("embed.conv.0.bias"), C, T1, f1, NE, FP, ev, od, s)))
+        return rc;
+    if ((rc = gm(ev, "#conv1.tap0", tt.get("embed.conv.2.bias"), nullptr, a))) return rc;
+    if ((rc = gm(od, "#conv1.tap1", nullptr, a, b))) return rc;
+    if ((rc = gm(ev + (size_t)FP * C, "#conv1.tap2", nullptr, b, a))) return rc;
+    if ((rc = launch_cf_act(a, Mc * C, 0, s))) return rc;
+    // The output linear sums (F2 + 1) C terms per element (2560 at 80 features and C = 128, 8192 at 256 features). One fp32 fma chain of
+    // that length drifts several times further from the exact sum than a blocked CPU GEMM does, so K goes in slices of 1024: a
+    // slice's chain starts at zero and the running sum rides in as the addend of the next launch (ping-pong, no in-place addend).
+    float *l = lin.as<float>(), *l_prev = lin2.as<float>();
+    const int Kl = (f2 + 1) * C;
+    for (int k0 = 0; k0 < Kl; k0 += LIN_K_SLICE) {
+        GemmArgs g{};
+        g.A = a + k0; g.lda = Kl; g.W = tt.get("#embed.out") + k0; g.ldw = Kl;
+        g.bias = k0 == 0 ? tt.get("embed.out.0.bias") : nullptr;
+        g.R1 = k0 == 0 ? nullptr : l_prev; g.ldr1 = D;
+        g.C = l; g.ldc = D; g.M = B * NE; g.N = D; g.K = std::min(LIN_K_SLICE, Kl - k0);
+        if ((rc = launch_gemm_f32(g, s))) return rc;
+        std::swap(l, l_prev);
+    }
+    *rows = l_prev;
+    return 0;
+}
+
 struct CfBlockX { int e_ffm_in = 0, e_ffm_h = 0, e_mha_in = 0, e_att = 0, e_conv_in = 0, e_cm = 0, e_ff_in = 0, e_ff_h = 0; };
 
 struct Cf {
@@ -36,11 +108,10 @@ struct Cf {
     TensorTable tt;
     unsigned long long prepared = ~0ull;
     std::vector<CfBlockX> bx;
-    DevBuf even, odd, ya, yb, lin, lin2, xa, xb, xn, qkv, P, att, hid, planes, klens;
+    CfSub sub_;
+    DevBuf xa, xb, xn, qkv, P, att, hid, planes, klens;
 
-    int C() const { return cfg.d_model; }
-    int F1() const { return (cfg.input_dim - 3) / 2 + 1; }
-    int F2() const { return (F1() - 3) / 2 + 1; }
+    int F2() const { return CfSub::F2(cfg.input_dim); }
     int pos_rows() const { return cfg.legacy ? 5000 : 9999; }
     static int sub(int L, int n) { const int m = std::min(L, n - 2); return m <= 0 ? 0 : (m + 1) / 2; }
     // encoder frames of a length-L clip inside a batch padded to n frames (the mask rule x_mask[:, :, :-2:2][:, :, :-2:2])
@@ -54,25 +125,8 @@ struct Cf {
 std::string blk(int i) { return "encoders." + std::to_string(i) + "."; }
 
 int Cf::prepare(hipStream_t s) {
-    const int C = cfg.d_model, D = cfg.d_model, f2 = F2(), NB = cfg.n_blocks, K = cfg.kernel_size, FF = cfg.ffn_dim;
-    {   // conv1 [C, C, 3, 3] -> per time tap dt the [C, 3 C] matrix W_dt[co][df C + ci]
-        std::vector<float> w = tt.host("embed.conv.2.weight");
-        if (w.empty()) { set_error("conformer: weight copy failed"); return -2; }
-        for (int dt = 0; dt < 3; ++dt) {
-            std::vector<float> m((size_t)C * 3 * C);
-            for (int co = 0; co < C; ++co)
-                for (int df = 0; df < 3; ++df)
-                    for (int ci = 0; ci < C; ++ci) m[((size_t)co * 3 + df) * C + ci] = w[(((size_t)co * C + ci) * 3 + dt) * 3 + df];
-            if (tt.put_derived("#conv1.tap" + std::to_string(dt), m)) return -2;
-        }
-        // output linear [D, C F2] (feature c F2 + f) -> [D, (F2 + 1) C] (feature f C + c, zero for the waste column)
-        std::vector<float> l = tt.host("embed.out.0.weight");
-        std::vector<float> m((size_t)D * (f2 + 1) * C, 0.f);
-        for (int d = 0; d < D; ++d)
-            for (int c = 0; c < C; ++c)
-                for (int f = 0; f < f2; ++f) m[((size_t)d * (f2 + 1) + f) * C + c] = l[((size_t)d * C + c) * f2 + f];
-        if (tt.put_derived("#embed.out", m)) return -2;
-    }
+    const int D = cfg.d_model, NB = cfg.n_blocks, K = cfg.kernel_size, FF = cfg.ffn_dim;
+    if (CfSub::prepare(tt, D, D, F2(), "conformer")) return -2;
     std::vector<float> bnv((size_t)NB * 2 * D);
     bx.assign(NB, CfBlockX());
     if (cfg.precision == 3) tt.drop_bf16();
@@ -130,7 +184,7 @@ int Cf::prepare(hipStream_t s) {
 
 int cf_forward(Cf* h, const float* feats, const int32_t* lens, int B, int Tin, float* out, int32_t* olens, hipStream_t s) {
     const pf_conformer_config& c = h->cfg;
-    const int C = c.d_model, D = c.d_model, FF = c.ffn_dim, F = c.input_dim, f1 = h->F1(), f2 = h->F2(), FP = 2 * (f2 + 1);
+    const int D = c.d_model, FF = c.ffn_dim;
     const int T1 = (Tin - 3) / 2 + 1, T = (T1 - 3) / 2 + 1, NE = T + 1;
     const bool x2 = c.precision == 3;
     const float eps = c.ln_eps;
@@ -139,50 +193,24 @@ int cf_forward(Cf* h, const float* feats, const int32_t* lens, int B, int Tin, f
         kl[b] = Cf::out_len(lens[b], Tin);
         if (olens) olens[b] = kl[b];
     }
-    const size_t M = (size_t)B * T, Mc = (size_t)B * NE * (f2 + 1), EO = (size_t)B * NE * FP * C, SL = (size_t)2 * FP * C;
+    const size_t M = (size_t)B * T;
     const int nP = c.legacy ? T : 2 * T - 1;
-    if (h->even.ensure(sizeof(float) * (EO + SL)) || h->odd.ensure(sizeof(float) * (EO + SL)) || h->ya.ensure(sizeof(float) * Mc * C) ||
-        h->yb.ensure(sizeof(float) * Mc * C) || h->lin.ensure(sizeof(float) * (size_t)B * NE * D) ||
-        h->lin2.ensure(sizeof(float) * (size_t)B * NE * D) || h->xa.ensure(sizeof(float) * M * D) ||
-        h->xb.ensure(sizeof(float) * M * D) || h->xn.ensure(sizeof(float) * M * D) || h->qkv.ensure(sizeof(float) * M * 3 * D) ||
-        h->P.ensure(sizeof(float) * (size_t)nP * D) || h->att.ensure(sizeof(float) * M * D) ||
+    if (h->xa.ensure(sizeof(float) * M * D) || h->xb.ensure(sizeof(float) * M * D) || h->xn.ensure(sizeof(float) * M * D) ||
+        h->qkv.ensure(sizeof(float) * M * 3 * D) || h->P.ensure(sizeof(float) * (size_t)nP * D) || h->att.ensure(sizeof(float) * M * D) ||
         h->hid.ensure(sizeof(float) * M * std::max(FF, 2 * D)) || h->klens.ensure(sizeof(int32_t) * B))
         return -2;
     if (upload_h2d(h->klens.p, kl.data(), sizeof(int32_t) * B, s)) return -2;
     int rc;
-    // C[M, N] = A[M, K] (row stride lda) W^T + bias (+ R1); the subsampling's overlapping views (lda = 2 C, K = 3 C) are fp32 only
+    // C[M, N] = A[M, K] (row stride lda) W^T + bias (+ R1)
     auto gm = [&](bool x2_, const float* A, int lda, int M_, int K, const std::string& w, int N, const float* bias, const float* R1, float* Cc,
                   int ldc, int e_a) {
         return gemm_two_mode(h->tt, h->planes, x2_, A, K, (size_t)M_, lda, M_, K, w, N, bias, R1, Cc, ldc, e_a, 0, s);
     };
-    float *even = h->even.as<float>(), *odd = h->odd.as<float>(), *ya = h->ya.as<float>(), *yb = h->yb.as<float>();
-    PF_HIP_TRY(hipMemsetAsync(even + EO, 0, sizeof(float) * SL, s));
-    PF_HIP_TRY(hipMemsetAsync(odd + EO, 0, sizeof(float) * SL, s));
-    if ((rc = launch_cf_conv0(feats, B, Tin, F, h->tt.get("embed.conv.0.weight"), h->tt.get("embed.conv.0.bias"), C, T1, f1, NE, FP, even,
-                              odd, s)))
-        return rc;
-    const float* cb = h->tt.get("embed.conv.2.bias");
-    if ((rc = gm(false, even, 2 * C, (int)Mc, 3 * C, "#conv1.tap0", C, cb, nullptr, ya, C, 0))) return rc;
-    if ((rc = gm(false, odd, 2 * C, (int)Mc, 3 * C, "#conv1.tap1", C, nullptr, ya, yb, C, 0))) return rc;
-    if ((rc = gm(false, even + (size_t)FP * C, 2 * C, (int)Mc, 3 * C, "#conv1.tap2", C, nullptr, yb, ya, C, 0))) return rc;
-    if ((rc = launch_cf_act(ya, Mc * C, 0, s))) return rc;
-    // The output linear sums (F2 + 1) C terms per element (2560 at 80 features and C = 128, 8192 at 256 features). One fp32 fma chain of
-    // that length drifts several times further from the exact sum than a blocked CPU GEMM does, so K goes in slices of 1024: a
-    // slice's chain starts at zero and the running sum rides in as the addend of the next launch (ping-pong, no in-place addend).
-    float *lin = h->lin.as<float>(), *lin_prev = h->lin2.as<float>();
-    const int Kl = (f2 + 1) * C;
-    for (int k0 = 0; k0 < Kl; k0 += LIN_K_SLICE) {
-        GemmArgs g{};
-        g.A = ya + k0; g.lda = Kl; g.W = h->tt.get("#embed.out") + k0; g.ldw = Kl;
-        g.bias = k0 == 0 ? h->tt.get("embed.out.0.bias") : nullptr;
-        g.R1 = k0 == 0 ? nullptr : lin_prev; g.ldr1 = D;
-        g.C = lin; g.ldc = D; g.M = B * NE; g.N = D; g.K = std::min(LIN_K_SLICE, Kl - k0);
-        if ((rc = launch_gemm_f32(g, s))) return rc;
-        std::swap(lin, lin_prev);
-    }
+    const float* lin_prev;
+    if ((rc = h->sub_.forward(h->tt, h->planes, feats, B, Tin, c.input_dim, D, D, &lin_prev, s))) return rc;
     float* x = h->xa.as<float>();
     float* y = h->xb.as<float>();
-    if ((rc = launch_cf_scale_rows(lin_prev, NE, x, B, T, D, sqrtf((float)D), s))) return rc;
+    if ((rc = launch_cf_scale_rows(lin_prev, NE, x, B, T, D, sqrtf((float)D), nullptr, s))) return rc;
     const float* pos = h->tt.get("pos_table") + (c.legacy ? (size_t)0 : (size_t)(5000 - T) * D);
     float *xn = h->xn.as<float>(), *qkv = h->qkv.as<float>(), *Pm = h->P.as<float>(), *att = h->att.as<float>(), *hid = h->hid.as<float>();
     const int Mi = (int)M;
@@ -237,6 +265,97 @@ int cf_forward(Cf* h, const float* feats, const int32_t* lens, int B, int Tin, f
         std::swap(x, y);
     }
     return layernorm(x, D, h->tt.get("after_norm.weight"), h->tt.get("after_norm.bias"), out, D, Mi, D, D, eps, s);
+}
+
+// ================================================================================================ Transformer encoder
+// funasr/models/transformer/encoder.py TransformerEncoder (input_layer conv2d, normalize_before): the shared subsampling ->
+// x sqrt(D) + pe -> blocks: LayerNorm(norm1), q / k / v GEMMs, plain masked attention, linear_out (+ residual) -> LayerNorm(norm2),
+// w_1, ReLU, w_2 (+ residual); after_norm. precision 3: the block GEMMs from two-plane fp16 operands, exponents from a-priori
+// bounds: the LayerNorm bounds for the q / k / v and w_1 operands, the row-L1 bound of linear_v for the attention output (a convex
+// combination of value rows) and the row-L1 bound of w_1 for the hidden rows (ReLU does not enlarge it).
+struct TfBlockX { int e_mha_in = 0, e_att = 0, e_ff_in = 0, e_ff_h = 0; };
+
+struct Tf {
+    pf_tfencoder_config cfg;
+    TensorTable tt;
+    unsigned long long prepared = ~0ull;
+    std::vector<TfBlockX> bx;
+    CfSub sub_;
+    DevBuf xa, xb, xn, qkv, att, hid, planes, klens;
+    int prepare(hipStream_t s);
+};
+
+int Tf::prepare(hipStream_t s) {
+    const int D = cfg.d_model, NB = cfg.n_blocks, FF = cfg.ffn_dim;
+    if (CfSub::prepare(tt, D, D, CfSub::F2(cfg.input_dim), "tfencoder")) return -2;
+    bx.assign(NB, TfBlockX());
+    if (cfg.precision == 3) tt.drop_bf16();
+    for (int i = 0; i < NB && cfg.precision == 3; ++i) {
+        const std::string p = blk(i);
+        TfBlockX& x = bx[i];
+        float nb, hb;
+        if (TensorTable::dev_ln_bound(tt.get(p + "norm1.weight"), tt.get(p + "norm1.bias"), D, &nb, s)) return -2;
+        x.e_mha_in = exp_for_bound(nb);
+        if (TensorTable::dev_linear_bound(tt.get(p + "self_attn.linear_v.weight"), D, D, D, tt.get(p + "self_attn.linear_v.bias"), nb, &hb, s))
+            return -2;
+        x.e_att = exp_for_bound(hb);
+        if (TensorTable::dev_ln_bound(tt.get(p + "norm2.weight"), tt.get(p + "norm2.bias"), D, &nb, s)) return -2;
+        x.e_ff_in = exp_for_bound(nb);
+        if (TensorTable::dev_linear_bound(tt.get(p + "feed_forward.w_1.weight"), FF, D, D, tt.get(p + "feed_forward.w_1.bias"), nb, &hb, s))
+            return -2;
+        x.e_ff_h = exp_for_bound(hb);
+    }
+    prepared = tt.version;
+    return 0;
+}
+
+int tf_forward(Tf* h, const float* feats, const int32_t* lens, int B, int Tin, float* out, int32_t* olens, hipStream_t s) {
+    const pf_tfencoder_config& c = h->cfg;
+    const int D = c.d_model, FF = c.ffn_dim;
+    const int T1 = (Tin - 3) / 2 + 1, T = (T1 - 3) / 2 + 1, NE = T + 1;
+    const bool x2 = c.precision == 3;
+    std::vector<int32_t> kl(B);
+    for (int b = 0; b < B; ++b) {
+        kl[b] = Cf::out_len(lens[b], Tin);
+        if (olens) olens[b] = kl[b];
+    }
+    const size_t M = (size_t)B * T;
+    if (h->xa.ensure(sizeof(float) * M * D) || h->xb.ensure(sizeof(float) * M * D) || h->xn.ensure(sizeof(float) * M * D) ||
+        h->qkv.ensure(sizeof(float) * M * 3 * D) || h->att.ensure(sizeof(float) * M * D) || h->hid.ensure(sizeof(float) * M * FF) ||
+        h->klens.ensure(sizeof(int32_t) * B))
+        return -2;
+    if (upload_h2d(h->klens.p, kl.data(), sizeof(int32_t) * B, s)) return -2;
+    int rc;
+    const float* rows;
+    if ((rc = h->sub_.forward(h->tt, h->planes, feats, B, Tin, c.input_dim, D, D, &rows, s))) return rc;
+    float *x = h->xa.as<float>(), *y = h->xb.as<float>(), *xn = h->xn.as<float>(), *qkv = h->qkv.as<float>(), *att = h->att.as<float>(),
+          *hid = h->hid.as<float>();
+    if ((rc = launch_cf_scale_rows(rows, NE, x, B, T, D, sqrtf((float)D), h->tt.get("pos_table"), s))) return rc;
+    const int Mi = (int)M;
+    // C[M, N] = A[M, K] W^T + bias (+ R1)
+    auto gm = [&](const float* A, int K, const std::string& w, int N, const float* R1, float* Cc, int ldc, int e_a) {
+        return gemm_two_mode(h->tt, h->planes, x2, A, K, M, K, Mi, K, w + "weight", N, h->tt.get(w + "bias"), R1, Cc, ldc, e_a, 0, s);
+    };
+    auto ln = [&](const std::string& p, const float* in, float* o) {
+        return layernorm(in, D, h->tt.get(p + "weight"), h->tt.get(p + "bias"), o, D, Mi, D, D, c.ln_eps, s);
+    };
+    for (int i = 0; i < c.n_blocks; ++i) {
+        const std::string p = blk(i);
+        const TfBlockX& e = h->bx[i];
+        if ((rc = ln(p + "norm1.", x, xn))) return rc;
+        const char* names[3] = {"self_attn.linear_q.", "self_attn.linear_k.", "self_attn.linear_v."};
+        for (int j = 0; j < 3; ++j)
+            if ((rc = gm(xn, D, p + names[j], D, nullptr, qkv + (size_t)j * D, 3 * D, e.e_mha_in))) return rc;
+        if ((rc = launch_tf_attention(qkv, h->klens.as<int>(), B, T, c.n_heads, att, s))) return rc;
+        if ((rc = gm(att, D, p + "self_attn.linear_out.", D, x, y, D, e.e_att))) return rc;
+        std::swap(x, y);
+        if ((rc = ln(p + "norm2.", x, xn))) return rc;
+        if ((rc = gm(xn, D, p + "feed_forward.w_1.", FF, nullptr, hid, FF, e.e_ff_in))) return rc;
+        if ((rc = launch_cf_act(hid, M * FF, 0, s))) return rc;
+        if ((rc = gm(hid, FF, p + "feed_forward.w_2.", D, x, y, D, e.e_ff_h))) return rc;
+        std::swap(x, y);
+    }
+    return ln("after_norm.", x, out);
 }
 
 // ================================================================================================ decoder
@@ -342,6 +461,75 @@ int pf_conformer_forward(pf_conformer* hh, const float* feats, const int32_t* le
     if ((rc = h->tt.require_all("conformer"))) return rc;
     if (h->prepared != h->tt.version && (rc = h->prepare(s))) return rc;
     return cf_forward(h, feats, lens_host, B, Tin, out, out_lens_host, s);
+}
+
+pf_tfencoder* pf_tfencoder_create(const pf_tfencoder_config* cfg) {
+    if (!cfg) { set_error("tfencoder: null config"); return nullptr; }
+    if (check_device()) return nullptr;
+    const pf_tfencoder_config& c = *cfg;
+    const bool ok = c.input_dim >= 7 && c.input_dim <= 256 && c.d_model > 0 && c.d_model % 64 == 0 && c.d_model <= 2048 &&
+                    c.n_heads > 0 && c.d_model == 64 * c.n_heads && c.ffn_dim > 0 && c.ffn_dim % 32 == 0 && c.n_blocks >= 0 &&
+                    (c.precision == 0 || c.precision == 3) && c.ln_eps > 0.f;
+    if (!ok) {
+        set_error("tfencoder: unsupported config (7 .. 256 input features, head dim 64, d_model % 64, ffn_dim % 32, precision 0 or 3)");
+        return nullptr;
+    }
+    std::unique_ptr<Tf> h(new Tf());
+    h->cfg = c;
+    const int D = c.d_model, FF = c.ffn_dim;
+    int rc = 0;
+    auto lin = [&](const std::string& n, int o, int i) {
+        rc |= h->tt.add(n + "weight", (int64_t)o * i);
+        rc |= h->tt.add(n + "bias", o);
+    };
+    lin("embed.conv.0.", D, 9);
+    lin("embed.conv.2.", D, D * 9);
+    lin("embed.out.0.", D, D * CfSub::F2(c.input_dim));
+    rc |= h->tt.add("pos_table", (int64_t)5000 * D);
+    for (int i = 0; i < c.n_blocks; ++i) {
+        const std::string p = blk(i);
+        for (const char* n : {"linear_q.", "linear_k.", "linear_v.", "linear_out."}) lin(p + "self_attn." + n, D, D);
+        lin(p + "feed_forward.w_1.", FF, D);
+        lin(p + "feed_forward.w_2.", D, FF);
+        for (const char* n : {"norm1.", "norm2."}) lin(p + n, D, 1);
+    }
+    lin("after_norm.", D, 1);
+    if (rc) return nullptr;
+    return reinterpret_cast<pf_tfencoder*>(h.release());
+}
+void pf_tfencoder_destroy(pf_tfencoder* h) { delete reinterpret_cast<Tf*>(h); }
+int pf_tfencoder_set_tensor(pf_tfencoder* hh, const char* name, const float* data, int64_t numel) {
+    Tf* h = reinterpret_cast<Tf*>(hh);
+    PF_REQUIRE(h && name && data, "tfencoder_set_tensor: null");
+    return h->tt.set(name, data, numel);
+}
+int pf_tfencoder_missing(const pf_tfencoder* hh) {
+    const Tf* h = reinterpret_cast<const Tf*>(hh);
+    return h ? h->tt.missing() : -1;
+}
+int pf_tfencoder_set_precision(pf_tfencoder* hh, int32_t precision) {
+    Tf* h = reinterpret_cast<Tf*>(hh);
+    PF_REQUIRE(h && (precision == 0 || precision == 3), "tfencoder_set_precision: 0 (fp32) or 3 (f16x2)");
+    if (h->cfg.precision != precision) { h->cfg.precision = precision; h->prepared = ~0ull; }
+    return 0;
+}
+int32_t pf_tfencoder_num_frames(const pf_tfencoder* hh, int32_t n_frames, int32_t padded_frames) {
+    if (!hh || padded_frames < 7 || n_frames > padded_frames) return -1;
+    return Cf::out_len(n_frames, padded_frames);
+}
+int pf_tfencoder_forward(pf_tfencoder* hh, const float* feats, const int32_t* lens_host, int32_t B, int32_t Tin, float* out,
+                         int32_t* out_lens_host, void* stream) {
+    Tf* h = reinterpret_cast<Tf*>(hh);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    PF_REQUIRE(h && feats && lens_host && out && B > 0, "tfencoder_forward: null/empty argument");
+    if (Tin < 7) { set_error("tfencoder: has " + std::to_string(Tin) + " frames and is too short for subsampling (it needs more than 7 frames)"); return -1; }
+    for (int b = 0; b < B; ++b) PF_REQUIRE(lens_host[b] >= 0 && lens_host[b] <= Tin, "tfencoder_forward: a length exceeds the padded length");
+    const int T = Cf::out_len(Tin, Tin);
+    if (T > 5000) { set_error("tfencoder: " + std::to_string(T) + " encoder frames; the positional table holds 5000 (200 s)"); return -1; }
+    int rc;
+    if ((rc = h->tt.require_all("tfencoder"))) return rc;
+    if (h->prepared != h->tt.version && (rc = h->prepare(s))) return rc;
+    return tf_forward(h, feats, lens_host, B, Tin, out, out_lens_host, s);
 }
 
 pf_tdecoder* pf_tdecoder_create(const pf_tdecoder_config* cfg) {
@@ -497,7 +685,13 @@ int pf_k_relpos_attention(const float* qkv, const float* P, const float* u, cons
                           int32_t H, int32_t legacy, float* out, void* stream) {
     return launch_cf_relpos_attention(qkv, P, u, v, klens_dev, B, T, H, legacy, out, reinterpret_cast<hipStream_t>(stream));
 }
-int pf_k_conformer_glu_dw(const float* g, const float* dw, const float* dw_bias, const float* bn_scale, const float* bn_shift, int32_t B,
+int pf_k_tf_attention(const float* qkv, const int32_t* klens_dev, int32_t B, int32_t T, int32_t H, float* out, void* stream) {
+    return launch_tf_attention(qkv, klens_dev, B, T, H, out, reinterpret_cast<hipStream_t>(stream));
+}
+int pf_k_tf_embed_rows(const float* x, int32_t NE, const float* pe, int32_t B, int32_t T, int32_t D, float scale, float* y, void* stream) {
+    return launch_cf_scale_rows(x, NE, y, B, T, D, scale, pe, reinterpret_cast<hipStream_t>(stream));
+}
+int pf_k_conformer_glu_dw(const float* g,const float* dw, const float* dw_bias, const float* bn_scale, const float* bn_shift, int32_t B,
                           int32_t T, int32_t D, int32_t taps, float* y, void* stream) {
     return launch_cf_glu_dw(g, dw, dw_bias, bn_scale, bn_shift, B, T, D, taps, y, reinterpret_cast<hipStream_t>(stream));
 }

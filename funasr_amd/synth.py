@@ -387,6 +387,26 @@ CONFORMER_AISHELL = dict(output_size=256, attention_heads=4, linear_units=2048, 
                          rel_pos_type="legacy", vocab=4234)
 
 
+def transformer_conf(output_size: int = 128, attention_heads: int = 2, linear_units: int = 256, enc_blocks: int = 2, dec_blocks: int = 2,
+                     vocab: int = 60, input_size: int = 80) -> dict:
+    """constructor arguments of a Transformer model (the layout of examples/aishell/transformer/conf/*.yaml) at a chosen size"""
+    enc = {"output_size": output_size, "attention_heads": attention_heads, "linear_units": linear_units, "num_blocks": enc_blocks,
+           "dropout_rate": 0.1, "positional_dropout_rate": 0.1, "attention_dropout_rate": 0.0, "input_layer": "conv2d",
+           "normalize_before": True}
+    dec = {"attention_heads": attention_heads, "linear_units": linear_units, "num_blocks": dec_blocks, "dropout_rate": 0.1,
+           "positional_dropout_rate": 0.1, "self_attention_dropout_rate": 0.0, "src_attention_dropout_rate": 0.0}
+    return {"encoder": "TransformerEncoder", "encoder_conf": enc, "decoder": "TransformerDecoder", "decoder_conf": dec,
+            "ctc_weight": 0.3, "lsm_weight": 0.1, "length_normalized_loss": False, "input_size": input_size, "vocab_size": vocab}
+
+
+TRANSFORMER_AISHELL = dict(output_size=256, attention_heads=4, linear_units=2048, enc_blocks=12, dec_blocks=6, vocab=4234)
+
+
+def transformer_state_dict(seed: int, model) -> Dict[str, torch.Tensor]:
+    """synthetic weights in the layout of `model` (a Transformer module or the reference's), drawn as conformer_state_dict draws them"""
+    return conformer_state_dict(seed, model)
+
+
 def conformer_state_dict(seed: int, model) -> Dict[str, torch.Tensor]:
     """synthetic weights in the layout of `model` (a Conformer module or the reference's): fan-in scaled convs / linears, LayerNorms
     near identity, NON-trivial BatchNorm statistics (weight near 1, bias / running_mean off zero, running_var in [0.5, 2]),

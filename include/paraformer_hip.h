@@ -488,6 +488,29 @@ int32_t pf_conformer_num_frames(const pf_conformer* h, int32_t n_frames, int32_t
 int pf_conformer_forward(pf_conformer* h, const float* feats_dev, const int32_t* lens_host, int32_t B, int32_t Tin, float* out_dev,
                          int32_t* out_lens_host, void* stream);
 
+/* ---- Transformer encoder (funasr/models/transformer/encoder.py TransformerEncoder: Conv2dSubsampling, x sqrt(D) + the absolute
+ * sinusoid, pre-LayerNorm blocks of plain masked self-attention (MultiHeadedAttention, head dim 64) and a ReLU feed-forward).
+ * Tensor names are the reference's keys below `encoder.`: "embed.conv.0.weight", "embed.out.0.weight",
+ * "encoders.0.self_attn.linear_q.weight", "encoders.0.feed_forward.w_1.bias", "encoders.0.norm1.weight", "after_norm.bias", ...
+ * plus "pos_table" [5000, D] (row p = the sinusoid of position p, built on the host as the reference does).
+ * Shapes, lengths and precisions are pf_conformer's: the ZERO-PADDED batch in, every row computed, lengths by the mask rule;
+ * precision 3 runs the block GEMMs on the fp16 MFMA with two-plane operands, the subsampling GEMMs and the attention stay fp32. */
+typedef struct pf_tfencoder pf_tfencoder;
+typedef struct pf_tfencoder_config {
+    int32_t input_dim, d_model, n_heads, ffn_dim, n_blocks;
+    int32_t precision;            /* 0 fp32, 3 f16x2 */
+    float ln_eps;
+} pf_tfencoder_config;
+pf_tfencoder* pf_tfencoder_create(const pf_tfencoder_config* cfg);
+void pf_tfencoder_destroy(pf_tfencoder* h);
+int pf_tfencoder_set_tensor(pf_tfencoder* h, const char* name, const float* data, int64_t numel);
+int pf_tfencoder_missing(const pf_tfencoder* h);
+int pf_tfencoder_set_precision(pf_tfencoder* h, int32_t precision);
+int32_t pf_tfencoder_num_frames(const pf_tfencoder* h, int32_t n_frames, int32_t padded_frames);
+/* as pf_conformer_forward. Fails when Tin < 7 or T > 5000. No sync. */
+int pf_tfencoder_forward(pf_tfencoder* h, const float* feats_dev, const int32_t* lens_host, int32_t B, int32_t Tin, float* out_dev,
+                         int32_t* out_lens_host, void* stream);
+
 /* ---- Transformer decoder, one autoregressive step for all running hypotheses of a beam (funasr/models/transformer/decoder.py
  * TransformerDecoder.forward_one_step / batch_score: embed x sqrt(D) + sinusoid, pre-LN self-attention over the hypothesis' own
  * prefix, cross-attention over the utterance's encoder memory, ReLU feed-forward, after_norm, output layer, log-softmax; head dim 64).
@@ -519,6 +542,12 @@ int pf_k_relpos_attention(const float* qkv_dev, const float* P_dev, const float*
                           int32_t T, int32_t H, int32_t legacy, float* out_dev, void* stream);
 int pf_k_conformer_glu_dw(const float* g_dev, const float* dw_dev, const float* dw_bias_dev, const float* bn_scale_dev,
                           const float* bn_shift_dev, int32_t B, int32_t T, int32_t D, int32_t taps, float* y_dev, void* stream);
+/* single-kernel hooks of the Transformer encoder (tests): the plain masked attention (qkv_dev [B T, 3 D] q | k | v, klens_dev [B]
+ * -> out_dev [B T, D]; keys >= klens_dev[b] masked, no row at or past them read) and the embedding rows
+ * y[b T + t] = x[b NE + t] * scale + pe[t] for t < T <= NE (pe_dev [>= T, D] or NULL: the scale alone) */
+int pf_k_tf_attention(const float* qkv_dev, const int32_t* klens_dev, int32_t B, int32_t T, int32_t H, float* out_dev, void* stream);
+int pf_k_tf_embed_rows(const float* x_dev, int32_t NE, const float* pe_dev, int32_t B, int32_t T, int32_t D, float scale, float* y_dev,
+                       void* stream);
 
 typedef struct pf_ctc pf_ctc;
 pf_ctc* pf_ctc_create(int32_t d_model, int32_t vocab_size);
