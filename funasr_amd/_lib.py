@@ -99,6 +99,10 @@ class pf_tfencoder_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("input_dim", "d_model", "n_heads", "ffn_dim", "n_blocks", "precision")] + [("ln_eps", C.c_float)]
 
 
+class pf_transducer_config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("vocab", "enc_dim", "embed_dim", "hidden", "n_layers", "joint_dim", "blank_id")]
+
+
 class pf_tdecoder_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("vocab_size", "d_model", "n_heads", "ffn_dim", "n_blocks")] + [("ln_eps", C.c_float)]
 
@@ -107,6 +111,8 @@ class pf_stream_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_streams", "chunk_left", "chunk_cur", "chunk_right", "enc_look_back",
                                           "dec_look_back", "max_frames", "max_tokens", "use_graph")]
 
+
+TRANSDUCER_NONFINITE, TRANSDUCER_CAP = 2, 3      # PF_TRANSDUCER_* of pf_transducer_search
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 _pi32 = C.POINTER(C.c_int32)
@@ -216,6 +222,16 @@ SIGNATURES = {
     "pf_tdecoder_reorder": (C.c_int, [_vp, _pi32, _i32, _vp]),
     "pf_k_relpos_attention": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "pf_k_conformer_glu_dw": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "pf_transducer_create": (_vp, [C.POINTER(pf_transducer_config)]),
+    "pf_transducer_destroy": (None, [_vp]),
+    "pf_transducer_set_weights": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),
+    "pf_transducer_missing": (C.c_int, [_vp]),
+    "pf_transducer_last_error": (C.c_char_p, [_vp]),
+    "pf_transducer_search": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _pi32, _pi32, C.POINTER(C.c_double), _i32, _pi32,
+                                       C.POINTER(C.c_int64), _vp]),
+    "pf_k_rnnt_pred_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "pf_k_rnnt_joint_partial_floats": (_i64, [_i32, _i32]),
+    "pf_k_rnnt_joint_topk": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "pf_ctc_create": (_vp, [_i32, _i32]),
     "pf_ctc_destroy": (None, [_vp]),
     "pf_ctc_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),

@@ -44,6 +44,7 @@ import torch
 from . import bicif_paraformer as _bicif_paraformer  # noqa: F401  (registers BiCifParaformer / CifPredictorV3)
 from . import conformer as _conformer  # noqa: F401  (registers Conformer / ConformerEncoder / TransformerDecoder)
 from . import transformer as _transformer  # noqa: F401  (registers Transformer / TransformerEncoder)
+from . import transducer as _transducer  # noqa: F401  (registers Transducer / rnnt_decoder / joint_network)
 from . import contextual_paraformer as _contextual_paraformer  # noqa: F401  (registers ContextualParaformer + its decoder)
 from . import ct_transformer as _ct_transformer  # noqa: F401  (registers CTTransformer)
 from . import emotion2vec as _emotion2vec  # noqa: F401  (registers Emotion2vec)
@@ -327,6 +328,8 @@ class AutoModel:
         # model (:636-646)
         name = kwargs.get("model")
         model_class = tables.model_classes.get(name)
+        if model_class is None and name == "BAT":
+            raise NotImplementedError("model: BAT is not built (its boundary-aware predictor and search are not; model: Transducer is)")
         if model_class is None:
             raise KeyError(f"model class {name!r} is not registered in model_classes: {sorted(tables.model_classes)}")
         model_conf = dict(kwargs.get("model_conf") or {})

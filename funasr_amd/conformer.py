@@ -328,7 +328,42 @@ class TransformerDecoder(HipModule):
             torch.cuda.current_stream(self._handle_device).synchronize()
 
 
-class AttentionEncoderDecoder(nn.Module):
+class PaddedBatchFront:
+    """the head every model over a `Conv2dSubsampledEncoder` shares (a mix-in of nn.Module classes that hold `encoder` and
+    `normalize`): features of the ZERO-padded batch, (normalisation +) encoder, the lazily made result writer. Used by
+    `AttentionEncoderDecoder` below and by funasr_amd.transducer.Transducer."""
+
+    def encode(self, speech: torch.Tensor, speech_lengths, **kwargs):
+        """transformer/model.py:288-325: (normalisation +) encoder over the padded batch -> (encoder_out [B, T, D], lengths)"""
+        if self.normalize is not None:
+            dev = self.encoder._device()
+            speech, speech_lengths = self.normalize(speech.to(device=dev, dtype=torch.float32).contiguous(), speech_lengths)
+        out, olens, _ = self.encoder(speech, speech_lengths)
+        return out, olens
+
+    def _features(self, data_in, data_lengths, frontend, kwargs):
+        from .audio import batch_to_features
+
+        speech, speech_lengths, meta = batch_to_features(data_in, data_lengths, frontend, kwargs)
+        lens = [int(v) for v in (speech_lengths.tolist() if isinstance(speech_lengths, torch.Tensor) else
+                                 ([speech_lengths] if isinstance(speech_lengths, int) else speech_lengths))]
+        speech = speech.to(dtype=torch.float32)
+        if any(n < speech.shape[1] for n in lens):                    # the contract is the ZERO-padded batch
+            speech = speech.clone()
+            for b, n in enumerate(lens):
+                speech[b, n:] = 0
+        return speech, lens, meta
+
+    def _writer(self, kwargs, name):
+        if kwargs.get("output_dir") is None:
+            return None
+        if not hasattr(self, "writer"):
+            from .datadir_writer import DatadirWriter
+            self.writer = DatadirWriter(kwargs.get("output_dir"))
+        return self.writer[name]
+
+
+class AttentionEncoderDecoder(PaddedBatchFront, nn.Module):
     """funasr/models/transformer/model.py Transformer, the CTC / attention encoder-decoder the reference's `Conformer` subclasses
     with nothing added: everything but the encoder. A model class names the one encoder it accepts (`_encoder`) and what its
     refusal of another says (`_other_encoders`); funasr_amd.transformer.Transformer is the other one."""
@@ -388,14 +423,6 @@ class AttentionEncoderDecoder(nn.Module):
         return self
 
     # ------------------------------------------------------------------------------------------------ device pipeline
-    def encode(self, speech: torch.Tensor, speech_lengths, **kwargs):
-        """transformer/model.py:288-325: (normalisation +) encoder over the padded batch -> (encoder_out [B, T, D], lengths)"""
-        if self.normalize is not None:
-            dev = self.encoder._device()
-            speech, speech_lengths = self.normalize(speech.to(device=dev, dtype=torch.float32).contiguous(), speech_lengths)
-        out, olens, _ = self.encoder(speech, speech_lengths)
-        return out, olens
-
     def ctc_greedy(self, encoder_out: torch.Tensor, olens) -> List[List[int]]:
         """arg-max of the CTC head over each clip's valid frames, repeats collapsed, blanks dropped (model.py:442-447)"""
         ids = self.ctc.argmax(encoder_out).cpu()
@@ -428,27 +455,6 @@ class AttentionEncoderDecoder(nn.Module):
         return self.beam_search(self.decoder, int(encoder_out.shape[0]), ctc_logp, maxlenratio, minlenratio)
 
     # ------------------------------------------------------------------------------------------------ inference
-    def _features(self, data_in, data_lengths, frontend, kwargs):
-        from .audio import batch_to_features
-
-        speech, speech_lengths, meta = batch_to_features(data_in, data_lengths, frontend, kwargs)
-        lens = [int(v) for v in (speech_lengths.tolist() if isinstance(speech_lengths, torch.Tensor) else
-                                 ([speech_lengths] if isinstance(speech_lengths, int) else speech_lengths))]
-        speech = speech.to(dtype=torch.float32)
-        if any(n < speech.shape[1] for n in lens):                    # the contract is the ZERO-padded batch
-            speech = speech.clone()
-            for b, n in enumerate(lens):
-                speech[b, n:] = 0
-        return speech, lens, meta
-
-    def _writer(self, kwargs, name):
-        if kwargs.get("output_dir") is None:
-            return None
-        if not hasattr(self, "writer"):
-            from .datadir_writer import DatadirWriter
-            self.writer = DatadirWriter(kwargs.get("output_dir"))
-        return self.writer[name]
-
     def inference_batch_ctc(self, data_in, data_lengths=None, key: list = None, tokenizer=None, frontend=None, **kwargs):
         """transformer/model.py:390-462"""
         from .tokenizer import sentence_postprocess

@@ -109,7 +109,7 @@ class HipModule(nn.Module):
         return ()
 
     def _push_weights(self, lib):
-        set_tensor = getattr(lib, self._prefix + "_set_tensor")
+        set_tensor = getattr(lib, getattr(self, "_set_tensor_name", None) or self._prefix + "_set_tensor")
         named = list(self.named_parameters())
         if self._push_buffers:
             named += [(n, b) for n, b in self.named_buffers() if not n.endswith("num_batches_tracked")]

@@ -436,3 +436,91 @@ def conformer_state_dict(seed: int, model) -> Dict[str, torch.Tensor]:
                 fan_in *= d
             sd[k] = torch.randn(shp, generator=g) * (1.0 / fan_in) ** 0.5
     return sd
+
+
+def transducer_conf(encoder: str = "ConformerEncoder", output_size: int = 128, attention_heads: int = 2, linear_units: int = 256,
+                    enc_blocks: int = 2, embed_size: int = 48, hidden_size: int = 64, num_layers: int = 2, joint_space_size: int = 96,
+                    vocab: int = 61, input_size: int = 80) -> dict:
+    """constructor arguments of a Transducer model (the layout of funasr/models/rwkv_bat/template.yaml's prediction and joint
+    networks over one of the two built encoders) at a chosen size"""
+    enc = (conformer_conf if encoder == "ConformerEncoder" else transformer_conf)(
+        output_size=output_size, attention_heads=attention_heads, linear_units=linear_units, enc_blocks=enc_blocks)["encoder_conf"]
+    return {"encoder": encoder, "encoder_conf": enc, "decoder": "rnnt_decoder",
+            "decoder_conf": {"embed_size": embed_size, "hidden_size": hidden_size, "num_layers": num_layers, "embed_dropout_rate": 0.1,
+                             "dropout_rate": 0.1, "use_embed_mask": False},
+            "joint_network": "joint_network", "joint_network_conf": {"joint_space_size": joint_space_size},
+            "auxiliary_ctc_weight": 0.0, "input_size": input_size, "vocab_size": vocab}
+
+
+TRANSDUCER_TEMPLATE = dict(embed_size=512, hidden_size=512, num_layers=1, joint_space_size=512, vocab=4234)
+
+
+def transducer_state_dict(seed: int, model, n_planted: int = 10, threshold: float = 0.7) -> Dict[str, torch.Tensor]:
+    """synthetic weights in the layout of `model` (a Transducer module or the reference's). The encoder is drawn as
+    conformer_state_dict draws it. Plain random search networks do not make a search that SETTLES (an output layer that rarely
+    prefers blank expands without end), so the tokens are planted over a random background:
+      * background: an embedding of order 1, LSTMs with a strong input and a weak recurrent part, small `lin_enc` / `lin_dec`, an
+        output layer with logit noise of order 1 over a STAIRCASE of biases: blank at +3, the unplanted labels in a random order at
+        -2, -5, -8, ... (3 apart, level at -26 from rank 8 on). Blank takes ~ 99 %, and neither the rank k / k + 1 boundary of the
+        label scores nor two copies of one hypothesis made at different frames come close to a tie;
+      * planted label i < n_planted owns joint dimension i, embedding dimension i and hidden unit i of every LSTM layer.
+        `lin_enc` row i is a random direction of gain 3 with bias -3 threshold: tanh is ~ +1 on the few frames whose projection
+        exceeds `threshold` sigma by ~ 0.6 and ~ -1 elsewhere; `lin_out` maps +1 to a logit of blank + 5 and -1 to -28 (magnitudes stay small: float32 resolves a log-probability of 30 to 2e-6);
+      * hidden unit i passes "the LAST label is label i" up the stack (input and output gates open, forget gate shut, the cell input
+        reads dimension i only): ~ 0.74 then, ~ 0 otherwise, whatever came before. `lin_dec` row i turns it into -12, so a label is
+        not emitted twice in a row and the frame falls back to blank."""
+    sd = conformer_state_dict(seed, model)
+    g = torch.Generator().manual_seed(seed + 7919)
+    gains = {"weight_ih_l0": 2.0, "weight_hh_l0": 0.5, "joint_network.lin_enc.weight": 0.5, "joint_network.lin_dec.weight": 0.5,
+             "joint_network.lin_out.weight": 1.5}
+    for k, v in model.state_dict().items():
+        if not (k.startswith("decoder.") or k.startswith("joint_network.")):
+            continue
+        shp = tuple(v.shape)
+        if k == "decoder.embed.weight":
+            sd[k] = torch.randn(shp, generator=g)
+        elif len(shp) == 1:
+            sd[k] = 0.1 * torch.randn(shp, generator=g)
+        else:
+            gain = [x for n, x in gains.items() if k.endswith(n)][0]
+            sd[k] = torch.randn(shp, generator=g) * gain * (1.0 / shp[1]) ** 0.5
+    V, J = sd["joint_network.lin_out.weight"].shape
+    D = sd["joint_network.lin_enc.weight"].shape[1]
+    E = sd["decoder.embed.weight"].shape[1]
+    H = sd["decoder.rnn.0.weight_hh_l0"].shape[1]
+    P = min(n_planted, V - 3, J // 2 - 1, E // 2, H // 2)
+    blank, off = 4.0, -19.0
+    labels = (3 + torch.randperm(V - 3, generator=g)[:P]).tolist()
+    others = [v for v in range(1, V) if v not in set(labels)]
+    rank = torch.randperm(len(others), generator=g).tolist()
+    sd["joint_network.lin_out.bias"][0] += blank
+    for v, r in zip(others, rank):
+        sd["joint_network.lin_out.bias"][v] += -2.0 - 2.4 * min(r, 5) - (5.0 if r > 5 else 0.0)
+    # joint dimension P: a frame-dependent level shared by all unplanted labels (two copies of a hypothesis made at different frames
+    # then differ by units, not by the noise alone); it moves no rank among them
+    sd["joint_network.lin_enc.weight"][P] = 1.5 * torch.randn(D, generator=g) * (1.0 / D) ** 0.5
+    sd["joint_network.lin_enc.bias"][P] = 0.0
+    sd["joint_network.lin_dec.weight"][P] = 0.0
+    sd["joint_network.lin_out.weight"][:, P] = 0.0
+    sd["joint_network.lin_out.weight"][others, P] = 3.0
+    sd["decoder.embed.weight"][:, :P] = 0.0
+    layers = 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("decoder.rnn."))
+    for i, v in enumerate(labels):
+        sd["decoder.embed.weight"][v, i] = 3.0
+        for l in range(layers):
+            p = f"decoder.rnn.{l}."
+            for gate, bias in enumerate((4.0, -4.0, 0.0, 4.0)):                             # i, f, g, o
+                row = gate * H + i
+                sd[p + "weight_ih_l0"][row] = 0.0
+                sd[p + "weight_hh_l0"][row] = 0.0
+                sd[p + "bias_ih_l0"][row] = bias
+                sd[p + "bias_hh_l0"][row] = 0.0
+            sd[p + "weight_ih_l0"][2 * H + i, i] = 4.0
+        sd["joint_network.lin_enc.weight"][i] = 3.0 * torch.randn(D, generator=g) * (1.0 / D) ** 0.5
+        sd["joint_network.lin_enc.bias"][i] = -3.0 * threshold
+        sd["joint_network.lin_dec.weight"][i] = 0.0
+        sd["joint_network.lin_dec.weight"][i, i] = -12.0 / 0.74
+        sd["joint_network.lin_out.weight"][:, i] = 0.0
+        sd["joint_network.lin_out.weight"][v, i] = (blank + 5.0 - off) / 2
+        sd["joint_network.lin_out.bias"][v] += (blank + 5.0 + off) / 2
+    return sd

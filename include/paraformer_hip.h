@@ -549,6 +549,51 @@ int pf_k_tf_attention(const float* qkv_dev, const int32_t* klens_dev, int32_t B,
 int pf_k_tf_embed_rows(const float* x_dev, int32_t NE, const float* pe_dev, int32_t B, int32_t T, int32_t D, float scale, float* y_dev,
                        void* stream);
 
+/* ---- Transducer (RNN-T) search (funasr/models/transducer: RNNTDecoder + JointNetwork + BeamSearchTransducer.default_beam_search,
+ * the one decoding path the reference's Transducer builds: one utterance, is_final, no LM, no length normalisation). One handle
+ * holds the prediction network (embedding, n_layers LSTM cells) and the joint network; the search loop runs on the host side of the
+ * library: a prediction step (one launch per layer + lin_dec) only for a label prefix not seen in this utterance, two launches per
+ * joint evaluation, one small read-back. All of it exact fp32 on the VALU; scores accumulate in double on the host.
+ * Tensor names are the reference's keys: "decoder.embed.weight" [vocab, embed_dim], "decoder.rnn.<l>.weight_ih_l0" [4 hidden, in],
+ * "decoder.rnn.<l>.weight_hh_l0" [4 hidden, hidden], "decoder.rnn.<l>.bias_ih_l0" / "bias_hh_l0" [4 hidden] (gates i, f, g, o),
+ * "joint_network.lin_enc.weight" [joint_dim, enc_dim] / ".bias", "joint_network.lin_dec.weight" [joint_dim, hidden],
+ * "joint_network.lin_out.weight" [vocab, joint_dim] / ".bias".
+ * Limits: vocab >= 2, blank_id 0, embed_dim / hidden / joint_dim multiples of 4 and <= 1024, enc_dim a multiple of 32 (the K step of
+ * the fp32 GEMM that projects the frames) and <= 1024, 1 <= n_layers <= 4, beam <= 16. */
+typedef struct pf_transducer pf_transducer;
+typedef struct pf_transducer_config {
+    int32_t vocab, enc_dim, embed_dim, hidden, n_layers, joint_dim, blank_id;
+} pf_transducer_config;
+pf_transducer* pf_transducer_create(const pf_transducer_config* cfg);
+void pf_transducer_destroy(pf_transducer* h);
+int pf_transducer_set_weights(pf_transducer* h, const char* name, const float* data, int64_t numel);
+int pf_transducer_missing(const pf_transducer* h);
+/* the message of this handle's last failed search ("" after a good one); the string lives until the next search on the handle */
+const char* pf_transducer_last_error(const pf_transducer* h);
+/* what pf_transducer_search returns beside 0 and the negative statuses of every entry point */
+#define PF_TRANSDUCER_NONFINITE 2     /* a joint record held a non-finite value (NaN / inf weights or encoder output) */
+#define PF_TRANSDUCER_CAP 3           /* a frame needed more than max_expansions_per_frame joint evaluations */
+/* enc_out_dev [T, enc_dim] of ONE utterance -> the min(nbest, found) best hypotheses, best first: ids_out [nbest, max_len] (row i:
+ * lens_out[i] labels, the leading blank of the reference's yseq included), scores_out [nbest], *n_out rows.
+ * max_expansions_per_frame <= 0: 64 * beam. stats_out (optional) int64 [3]: joint evaluations, prediction steps, the largest
+ * number of joint evaluations of one frame -- written on failure too. Synchronises the stream (one read-back per evaluation). */
+int pf_transducer_search(pf_transducer* h, const float* enc_out_dev, int32_t T, int32_t beam, int32_t nbest,
+                         int32_t max_expansions_per_frame, int32_t* ids_out, int32_t* lens_out, double* scores_out, int32_t max_len,
+                         int32_t* n_out, int64_t* stats_out, void* stream);
+/* single-kernel hooks of the above (tests), on caller-supplied device buffers.
+ * pf_k_rnnt_pred_step: one prediction step for `label`. weights_dev: per layer l, back to back, weight_ih [4 H, in_l] (in_0 = E,
+ * else H), weight_hh [4 H, H], bias_ih [4 H], bias_hh [4 H]. state_dev [n_slots][L][2][H] (h then c), dec_proj_dev [n_slots][J].
+ * Reads slot src, writes slot dst (state and dec_proj = lin_dec . h' of the last layer) and nothing else; src == dst is refused.
+ * pf_k_rnnt_joint_topk: log-softmax(lin_out . tanh(enc_proj + dec_proj) + bias) -> record_dev [1 + 2 k] 4-byte words: logp of row 0,
+ * the k best logp among rows >= 1 (equal values: lower row first), their rows as int32. k <= min(16, V - 1). partials_dev: scratch of
+ * pf_k_rnnt_joint_partial_floats(V, k) floats, fully rewritten. */
+int pf_k_rnnt_pred_step(const float* embed_dev, const float* weights_dev, const float* lin_dec_dev, float* state_dev, float* dec_proj_dev,
+                        int32_t n_slots, int32_t V, int32_t E, int32_t H, int32_t L, int32_t J, int32_t label, int32_t src, int32_t dst,
+                        void* stream);
+int64_t pf_k_rnnt_joint_partial_floats(int32_t V, int32_t k);
+int pf_k_rnnt_joint_topk(const float* enc_proj_dev, const float* dec_proj_dev, const float* w_out_dev, const float* b_out_dev, int32_t V,
+                         int32_t J, int32_t k, float* partials_dev, float* record_dev, void* stream);
+
 typedef struct pf_ctc pf_ctc;
 pf_ctc* pf_ctc_create(int32_t d_model, int32_t vocab_size);
 void pf_ctc_destroy(pf_ctc* c);
