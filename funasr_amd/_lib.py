@@ -177,6 +177,18 @@ SIGNATURES = {
     "pf_vad_missing": (C.c_int, [_vp]),
     "pf_vad_forward": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _pi32, _i32, _vp, _vp, _i32, _vp]),
     "pf_vad_frame_decibel": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "pf_vad_logits": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp]),
+    "pf_kws_candidates": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "pf_kws_search_create": (_vp, [_i32]),
+    "pf_kws_search_destroy": (None, [_vp]),
+    "pf_kws_search_set_keywords": (C.c_int, [_vp, _pi32, _pi32, _i32]),
+    "pf_kws_search_missing": (C.c_int, [_vp]),
+    "pf_kws_search_token_mask": (C.c_int, [_vp, C.POINTER(C.c_uint32), _i32]),
+    "pf_kws_search_decode": (C.c_int, [_vp, _vp, _pi32, _i32, _i32, _pi32, _pi32, C.POINTER(C.c_double)]),
+    "pf_kws_search_nbest_count": (C.c_int, [_vp, _i32]),
+    "pf_kws_search_nbest": (C.c_int, [_vp, _i32, _i32, _i32, _pi32, C.POINTER(C.c_double), _pi32, _pi32, C.POINTER(C.c_double)]),
+    "pf_k_kws_fsmn": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "pf_k_vad_fsmn": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "pf_vad_decision_create": (_vp, [C.POINTER(pf_vad_options)]),
     "pf_vad_decision_destroy": (None, [_vp]),
     "pf_vad_decision_set_thresholds": (None, [_vp, C.c_double, C.c_double]),

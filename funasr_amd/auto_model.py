@@ -49,6 +49,7 @@ from . import contextual_paraformer as _contextual_paraformer  # noqa: F401  (re
 from . import ct_transformer as _ct_transformer  # noqa: F401  (registers CTTransformer)
 from . import emotion2vec as _emotion2vec  # noqa: F401  (registers Emotion2vec)
 from . import fsmn_vad as _fsmn_vad  # noqa: F401  (registers FSMN / FsmnVADStreaming)
+from . import kws as _kws  # noqa: F401  (registers FsmnKWS / SanmKWS)
 from . import paraformer as _paraformer  # noqa: F401  (registers the model classes)
 from . import paraformer_v2 as _paraformer_v2  # noqa: F401  (registers Paraformer_v2_community + its decoder)
 from . import paraformer_streaming as _paraformer_streaming  # noqa: F401  (WavFrontendOnline)
@@ -331,6 +332,7 @@ class AutoModel:
         if model_class is None and name == "BAT":
             raise NotImplementedError("model: BAT is not built (its boundary-aware predictor and search are not; model: Transducer is)")
         if model_class is None:
+            _kws.refuse_not_built(name)
             raise KeyError(f"model class {name!r} is not registered in model_classes: {sorted(tables.model_classes)}")
         model_conf = dict(kwargs.get("model_conf") or {})
         build_kwargs = {k: v for k, v in kwargs.items() if k not in ("model", "model_conf", "tokenizer", "frontend")}

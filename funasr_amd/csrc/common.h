@@ -558,4 +558,10 @@ int launch_vad_softmax_sil(const float* x, int ldx, int M, int N, const int* ids
                            int ldp, hipStream_t stream);
 int launch_frame_decibel(const float* wav, int n_frames, int flen, int shift, float* out, hipStream_t stream);
 
+// kws.hip: the FSMN memory block with a right context (no cache; R = 0 is the left-only block, bit for bit launch_vad_fsmn's) and
+// the candidate step of the keyword search (mask: ceil(V / 32) words, bit id set = a keyword token; out [M, 7] words)
+int launch_kws_fsmn(const float* x, int ldx, const float* wl, const float* wr, float* y, int ldy, int B, int T, int C, int L, int LS,
+                    int R, int RS, hipStream_t stream);
+int launch_kws_candidates(const float* x, long ldx, int M, int V, const unsigned* mask, int* out, hipStream_t stream);
+
 }  // namespace pf

@@ -1,7 +1,7 @@
 // Internal header of the C-ABI layer (include/paraformer_hip.h): the handle types of every module family and the helpers they
 // share. The layer is split by family -- engine.hip (shared state: errors, profiling, staging ring, instrumented launch helpers,
 // ABI version), engine_frontend.hip, engine_encoder.hip, engine_predictor.hip, engine_decoder.hip (decoder, CTC), engine_stream.hip,
-// engine_vad.hip, engine_pipeline.hip, engine_campplus.hip, engine_emotion2vec.hip, engine_conformer.hip (Conformer encoder and
+// engine_vad.hip, engine_kws.hip (keyword spotting: candidate step, host search), engine_pipeline.hip, engine_campplus.hip, engine_emotion2vec.hip, engine_conformer.hip (Conformer encoder and
 // Transformer decoder step), engine_posterior.hip (Paraformer-v2 posterior embedder), engine_kernels.hip (the pf_k_* single-kernel hooks) -- so that a kernel change recompiles one family
 // (round-3 review: engine.hip was one 3 400-line translation unit).
 //

@@ -16,9 +16,9 @@ pf_vad* pf_vad_create(const pf_vad_config* cfg) {
     if (check_device()) return nullptr;
     const pf_vad_config& c = *cfg;
     if (c.input_dim <= 0 || c.input_affine_dim <= 0 || c.linear_dim <= 0 || c.proj_dim <= 0 || c.proj_dim % 4 ||
-        c.proj_dim > 128 || c.fsmn_layers < 1 || c.lorder < 1 || c.lstride < 1 || c.rorder != 0 || c.output_affine_dim <= 0 ||
-        c.output_dim <= 0 || c.output_dim > 512) {
-        set_error("vad: unsupported config (uni-directional FSMN: rorder 0; proj_dim % 4 == 0 and <= 128; output_dim <= 512)");
+        c.proj_dim > 128 || c.fsmn_layers < 1 || c.lorder < 1 || c.lstride < 1 || c.rorder < 0 || (c.rorder > 0 && c.rstride < 1) ||
+        c.output_affine_dim <= 0 || c.output_dim <= 0 || c.output_dim > 65536) {
+        set_error("vad: unsupported config (proj_dim % 4 == 0 and <= 128; lorder >= 1, rorder >= 0, strides >= 1; output_dim <= 65536)");
         return nullptr;
     }
     std::unique_ptr<Vad> v(new Vad());
@@ -32,6 +32,7 @@ pf_vad* pf_vad_create(const pf_vad_config* cfg) {
         const std::string p = "fsmn." + std::to_string(i) + ".";
         rc |= v->tt.add_padded(p + "linear.linear.weight", c.proj_dim, c.linear_dim, vad_pad(c.linear_dim));
         rc |= v->tt.add(p + "fsmn_block.conv_left.weight", (int64_t)c.proj_dim * c.lorder);
+        if (c.rorder > 0) rc |= v->tt.add(p + "fsmn_block.conv_right.weight", (int64_t)c.proj_dim * c.rorder);
         rc |= v->tt.add_padded(p + "affine.linear.weight", c.linear_dim, c.proj_dim, vad_pad(c.proj_dim));
         rc |= v->tt.add(p + "affine.linear.bias", c.linear_dim);
     }
@@ -52,22 +53,22 @@ int pf_vad_missing(const pf_vad* vh) {
     const Vad* v = reinterpret_cast<const Vad*>(vh);
     return v ? v->tt.missing() : -1;
 }
-/* feats_dev [B, T, input_dim]; cache_dev [B, fsmn_layers, (lorder-1)*lstride, proj_dim] is the left context of every
- * memory block, read and updated in place (NULL: zero left context, nothing kept); sil_ids_host: the silence pdfs whose
- * posteriors are summed into p_sil_dev [B, T]; probs_dev [B, T, output_dim] (optional) receives the full softmax.
- * small_m != 0 routes the dense layers through the weight-streaming GEMM (streaming chunks of a few frames). */
-int pf_vad_forward(pf_vad* vh, const float* feats, int32_t B, int32_t T, float* cache, const int32_t* sil_ids_host,
-                   int32_t n_sil, float* p_sil, float* probs, int32_t small_m, void* stream) {
-    Vad* v = reinterpret_cast<Vad*>(vh);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    PF_REQUIRE(v && feats && p_sil && sil_ids_host && B > 0 && T > 0 && n_sil >= 1, "vad_forward: null/empty argument");
-    if (v->tt.require_all("vad")) return -3;
+}  // extern "C"
+
+// The network up to out_linear2's output, before any softmax: logits [B * T, output_dim] with row stride ldo (% 4, >= output_dim).
+// out == nullptr: they stay in the handle's scratch (*logits / *ldo_out say where). With rorder > 0 the memory blocks read future
+// frames of the padded batch (kws.hip) and there is no streaming cache.
+static int vad_network(Vad* v, const float* feats, int B, int T, float* cache, int small_m, hipStream_t s, float* out, int ldo,
+                       const float** logits, int* ldo_out) {
     const pf_vad_config& c = v->cfg;
+    PF_REQUIRE(!(cache && c.rorder > 0), "vad: a streaming cache with rorder > 0 does not exist (the right context reads future frames)");
+    PF_REQUIRE((int64_t)B * T <= INT32_MAX, "vad: B * T past 2^31 - 1 frames");
     const int M = B * T;
     const int Kin = vad_pad(c.input_dim), Ka = vad_pad(c.input_affine_dim), Kl = vad_pad(c.linear_dim), Kp = vad_pad(c.proj_dim),
               Ko = vad_pad(c.output_affine_dim);
+    if (!out) ldo = round_up(c.output_dim, 4);
     int wide = Kin;
-    for (int k : {Ka, Kl, Kp, Ko, round_up(c.output_dim, 4)}) wide = k > wide ? k : wide;
+    for (int k : {Ka, Kl, Kp, Ko, out ? 0 : ldo}) wide = k > wide ? k : wide;
     const size_t bytes = sizeof(float) * (size_t)M * wide;
     const int ctx = (c.lorder - 1) * c.lstride;
     if (v->a.ensure(bytes) || v->b.ensure(bytes) || v->c.ensure(bytes) ||
@@ -96,7 +97,10 @@ int pf_vad_forward(pf_vad* vh, const float* feats, int32_t B, int32_t T, float* 
         const std::string p = "fsmn." + std::to_string(i) + ".";
         if ((rc = lin(a, Kl, (p + "linear.linear.weight").c_str(), nullptr, b, Kp, c.proj_dim, 0))) return rc;
         float* lc = cache ? cache + (size_t)i * ctx * c.proj_dim : nullptr;       // layer i of stream 0; streams are
-        if (cache && B > 1) {                                                      // [B, layers, ctx, proj] apart
+        if (c.rorder > 0) {                                                        // (no cache: refused above)
+            if ((rc = launch_kws_fsmn(b, Kp, v->tt.get(p + "fsmn_block.conv_left.weight"), v->tt.get(p + "fsmn_block.conv_right.weight"),
+                                      cc, Kp, B, T, c.proj_dim, c.lorder, c.lstride, c.rorder, c.rstride, s))) return rc;
+        } else if (cache && B > 1) {                                                    // [B, layers, ctx, proj] apart
             // per-stream caches are not contiguous per layer: run the memory block stream by stream
             for (int bb = 0; bb < B; ++bb) {
                 float* sc = cache + ((size_t)bb * c.fsmn_layers + i) * ctx * c.proj_dim;
@@ -117,9 +121,40 @@ int pf_vad_forward(pf_vad* vh, const float* feats, int32_t B, int32_t T, float* 
             return rc;
     }
     if ((rc = lin(a, Kl, "out_linear1.linear.weight", "out_linear1.linear.bias", b, Ko, c.output_affine_dim, 0))) return rc;
-    const int ldo = round_up(c.output_dim, 4);
-    if ((rc = lin(b, Ko, "out_linear2.linear.weight", "out_linear2.linear.bias", cc, ldo, c.output_dim, 0))) return rc;
-    return launch_vad_softmax_sil(cc, ldo, M, c.output_dim, sil_ids_host, n_sil, p_sil, probs, c.output_dim, s);
+    float* dst = out ? out : cc;
+    if ((rc = lin(b, Ko, "out_linear2.linear.weight", "out_linear2.linear.bias", dst, ldo, c.output_dim, 0))) return rc;
+    if (logits) *logits = dst;
+    if (ldo_out) *ldo_out = ldo;
+    return 0;
+}
+
+extern "C" {
+
+/* feats_dev [B, T, input_dim]; cache_dev [B, fsmn_layers, (lorder-1)*lstride, proj_dim] is the left context of every
+ * memory block, read and updated in place (NULL: zero left context, nothing kept); sil_ids_host: the silence pdfs whose
+ * posteriors are summed into p_sil_dev [B, T]; probs_dev [B, T, output_dim] (optional) receives the full softmax.
+ * small_m != 0 routes the dense layers through the weight-streaming GEMM (streaming chunks of a few frames). */
+int pf_vad_forward(pf_vad* vh, const float* feats, int32_t B, int32_t T, float* cache, const int32_t* sil_ids_host,
+                   int32_t n_sil, float* p_sil, float* probs, int32_t small_m, void* stream) {
+    Vad* v = reinterpret_cast<Vad*>(vh);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    PF_REQUIRE(v && feats && p_sil && sil_ids_host && B > 0 && T > 0 && n_sil >= 1, "vad_forward: null/empty argument");
+    PF_REQUIRE(v->cfg.output_dim <= 512, "vad_forward: the softmax head takes output_dim <= 512 (pf_vad_logits leaves the logits)");
+    if (v->tt.require_all("vad")) return -3;
+    const float* logits = nullptr;
+    int ldo = 0, rc;
+    if ((rc = vad_network(v, feats, B, T, cache, small_m, s, nullptr, 0, &logits, &ldo))) return rc;
+    return launch_vad_softmax_sil(logits, ldo, B * T, v->cfg.output_dim, sil_ids_host, n_sil, p_sil, probs, v->cfg.output_dim, s);
+}
+/* the same network without its softmax: logits_dev [B * T, ld] (ld % 4 == 0, ld >= output_dim; the columns from output_dim on are
+ * not written) receives out_linear2's output. The head of FsmnKWS (use_softmax: false). */
+int pf_vad_logits(pf_vad* vh, const float* feats, int32_t B, int32_t T, float* cache, float* logits, int32_t ld, int32_t small_m,
+                  void* stream) {
+    Vad* v = reinterpret_cast<Vad*>(vh);
+    PF_REQUIRE(v && feats && logits && B > 0 && T > 0, "vad_logits: null/empty argument");
+    PF_REQUIRE(ld % 4 == 0 && ld >= v->cfg.output_dim, "vad_logits: row stride % 4 == 0 and >= output_dim");
+    if (v->tt.require_all("vad")) return -3;
+    return vad_network(v, feats, B, T, cache, small_m, reinterpret_cast<hipStream_t>(stream), logits, ld, nullptr, nullptr);
 }
 /* 10 log10(sum(x^2) + 1e-6) of n_frames frames of frame_len samples, frame_shift apart (ComputeDecibel, model.py:513-530) */
 int pf_vad_frame_decibel(const float* wav, int64_t n_samples, int32_t n_frames, int32_t frame_len, int32_t frame_shift,

@@ -2,7 +2,8 @@
 
 Host-side mirrors, registered under the reference's names:
   * `FSMN` (encoder_classes; funasr/models/fsmn_vad_streaming/encoder.py:288-378): holds the parameters under the
-    reference's state_dict keys; `forward(feats, cache)` returns the softmax over the output pdfs like the reference,
+    reference's state_dict keys (with `rorder > 0` also `fsmn.<i>.fsmn_block.conv_right.weight`: the keyword spotter's network,
+    funasr_amd/kws.py, whose `use_softmax: false` head is `logits`); `forward(feats, cache)` returns the softmax over the output pdfs like the reference,
     `silence_posterior(feats, cache, sil_pdf_ids)` the only thing the decision logic reads. Dense layers run on the
     fp32 GEMM kernels, the memory blocks / softmax / frame energies in csrc/vad.hip. The left-context cache of the memory
     blocks lives in HBM (`cache["fsmn_ctx"]`, [1, layers, (lorder-1)*lstride, proj_dim]).
@@ -25,7 +26,7 @@ import torch
 
 from . import _lib
 from .audio import load_audio_list
-from .hip_module import Holder, HipModule, HostCopyRing, ParamHolder, StagedUpload, linear, stream_ptr
+from .hip_module import Holder, HipModule, HostCopyRing, ParamHolder, StagedUpload, _truthy, linear, stream_ptr
 from .register import tables
 from .vad_decision import IN_SPEECH, NativeVadDecision, VadOptions
 
@@ -49,10 +50,14 @@ class FSMN(HipModule):
                  rorder: int, lstride: int, rstride: int, output_affine_dim: int, output_dim: int, use_softmax: bool = True,
                  **kwargs):
         super().__init__()
-        if rorder != 0:
-            raise NotImplementedError("FSMN(HIP): only the uni-directional memory (rorder 0) of fsmn-vad is built")
-        if not use_softmax:
-            raise NotImplementedError("FSMN(HIP): the VAD head is the softmax posterior")
+        if int(rorder) < 0 or (int(rorder) > 0 and int(rstride) < 1):
+            raise ValueError(f"FSMN: rorder {rorder} / rstride {rstride}")
+        if int(output_dim) > 65536:
+            raise NotImplementedError(f"FSMN(HIP): output_dim: {output_dim} is not built (at most 65536)")
+        if _truthy(use_softmax) and int(output_dim) > 512:
+            raise NotImplementedError(f"FSMN(HIP): use_softmax: true with output_dim: {output_dim} is not built (the softmax head "
+                                      "takes at most 512 outputs; use_softmax: false leaves the logits)")
+        self.use_softmax = _truthy(use_softmax)
         self.cfg = dict(input_dim=input_dim, input_affine_dim=input_affine_dim, fsmn_layers=fsmn_layers, linear_dim=linear_dim,
                         proj_dim=proj_dim, lorder=lorder, rorder=rorder, lstride=lstride, rstride=rstride,
                         output_affine_dim=output_affine_dim, output_dim=output_dim)
@@ -65,6 +70,8 @@ class FSMN(HipModule):
             b.linear = _affine(proj_dim, linear_dim, bias=False)
             b.fsmn_block = Holder()
             b.fsmn_block.conv_left = ParamHolder((proj_dim, 1, lorder, 1))
+            if rorder > 0:
+                b.fsmn_block.conv_right = ParamHolder((proj_dim, 1, rorder, 1))
             b.affine = _affine(linear_dim, proj_dim)
             blocks.append(b)
         self.fsmn = torch.nn.ModuleList(blocks)
@@ -106,7 +113,31 @@ class FSMN(HipModule):
                                           1 if B * T <= 64 else 0, stream_ptr()), "pf_vad_forward")
         return p_sil, probs
 
+    def logits(self, feats: torch.Tensor, cache: Optional[dict] = None) -> torch.Tensor:
+        """out_linear2's output before any softmax, [B, T, output_dim] (a view of rows whose stride is output_dim rounded up to
+        4). Every one of the B x T rows is computed: with rorder > 0 the last frames of a shorter clip read the padding frames
+        behind it, as the reference's `encoder(speech)` without lengths does. A cache with rorder > 0 is refused."""
+        if cache is not None and self.cfg["rorder"] > 0:
+            raise ValueError("FSMN: a streaming cache with rorder > 0 does not exist (the right context reads future frames)")
+        lib, h = self._ensure_handle()
+        dev = self._handle_device
+        x = feats.to(device=dev, dtype=torch.float32).contiguous()
+        B, T, D = x.shape
+        if D != self.input_dim:
+            raise ValueError(f"FSMN: expected {self.input_dim}-dim features, got {D}")
+        if cache is not None and B != 1:
+            raise ValueError("FSMN: the streaming cache is per stream (batch 1), like the reference")
+        ctx = self._context(cache, dev)
+        ld = (self.output_dim + 3) // 4 * 4
+        out = torch.empty(B, T, ld, device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            _lib.check(lib.pf_vad_logits(h, x.data_ptr(), B, T, ctx.data_ptr() if ctx is not None else None, out.data_ptr(), ld, 0,
+                                         stream_ptr()), "pf_vad_logits")
+        return out[..., : self.output_dim]
+
     def forward(self, input: torch.Tensor, cache: Optional[Dict[str, torch.Tensor]] = None):
+        if not self.use_softmax:
+            return self.logits(input, cache)
         return self._run(input, cache, [0], True)[1]
 
     def silence_posterior(self, feats: torch.Tensor, cache: Optional[dict] = None, sil_pdf_ids=(0,)) -> torch.Tensor:

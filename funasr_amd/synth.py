@@ -524,3 +524,68 @@ def transducer_state_dict(seed: int, model, n_planted: int = 10, threshold: floa
         sd["joint_network.lin_out.weight"][v, i] = (blank + 5.0 - off) / 2
         sd["joint_network.lin_out.bias"][v] += (blank + 5.0 + off) / 2
     return sd
+
+
+def kws_fsmn_conf(input_dim: int = 40, input_affine_dim: int = 24, fsmn_layers: int = 2, linear_dim: int = 32, proj_dim: int = 16,
+                  lorder: int = 4, rorder: int = 2, lstride: int = 1, rstride: int = 1, output_affine_dim: int = 24, vocab: int = 67) -> dict:
+    """constructor arguments of an FsmnKWS model (the layout of examples/industrial_data_pretraining/fsmn_kws/conf/*.yaml) at a
+    chosen size"""
+    enc = {"input_dim": input_dim, "input_affine_dim": input_affine_dim, "fsmn_layers": fsmn_layers, "linear_dim": linear_dim,
+           "proj_dim": proj_dim, "lorder": lorder, "rorder": rorder, "lstride": lstride, "rstride": rstride,
+           "output_affine_dim": output_affine_dim, "output_dim": vocab, "use_softmax": False}
+    return {"encoder": "FSMN", "encoder_conf": enc, "ctc_conf": {"dropout_rate": 0.0, "ctc_type": "builtin", "reduce": True,
+                                                                 "ignore_nan_grad": True, "extra_linear": False},
+            "ctc_weight": 1.0, "input_size": input_dim, "vocab_size": vocab}
+
+
+KWS_FSMN_RECIPE = dict(input_dim=400, input_affine_dim=140, fsmn_layers=4, linear_dim=250, proj_dim=128, lorder=10, rorder=2,
+                       output_affine_dim=140, vocab=2599)                       # fsmn_4e_l10r2_250_128_fdim80_t2599
+
+
+def kws_sanm_conf(output_size: int = 128, attention_heads: int = 2, linear_units: int = 64, num_blocks: int = 2, vocab: int = 67,
+                  input_size: int = 40) -> dict:
+    """constructor arguments of a SanmKWS model (examples/industrial_data_pretraining/sanm_kws/conf/*.yaml) at a chosen size"""
+    enc = {"output_size": output_size, "attention_heads": attention_heads, "linear_units": linear_units, "num_blocks": num_blocks,
+           "dropout_rate": 0.1, "positional_dropout_rate": 0.1, "attention_dropout_rate": 0.1, "input_layer": "pe",
+           "pos_enc_class": "SinusoidalPositionEncoder", "normalize_before": True, "kernel_size": 11, "sanm_shfit": 0,
+           "selfattention_layer_type": "sanm"}
+    return {"encoder": "SANMEncoder", "encoder_conf": enc, "ctc_conf": {"dropout_rate": 0.0, "ctc_type": "builtin", "reduce": True},
+            "ctc_weight": 1.0, "input_size": input_size, "vocab_size": vocab}
+
+
+KWS_SANM_RECIPE = dict(output_size=256, attention_heads=4, linear_units=320, num_blocks=6, vocab=2602, input_size=280)  # sanm_6e_320_256_fdim40_t2602
+
+
+def kws_state_dict(seed: int, model, planted=(), gain: float = 6.0, blank: float = 2.0, floor: float = -3.0) -> Dict[str, torch.Tensor]:
+    """synthetic weights in the layout of `model` (an FsmnKWS / SanmKWS module or the reference's). Everything but the output
+    layer is drawn by conformer_state_dict's rules (fan-in scaled matrices, LayerNorm weights near 1, other vectors of order 0.1), key
+    by key in NAME order. Plain random weights give a near-uniform posterior that never crosses the
+    search's 0.05 (a probe at 67 tokens: 0.02 at most), so the output layer -- `encoder.out_linear2.linear` where the model has no
+    `ctc_lo`, `ctc.ctc_lo` otherwise -- is planted over a quiet background:
+      * every row is a random direction with logit noise of order 1; the bias of blank is `blank`, of every other unplanted
+        token `floor`: blank holds most of the mass on most frames;
+      * the rows of the `planted` token ids have `gain` times the background's scale and bias 0: each of them overtakes blank on
+        the few frames whose hidden vector points its way, and two of them now and then share a frame."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for k, v in sorted(model.state_dict().items()):            # by NAME: the reference's modules register their parameters in another order
+        shp = tuple(v.shape)
+        if len(shp) == 1:
+            sd[k] = (1.0 + 0.2 * torch.randn(shp, generator=g)) if ("norm" in k and k.endswith("weight")) else 0.1 * torch.randn(shp, generator=g)
+        else:
+            fan_in = 1
+            for d in shp[1:]:
+                fan_in *= d
+            sd[k] = torch.randn(shp, generator=g) * (1.0 / fan_in) ** 0.5
+    g = torch.Generator().manual_seed(seed + 104729)
+    wkey = [k for k in sd if k.endswith("ctc_lo.weight")] or [k for k in sd if k.endswith("out_linear2.linear.weight")]
+    wkey = wkey[0]
+    bkey = wkey[: -len("weight")] + "bias"
+    V, K = sd[wkey].shape
+    sd[wkey] = torch.randn(V, K, generator=g) * (1.0 / K) ** 0.5
+    sd[bkey] = torch.full((V,), float(floor)) + 0.1 * torch.randn(V, generator=g)
+    sd[bkey][0] = float(blank)
+    for v in planted:
+        sd[wkey][int(v)] *= float(gain)
+        sd[bkey][int(v)] = 0.0
+    return sd

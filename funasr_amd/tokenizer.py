@@ -149,7 +149,13 @@ def sentence_postprocess(tokens: Iterable[Union[str, bytes]], time_stamp: Option
 
 @tables.register("tokenizer_classes", "CharTokenizer")
 class CharTokenizer:
-    def __init__(self, token_list=None, unk_symbol: str = "<unk>", space_symbol: str = "<space>", **kwargs):
+    def __init__(self, token_list=None, unk_symbol: str = "<unk>", space_symbol: str = "<space>", seg_dict: str = None, **kwargs):
+        # char_tokenizer.py:49-52: the word lexicon of the model directory, read by the keyword spotters (funasr_amd/kws.py)
+        self.seg_dict = None
+        seg_dict = seg_dict if seg_dict is not None else kwargs.get("seg_dict_file", None)
+        if seg_dict is not None:
+            from .seaco_paraformer import load_seg_dict
+            self.seg_dict = load_seg_dict(str(seg_dict))
         if isinstance(token_list, (str, os.PathLike)):
             path = str(token_list)
             with open(path, "r", encoding="utf-8") as f:

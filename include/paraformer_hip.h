@@ -24,6 +24,8 @@
  *                                                            funasr/models/paraformer/model.py:345,629-637, transformer/scorers/ctc.py:46
  *   pf_stream     <-> ParaformerStreaming chunk step         funasr/models/paraformer_streaming/model.py
  *   pf_vad, pf_vad_decision <-> FsmnVADStreaming (network / state machine)   funasr/models/fsmn_vad_streaming/{encoder,model}.py
+ *   pf_vad_logits, pf_kws_candidates, pf_kws_search <-> FsmnKWS / SanmKWS (FSMN without softmax; KwsCtcPrefixDecoder)
+ *                                                            funasr/models/fsmn_kws/model.py, sanm_kws/model.py, utils/kws_utils.py
  *   pf_k_lstm     <-> torch.nn.LSTM layer (hotword encoder of SeACo, seaco_paraformer/model.py:388-424)
  *   pf_campplus   <-> CAMPPlus.forward (speaker embedding)  funasr/models/campplus/model.py, components.py
  *
@@ -368,6 +370,43 @@ int pf_vad_forward(pf_vad* v, const float* feats_dev, int32_t B, int32_t T, floa
                    int32_t n_sil, float* p_sil_dev, float* probs_dev, int32_t small_m, void* stream);
 int pf_vad_frame_decibel(const float* wav_dev, int64_t n_samples, int32_t n_frames, int32_t frame_len, int32_t frame_shift,
                          float* out_dev, void* stream);
+/* The same network without its softmax (the FSMN of FsmnKWS: use_softmax false): logits_dev [B * T, ld] receives out_linear2's
+ * output (ld % 4 == 0, ld >= output_dim; columns from output_dim on are not written). pf_vad_create takes rorder > 0 (a further
+ * tensor "fsmn.<i>.fsmn_block.conv_right.weight" [proj, 1, rorder, 1]; the memory blocks then read future frames of the PADDED
+ * batch, as the reference does, and a cache pointer is refused) and output_dim up to 65536; pf_vad_forward refuses
+ * output_dim > 512, which its softmax kernel cannot do. No sync. */
+int pf_vad_logits(pf_vad* v, const float* feats_dev, int32_t B, int32_t T, float* cache_dev, float* logits_dev, int32_t ld,
+                  int32_t small_m, void* stream);
+
+/* ---- keyword spotting (FsmnKWS / SanmKWS; funasr/utils/kws_utils.py KwsCtcPrefixDecoder)
+ * pf_kws_candidates: the per-frame candidate step of beam_search (:156-171) for M rows of logits (row stride ld >= V, 3 <= V <=
+ * 65536): the three largest of the row in descending order (equal values: the lower index first), p = exp(x - max) / sum exp(x - max),
+ * an entry kept if p > 0.05 and bit id of mask_dev (ceil(V / 32) words; bit 0 = blank is always set by pf_kws_search_token_mask) is
+ * set. out_dev [M, 7] words per row: n, ids[3] (-1 from n on), the fp32 bits of probs[3] (0 from n on). No sync.
+ * pf_kws_search: host code without device work (creating it needs no GPU). Keywords are token-id lists (keyword k =
+ * ids[offsets[k] .. offsets[k + 1])). pf_kws_search_decode runs the CTC prefix search (path beam 20) of B clips over the read-back
+ * candidates cand_host [B, T, 7] (frames < lens_host[b]) and the hit test of _decode_inside: hit_host[b] = index of the keyword or -1,
+ * offset_host[b] (nullable) where it starts in the hypothesis, score_host[b] = sqrt(product of the matched nodes' probabilities).
+ * The n-best of the last decode stay readable: pf_kws_search_nbest returns the prefix length of hypothesis i of a clip (final order)
+ * and, if it fits `capacity`, its prefix ids and per node token / frame / prob; *score = pb + pnb. */
+typedef struct pf_kws_search pf_kws_search;
+int pf_kws_candidates(const float* logits_dev, int64_t ld, int32_t M, int32_t V, const uint32_t* mask_dev, int32_t* out_dev,
+                      void* stream);
+pf_kws_search* pf_kws_search_create(int32_t vocab_size);
+void pf_kws_search_destroy(pf_kws_search* k);
+int pf_kws_search_set_keywords(pf_kws_search* k, const int32_t* ids, const int32_t* offsets, int32_t n_keywords);
+int pf_kws_search_missing(const pf_kws_search* k);   /* 1 until keywords are set */
+int pf_kws_search_token_mask(const pf_kws_search* k, uint32_t* mask_host, int32_t n_words);
+int pf_kws_search_decode(pf_kws_search* k, const int32_t* cand_host, const int32_t* lens_host, int32_t B, int32_t T,
+                         int32_t* hit_host, int32_t* offset_host, double* score_host);
+int pf_kws_search_nbest_count(const pf_kws_search* k, int32_t clip);
+int pf_kws_search_nbest(const pf_kws_search* k, int32_t clip, int32_t i, int32_t capacity, int32_t* prefix, double* score,
+                        int32_t* node_token, int32_t* node_frame, double* node_prob);
+/* the FSMN memory block with a right context alone, and the VAD network's left-only block it equals bit for bit at rorder 0 */
+int pf_k_kws_fsmn(const float* x, int32_t ldx, const float* w_left, const float* w_right, float* y, int32_t ldy, int32_t B, int32_t T,
+                  int32_t C, int32_t lorder, int32_t lstride, int32_t rorder, int32_t rstride, void* stream);
+int pf_k_vad_fsmn(const float* x, int32_t ldx, const float* w_left, float* y, int32_t ldy, int32_t B, int32_t T, int32_t C,
+                  int32_t lorder, int32_t lstride, void* stream);
 
 /* ---- FSMN-VAD decision logic in native host code (no device work): silence posteriors + frame energies -> speech
  * segments; restates what FsmnVADStreaming.forward does after the network (model.py:552-905,1117-1302). Options = the
