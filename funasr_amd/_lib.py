@@ -107,6 +107,11 @@ class pf_tdecoder_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("vocab_size", "d_model", "n_heads", "ffn_dim", "n_blocks")] + [("ln_eps", C.c_float)]
 
 
+class pf_fsmndecoder_config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("vocab_size", "d_model", "n_heads", "ffn_dim", "n_blocks", "att_layer_num", "kernel_size",
+                                          "sanm_shift")] + [("ln_eps", C.c_float)]
+
+
 class pf_stream_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_streams", "chunk_left", "chunk_cur", "chunk_right", "enc_look_back",
                                           "dec_look_back", "max_frames", "max_tokens", "use_graph")]
@@ -232,6 +237,15 @@ SIGNATURES = {
     "pf_tdecoder_begin": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "pf_tdecoder_step": (C.c_int, [_vp, _pi32, _i32, _i32, _vp, _vp]),
     "pf_tdecoder_reorder": (C.c_int, [_vp, _pi32, _i32, _vp]),
+    "pf_fsmndecoder_create": (_vp, [C.POINTER(pf_fsmndecoder_config)]),
+    "pf_fsmndecoder_destroy": (None, [_vp]),
+    "pf_fsmndecoder_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),
+    "pf_fsmndecoder_missing": (C.c_int, [_vp]),
+    "pf_fsmndecoder_begin": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "pf_fsmndecoder_step": (C.c_int, [_vp, _pi32, _i32, _i32, _vp, _vp]),
+    "pf_fsmndecoder_reorder": (C.c_int, [_vp, _pi32, _i32, _vp]),
+    "pf_k_fsmn_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _f32, _vp, _vp, _vp]),
+    "pf_k_cross_attention_step": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "pf_k_relpos_attention": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "pf_k_conformer_glu_dw": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "pf_transducer_create": (_vp, [C.POINTER(pf_transducer_config)]),

@@ -366,9 +366,11 @@ class PaddedBatchFront:
 class AttentionEncoderDecoder(PaddedBatchFront, nn.Module):
     """funasr/models/transformer/model.py Transformer, the CTC / attention encoder-decoder the reference's `Conformer` subclasses
     with nothing added: everything but the encoder. A model class names the one encoder it accepts (`_encoder`) and what its
-    refusal of another says (`_other_encoders`); funasr_amd.transformer.Transformer is the other one."""
+    refusal of another says (`_other_encoders`), and the one decoder (`_decoder`); funasr_amd.transformer.Transformer and
+    funasr_amd.sanm.SANM are the others."""
     _encoder = None                # the encoder_classes key
     _other_encoders = ""
+    _decoder = "TransformerDecoder"    # the decoder_classes key (funasr_amd.sanm.SANM names "FsmnDecoder")
 
     def __init__(self, specaug: Optional[str] = None, specaug_conf: Optional[Dict] = None, normalize: str = None,
                  normalize_conf: Optional[Dict] = None, encoder: str = None, encoder_conf: Optional[Dict] = None, decoder: str = None,
@@ -382,8 +384,8 @@ class AttentionEncoderDecoder(PaddedBatchFront, nn.Module):
             raise NotImplementedError(f"{me}(HIP): encoder: {encoder} is not built (only {self._encoder}; {self._other_encoders})")
         if decoder is None or float(ctc_weight) == 1.0:
             raise NotImplementedError(f"{me}(HIP): a model without decoder (decoder: null or ctc_weight: 1.0) is not built")
-        if decoder != "TransformerDecoder":
-            raise NotImplementedError(f"{me}(HIP): decoder: {decoder} is not built (only TransformerDecoder)")
+        if decoder != self._decoder:
+            raise NotImplementedError(f"{me}(HIP): decoder: {decoder} is not built (only {self._decoder})")
         if float(interctc_weight) != 0.0:
             raise NotImplementedError(f"{me}(HIP): interctc_weight is not built")
         if _truthy(share_embedding):
@@ -395,7 +397,7 @@ class AttentionEncoderDecoder(PaddedBatchFront, nn.Module):
         dec_conf = dict(decoder_conf or {})
         dec_conf.pop("vocab_size", None)
         dec_conf.pop("encoder_output_size", None)
-        self.decoder = TransformerDecoder(vocab_size=vocab_size, encoder_output_size=d, **dec_conf)
+        self.decoder = tables.decoder_classes[self._decoder](vocab_size=vocab_size, encoder_output_size=d, **dec_conf)
         self.ctc = None
         if float(ctc_weight) > 0.0:                                   # transformer/model.py:118-123,163-166
             from .ctc import CTC

@@ -1,4 +1,4 @@
-// Kernel launchers of the Conformer encoder, the Transformer encoder and the Transformer decoder step (conformer.hip,
+// Kernel launchers of the Conformer encoder, the Transformer encoder, the Transformer decoder step and the SAN-M decoder step (conformer.hip,
 // attention_relpos.hip, attention_abs.hip; driven by engine_conformer.hip). Activations are rows of a [B * T, D] buffer (T = the BATCH's encoder length: the reference computes every
 // row of the zero-padded batch and so does this path). Every kernel computes a row in a fixed order and without atomics.
 #pragma once
@@ -43,7 +43,8 @@ int launch_cf_relpos_attention(const float* qkv, const float* P, const float* u,
 int launch_tf_attention(const float* qkv, const int* klens, int B, int T, int H, float* out, hipStream_t stream);
 
 // ---- Transformer decoder step
-// x[r] = table[ids[r]] * scale + pe[pos] (r < n; ids on the device)
+// x[r] = table[ids[r]] * scale + pe[pos] (r < n; ids on the device); pe_row == nullptr: the scale alone (the SAN-M decoder's bare
+// embedding with scale 1)
 int launch_td_embed(const float* table, const int* ids, const float* pe_row, float scale, float* x, int n, int D, hipStream_t stream);
 
 // few-query attention, head dim 64: query r (q [n, D], head h at column 64 h) over nk keys K / V rows of `ldkv` floats, the
@@ -55,5 +56,23 @@ int launch_td_attention(const float* q, const float* K, const float* V, int ldkv
 // a layer `layer_floats`, a position `row_floats`
 int launch_td_reorder(const float* src, float* dst, const int* parents, int n, int L, size_t layer_floats, size_t slot_floats,
                       int len, int row_floats, hipStream_t stream);
+
+// ---- SAN-M (FsmnDecoder) step
+// The FSMN memory block of one decoder layer for the n running slots of step `pos`, one launch:
+//   u = LayerNorm(t[r]; g2, b2)
+//   window of slot r, K columns of D floats:  pos == 0: zeros with u at column left_pad;
+//                                             pos > 0:  columns 1 .. K - 1 of win_in[parents[r]] (parents == nullptr: r), then u
+//   x_out[r] = x[r] + (sum_k w[d][k] window[k][d] + u)          (the block adds its own input; no bias)
+//   xn_out[r] = LayerNorm(x_out[r]; g3, b3)                     (g3 != nullptr: the layer has cross-attention)
+// and the new window is written to win_out[r]. win_in / win_out [slots][K][D] must not overlap (ping-pong); every parent index is
+// below the slot count of win_in (checked by the caller on the host). D % 4 == 0, D <= 2048, 1 <= K <= 32, 0 <= left_pad < K.
+int launch_fd_fsmn_step(const float* t, const float* x, const float* g2, const float* b2, const float* w, const float* win_in,
+                        float* win_out, const int* parents, int pos, int n, int D, int K, int left_pad, const float* g3,
+                        const float* b3, float eps, float* x_out, float* xn_out, hipStream_t stream);
+
+// few-query cross-attention for head dims 64 and 128: query r (q [n, H dk], head h at column dk h) over the SAME nk memory rows for
+// every query, K / V rows of `ldkv` floats. softmax(q . k / sqrt(dk)) v -> out [n, H dk]. No mask.
+int launch_fd_attention(const float* q, const float* K, const float* V, int ldkv, int nk, int n, int H, int dk, float* out,
+                        hipStream_t stream);
 
 }  // namespace pf

@@ -1,6 +1,7 @@
 // Row kernels of the Conformer encoder and of the Transformer decoder step (see conformer.h): the first conv of Conv2dSubsampling,
 // ReLU / Swish rows, the GLU + depthwise conv + BatchNorm + Swish row kernel of the convolution module, and the decoder step's
-// embedding, few-query attention and cache reorder.
+// embedding, few-query attention and cache reorder; the SAN-M decoder step's fused norm2 / FSMN window / norm3 kernel and
+// few-query cross-attention for heads of 64 or 128 dims.
 #include <algorithm>
 
 #include "conformer.h"
@@ -106,6 +107,10 @@ __global__ void __launch_bounds__(256) td_embed_kernel(const float* table, const
                                                        int D) {
     const int r = blockIdx.x;
     const float* e = table + (size_t)ids[r] * D;
+    if (!pe_row) {                                   // the SAN-M decoder's bare embedding (scale 1)
+        for (int d = threadIdx.x; d < D; d += 256) x[(size_t)r * D + d] = e[d] * scale;
+        return;
+    }
     for (int d = threadIdx.x; d < D; d += 256) x[(size_t)r * D + d] = e[d] * scale + pe_row[d];
 }
 
@@ -154,6 +159,124 @@ __global__ void __launch_bounds__(256) td_reorder_kernel(const float* src, float
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) d[i] = s[i];
 }
 
+// ---- SAN-M (FsmnDecoder) step
+// the sum over the 256 threads of a workgroup in a fixed order (wave 0 + 1 + 2 + 3), the same value in every thread
+__device__ __forceinline__ float fd_block_sum(float v, float* red) {
+    v = wave_sum(v);
+    __syncthreads();                                 // the previous reduction's readers are done with `red`
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+constexpr int FD_NV = 8;                             // elements per thread: D <= 256 * 8
+
+// one workgroup = one running slot; thread t holds elements t, t + 256, ... of the row in registers through both LayerNorms
+__global__ void __launch_bounds__(256) fd_fsmn_step_kernel(const float* t, const float* x, const float* g2, const float* b2, const float* w,
+                                                           const float* win_in, float* win_out, const int* parents, int pos, int D, int K,
+                                                           int left_pad, const float* g3, const float* b3, float eps, float* x_out,
+                                                           float* xn_out) {
+    __shared__ float red[4];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const size_t row = (size_t)r * D;
+    float v[FD_NV];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < FD_NV; ++i) {
+        const int d = tid + 256 * i;
+        v[i] = d < D ? t[row + d] : 0.f;
+        s += v[i];
+    }
+    float mean = fd_block_sum(s, red) / (float)D;
+    s = 0.f;
+#pragma unroll
+    for (int i = 0; i < FD_NV; ++i)
+        if (tid + 256 * i < D) { const float c = v[i] - mean; s = fmaf(c, c, s); }
+    float rstd = 1.f / sqrtf(fd_block_sum(s, red) / (float)D + eps);
+    const float* src = pos > 0 ? win_in + (size_t)(parents ? parents[r] : r) * K * D : nullptr;
+    float* dst = win_out + (size_t)r * K * D;
+    s = 0.f;
+#pragma unroll
+    for (int i = 0; i < FD_NV; ++i) {
+        const int d = tid + 256 * i;
+        if (d >= D) continue;
+        const float u = (v[i] - mean) * rstd * g2[d] + b2[d];
+        const float* wd = w + (size_t)d * K;
+        float acc = 0.f;
+        for (int k = 0; k < K; ++k) {
+            float c;
+            if (pos > 0) c = k == K - 1 ? u : src[(size_t)(k + 1) * D + d];
+            else c = k == left_pad ? u : 0.f;
+            dst[(size_t)k * D + d] = c;
+            acc = fmaf(wd[k], c, acc);
+        }
+        const float y = x[row + d] + (acc + u);
+        x_out[row + d] = y;
+        v[i] = y;
+        s += y;
+    }
+    if (!g3) return;
+    mean = fd_block_sum(s, red) / (float)D;
+    s = 0.f;
+#pragma unroll
+    for (int i = 0; i < FD_NV; ++i)
+        if (tid + 256 * i < D) { const float c = v[i] - mean; s = fmaf(c, c, s); }
+    rstd = 1.f / sqrtf(fd_block_sum(s, red) / (float)D + eps);
+#pragma unroll
+    for (int i = 0; i < FD_NV; ++i) {
+        const int d = tid + 256 * i;
+        if (d < D) xn_out[row + d] = (v[i] - mean) * rstd * g3[d] + b3[d];
+    }
+}
+
+// td_attention_kernel's mapping for a head of DK = 64 or 128 dims over ONE memory: one wave per (query, head), keys strided over the
+// lanes for the scores, lane = DK / 64 of the output dims
+template <int DK>
+__global__ void __launch_bounds__(64) fd_attention_kernel(const float* q, const float* K, const float* V, int ldkv, int nk, int D,
+                                                          float* out) {
+    const int r = blockIdx.x, h = blockIdx.y, lane = threadIdx.x;
+    extern __shared__ float sc[];                    // nk scores
+    __shared__ float qs[DK];
+#pragma unroll
+    for (int c = 0; c < DK / 64; ++c) qs[lane + 64 * c] = q[(size_t)r * D + h * DK + lane + 64 * c];
+    __syncthreads();
+    const float* Kb = K + h * DK;
+    const float* Vb = V + h * DK;
+    const float scale = DK == 64 ? 0.125f : 0.08838834764831845f;      // 1 / sqrt(DK)
+    float mx = -INFINITY;
+    for (int j = lane; j < nk; j += 64) {
+        const float* kp = Kb + (size_t)j * ldkv;
+        float a = 0.f;
+#pragma unroll 8
+        for (int d = 0; d < DK; d += 4) {
+            const float4 kv = *reinterpret_cast<const float4*>(kp + d);
+            a = fmaf(qs[d], kv.x, a); a = fmaf(qs[d + 1], kv.y, a); a = fmaf(qs[d + 2], kv.z, a); a = fmaf(qs[d + 3], kv.w, a);
+        }
+        a *= scale;
+        sc[j] = a;
+        mx = fmaxf(mx, a);
+    }
+    mx = wave_max(mx);
+    float sum = 0.f;
+    for (int j = lane; j < nk; j += 64) {
+        const float p = expf(sc[j] - mx);
+        sc[j] = p;
+        sum += p;
+    }
+    sum = wave_sum(sum);
+    __syncthreads();
+    float acc[DK / 64];
+#pragma unroll
+    for (int c = 0; c < DK / 64; ++c) acc[c] = 0.f;
+    for (int j = 0; j < nk; ++j) {
+        const float p = sc[j];
+#pragma unroll
+        for (int c = 0; c < DK / 64; ++c) acc[c] = fmaf(p, Vb[(size_t)j * ldkv + lane + 64 * c], acc[c]);
+    }
+#pragma unroll
+    for (int c = 0; c < DK / 64; ++c) out[(size_t)r * D + h * DK + lane + 64 * c] = acc[c] / sum;
+}
+
 }  // namespace
 
 int launch_cf_conv0(const float* feats, int B, int Tin, int F, const float* w, const float* bias, int C, int T1, int F1, int NE,
@@ -194,7 +317,7 @@ int launch_cf_glu_dw(const float* g, const float* dw, const float* dw_bias, cons
 }
 
 int launch_td_embed(const float* table, const int* ids, const float* pe_row, float scale, float* x, int n, int D, hipStream_t stream) {
-    PF_REQUIRE(n > 0 && D > 0 && table && ids && pe_row && x, "td_embed: bad arguments");
+    PF_REQUIRE(n > 0 && D > 0 && table && ids && x, "td_embed: bad arguments");
     hipLaunchKernelGGL(td_embed_kernel, dim3(n), dim3(256), 0, stream, table, ids, pe_row, scale, x, D);
     PF_HIP_TRY(hipGetLastError());
     return 0;
@@ -216,6 +339,32 @@ int launch_td_reorder(const float* src, float* dst, const int* parents, int n, i
     const size_t n4 = (size_t)len * row_floats / 4;
     const unsigned gx = (unsigned)std::min<size_t>((n4 + 255) / 256, 64);
     hipLaunchKernelGGL(td_reorder_kernel, dim3(gx, n, L), dim3(256), 0, stream, src, dst, parents, layer_floats, slot_floats, n4);
+    PF_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_fd_fsmn_step(const float* t, const float* x, const float* g2, const float* b2, const float* w, const float* win_in,
+                        float* win_out, const int* parents, int pos, int n, int D, int K, int left_pad, const float* g3,
+                        const float* b3, float eps, float* x_out, float* xn_out, hipStream_t stream) {
+    PF_REQUIRE(t && x && g2 && b2 && w && win_in && win_out && x_out && win_in != win_out, "fd_fsmn_step: null argument, or one window buffer");
+    PF_REQUIRE(n > 0 && n <= 65535 && D > 0 && D % 4 == 0 && D <= 256 * FD_NV && K >= 1 && K <= 32 && left_pad >= 0 && left_pad < K && pos >= 0,
+               "fd_fsmn_step: D % 4 and <= 2048, 1 <= K <= 32, 0 <= left_pad < K");
+    PF_REQUIRE((g3 == nullptr) == (b3 == nullptr) && (g3 == nullptr || xn_out != nullptr), "fd_fsmn_step: norm3 needs weight, bias and an output");
+    hipLaunchKernelGGL(fd_fsmn_step_kernel, dim3(n), dim3(256), 0, stream, t, x, g2, b2, w, win_in, win_out, parents, pos, D, K, left_pad, g3,
+                       b3, eps, x_out, xn_out);
+    PF_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_fd_attention(const float* q, const float* K, const float* V, int ldkv, int nk, int n, int H, int dk, float* out,
+                        hipStream_t stream) {
+    PF_REQUIRE(q && K && V && out && n > 0 && n <= 65535 && H > 0 && H <= 65535 && nk > 0 && nk <= 12000 && (dk == 64 || dk == 128) &&
+                   ldkv % 4 == 0 && ldkv >= H * dk && ((uintptr_t)K & 15) == 0,
+               "fd_attention: head dim 64 or 128, 1 .. 12000 keys, 16-B aligned rows");
+    if (dk == 64)
+        hipLaunchKernelGGL(fd_attention_kernel<64>, dim3(n, H), dim3(64), sizeof(float) * nk, stream, q, K, V, ldkv, nk, H * dk, out);
+    else
+        hipLaunchKernelGGL(fd_attention_kernel<128>, dim3(n, H), dim3(64), sizeof(float) * nk, stream, q, K, V, ldkv, nk, H * dk, out);
     PF_HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -1,5 +1,5 @@
-// C-ABI layer, Conformer / Transformer ASR: pf_conformer_* and pf_tfencoder_* (the two encoders over one Conv2dSubsampling front)
-// and pf_tdecoder_* (the autoregressive Transformer decoder step); kernels in conformer.hip, attention_relpos.hip and
+// C-ABI layer, Conformer / Transformer / SANM ASR: pf_conformer_* and pf_tfencoder_* (the two encoders over one Conv2dSubsampling front),
+// pf_tdecoder_* (the autoregressive Transformer decoder step) and pf_fsmndecoder_* (the SAN-M decoder step); kernels in conformer.hip, attention_relpos.hip and
 // attention_abs.hip, GEMMs through the shared launchers.
 //
 // Encoder forward over the zero-padded batch [B, Tin, F] (the reference runs Conv2dSubsampling and the convolution module over
@@ -18,6 +18,11 @@
 // Decoder: begin() computes the cross-attention K / V of every layer once per utterance; step() runs all running hypotheses of a
 // beam through the layers (M = n_hyp rows: the small-M weight-streaming GEMMs, fp32 in both modes), appending each layer's
 // self-attention K / V at `pos` of the hypothesis' slot; reorder() gathers the surviving hypotheses' parent slots on the device.
+//
+// SAN-M decoder (pf_fsmndecoder_*, FsmnDecoder.forward_one_step): the same three calls. begin() projects K | V of every cross-attention
+// layer through linear_k_v and zeroes the FSMN windows; step() runs FFN -> fused norm2 / FSMN window / norm3 kernel -> cross-attention per
+// layer; reorder() only records the parents: the FSMN kernel of the next step reads the parent's window of one buffer and writes its own
+// into the other.
 #include <algorithm>
 #include <cmath>
 
@@ -371,6 +376,39 @@ struct Td {
 
 std::string dl(int i) { return "decoders." + std::to_string(i) + "."; }
 
+// ================================================================================================ SAN-M (FsmnDecoder) step
+// One layer table for the three groups of the reference's module: `decoders` (FFN, FSMN memory, cross-attention), `decoders2` (FFN,
+// FSMN memory) and the one FFN-only layer of `decoders3`.
+struct FdLayer { std::string p; bool fsmn, cross; };
+
+struct Fd {
+    pf_fsmndecoder_config cfg;
+    TensorTable tt;
+    std::vector<FdLayer> layers;
+    DevBuf ckv, win, x, y, xn, t, q, a, hid, hidn, logits, ids, par;
+    int T = 0, max_len = 0, max_hyp = 0, filled = 0, cur = 0, n_prev = 0, n_par = 0;
+    int n_fsmn() const { return cfg.n_blocks; }
+    int left_pad() const { return (cfg.kernel_size - 1) / 2 + (cfg.sanm_shift > 0 ? cfg.sanm_shift : 0); }
+    size_t slot() const { return (size_t)cfg.kernel_size * cfg.d_model; }            // the window of one (layer, slot): K columns
+    size_t layer() const { return slot() * max_hyp; }
+    float* win_of(int which, int l) { return win.as<float>() + ((size_t)which * n_fsmn() + l) * layer(); }
+};
+
+// the limits of the handle, one message per field; nullptr = accepted
+const char* fd_refusal(const pf_fsmndecoder_config& c) {
+    if (c.vocab_size < 1) return "fsmndecoder: vocab_size must be positive";
+    if (c.n_heads < 1 || (c.d_model != 64 * c.n_heads && c.d_model != 128 * c.n_heads))
+        return "fsmndecoder: n_heads with d_model: only a head dim of 64 or 128 is built";
+    if (c.d_model > 2048) return "fsmndecoder: d_model above 2048";
+    if (c.ffn_dim < 32 || c.ffn_dim % 32 != 0 || c.ffn_dim > 2048) return "fsmndecoder: ffn_dim must be a multiple of 32 up to 2048";
+    if (c.kernel_size < 1 || c.kernel_size > 32) return "fsmndecoder: kernel_size outside 1 .. 32";
+    if (c.sanm_shift < 0 || (c.kernel_size - 1) / 2 + c.sanm_shift > c.kernel_size - 1)
+        return "fsmndecoder: sanm_shift leaves a negative right padding (kernel_size - 1 - (kernel_size - 1) / 2 - sanm_shift < 0)";
+    if (c.n_blocks < 1 || c.att_layer_num < 1 || c.att_layer_num > c.n_blocks) return "fsmndecoder: att_layer_num outside 1 .. n_blocks";
+    if (!(c.ln_eps > 0.f)) return "fsmndecoder: ln_eps must be positive";
+    return nullptr;
+}
+
 }  // namespace
 
 extern "C" {
@@ -680,7 +718,166 @@ int pf_tdecoder_reorder(pf_tdecoder* hh, const int32_t* parents_host, int32_t n,
     return 0;
 }
 
+pf_fsmndecoder* pf_fsmndecoder_create(const pf_fsmndecoder_config* cfg) {
+    if (!cfg) { set_error("fsmndecoder: null config"); return nullptr; }
+    if (const char* why = fd_refusal(*cfg)) { set_error(why); return nullptr; }     // (before any device call)
+    if (check_device()) return nullptr;
+    const pf_fsmndecoder_config& c = *cfg;
+    std::unique_ptr<Fd> h(new Fd());
+    h->cfg = c;
+    const int D = c.d_model, FF = c.ffn_dim, V = c.vocab_size, K = c.kernel_size;
+    for (int i = 0; i < c.att_layer_num; ++i) h->layers.push_back({dl(i), true, true});
+    for (int i = 0; i < c.n_blocks - c.att_layer_num; ++i) h->layers.push_back({"decoders2." + std::to_string(i) + ".", true, false});
+    h->layers.push_back({"decoders3.0.", false, false});
+    int rc = 0;
+    auto lin = [&](const std::string& n, int o, int i, bool bias = true) {
+        rc |= h->tt.add(n + "weight", (int64_t)o * i);
+        if (bias) rc |= h->tt.add(n + "bias", o);
+    };
+    rc |= h->tt.add("embed.0.weight", (int64_t)V * D);
+    for (const FdLayer& l : h->layers) {
+        lin(l.p + "norm1.", D, 1);
+        lin(l.p + "feed_forward.w_1.", FF, D);
+        lin(l.p + "feed_forward.norm.", FF, 1);
+        lin(l.p + "feed_forward.w_2.", D, FF, false);
+        if (l.fsmn) {
+            lin(l.p + "norm2.", D, 1);
+            rc |= h->tt.add(l.p + "self_attn.fsmn_block.weight", (int64_t)D * K);
+        }
+        if (l.cross) {
+            lin(l.p + "norm3.", D, 1);
+            lin(l.p + "src_attn.linear_q.", D, D);
+            lin(l.p + "src_attn.linear_k_v.", 2 * D, D);
+            lin(l.p + "src_attn.linear_out.", D, D);
+        }
+    }
+    lin("after_norm.", D, 1);
+    lin("output_layer.", V, D);
+    if (rc) return nullptr;
+    return reinterpret_cast<pf_fsmndecoder*>(h.release());
+}
+void pf_fsmndecoder_destroy(pf_fsmndecoder* h) { delete reinterpret_cast<Fd*>(h); }
+int pf_fsmndecoder_set_tensor(pf_fsmndecoder* hh, const char* name, const float* data, int64_t numel) {
+    Fd* h = reinterpret_cast<Fd*>(hh);
+    PF_REQUIRE(h && name && data, "fsmndecoder_set_tensor: null");
+    return h->tt.set(name, data, numel);
+}
+int pf_fsmndecoder_missing(const pf_fsmndecoder* hh) {
+    const Fd* h = reinterpret_cast<const Fd*>(hh);
+    return h ? h->tt.missing() : -1;
+}
+int pf_fsmndecoder_begin(pf_fsmndecoder* hh, const float* memory, int32_t T, int32_t max_len, int32_t max_hyp, void* stream) {
+    Fd* h = reinterpret_cast<Fd*>(hh);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    PF_REQUIRE(h && memory && T > 0 && T <= 12000 && max_len > 0 && max_len <= 5000 && max_hyp > 0 && max_hyp <= 256,
+               "fsmndecoder_begin: 1 .. 12000 memory rows, 1 .. 5000 positions (max_len), 1 .. 256 hypotheses (max_hyp)");
+    if (h->tt.require_all("fsmndecoder")) return -3;
+    const int D = h->cfg.d_model, LA = h->cfg.att_layer_num;
+    h->T = T; h->max_len = max_len; h->max_hyp = max_hyp; h->filled = 0; h->cur = 0; h->n_prev = 0; h->n_par = 0;
+    const size_t n = (size_t)max_hyp, wbytes = sizeof(float) * 2 * h->n_fsmn() * h->layer();
+    if (h->ckv.ensure(sizeof(float) * (size_t)LA * T * 2 * D) || h->win.ensure(wbytes) || h->x.ensure(sizeof(float) * n * D) ||
+        h->y.ensure(sizeof(float) * n * D) || h->xn.ensure(sizeof(float) * n * D) || h->t.ensure(sizeof(float) * n * D) ||
+        h->q.ensure(sizeof(float) * n * D) || h->a.ensure(sizeof(float) * n * D) || h->hid.ensure(sizeof(float) * n * h->cfg.ffn_dim) ||
+        h->hidn.ensure(sizeof(float) * n * h->cfg.ffn_dim) || h->logits.ensure(sizeof(float) * n * h->cfg.vocab_size) ||
+        h->ids.ensure(sizeof(int32_t) * n) || h->par.ensure(sizeof(int32_t) * n))
+        return -2;
+    PF_HIP_TRY(hipMemsetAsync(h->win.p, 0, wbytes, s));
+    int rc;
+    for (int l = 0; l < LA; ++l) {                   // K | V of the whole memory, once per utterance: one GEMM through linear_k_v
+        const std::string p = h->layers[l].p + "src_attn.linear_k_v.";
+        GemmArgs g{};
+        g.A = memory; g.lda = D; g.ldw = D; g.ldc = 2 * D; g.M = T; g.N = 2 * D; g.K = D;
+        g.W = h->tt.get(p + "weight"); g.bias = h->tt.get(p + "bias"); g.C = h->ckv.as<float>() + (size_t)l * T * 2 * D;
+        if ((rc = launch_gemm_f32(g, s))) return rc;
+    }
+    return 0;
+}
+int pf_fsmndecoder_step(pf_fsmndecoder* hh, const int32_t* tokens_host, int32_t pos, int32_t n, float* logp, void* stream) {
+    Fd* h = reinterpret_cast<Fd*>(hh);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    PF_REQUIRE(h && tokens_host && logp && h->max_len > 0, "fsmndecoder_step: null argument or no begin()");
+    PF_REQUIRE(n > 0 && n <= h->max_hyp && pos >= 0 && pos < h->max_len && pos == h->filled,
+               "fsmndecoder_step: n_hyp <= max_hyp, every position once and in order below max_len");
+    // whose window a slot continues: the parents of the last reorder(), else its own (then it must have run at the last position)
+    PF_REQUIRE(pos == 0 || (h->n_par ? n == h->n_par : n <= h->n_prev),
+               "fsmndecoder_step: n_hyp differs from the last reorder(), or a slot without a parent");
+    const pf_fsmndecoder_config& c = h->cfg;
+    const int D = c.d_model, FF = c.ffn_dim, V = c.vocab_size, H = c.n_heads, T = h->T, K = c.kernel_size;
+    for (int i = 0; i < n; ++i) PF_REQUIRE(tokens_host[i] >= 0 && tokens_host[i] < V, "fsmndecoder_step: token id outside the vocabulary");
+    if (upload_h2d(h->ids.p, tokens_host, sizeof(int32_t) * n, s)) return -2;
+    int rc;
+    StreamModeScope small_m;                         // every GEMM of the step has M = n_hyp rows: the weight-streaming kernel
+    float *x = h->x.as<float>(), *y = h->y.as<float>(), *xn = h->xn.as<float>(), *t = h->t.as<float>(), *q = h->q.as<float>(),
+          *a = h->a.as<float>(), *hid = h->hid.as<float>(), *hidn = h->hidn.as<float>();
+    if ((rc = launch_td_embed(h->tt.get("embed.0.weight"), h->ids.as<int>(), nullptr, 1.f, x, n, D, s))) return rc;      // bare: no positional row
+    auto W = [&](const std::string& nme) { return h->tt.get(nme); };
+    const int* parents = pos > 0 && h->n_par ? h->par.as<int>() : nullptr;
+    int lf = 0, lc = 0;
+    for (const FdLayer& l : h->layers) {
+        const std::string& p = l.p;
+        // t = w_2(LayerNorm_FF(relu(w_1(norm1(x)))))
+        if ((rc = layernorm(x, D, W(p + "norm1.weight"), W(p + "norm1.bias"), xn, D, n, D, D, c.ln_eps, s))) return rc;
+        if ((rc = gemm_simple(xn, D, W(p + "feed_forward.w_1.weight"), D, W(p + "feed_forward.w_1.bias"), hid, FF, n, FF, D, 1, nullptr, 0,
+                              nullptr, 0, s)))
+            return rc;
+        if ((rc = layernorm(hid, FF, W(p + "feed_forward.norm.weight"), W(p + "feed_forward.norm.bias"), hidn, FF, n, FF, FF, c.ln_eps, s)))
+            return rc;
+        if ((rc = gemm_simple(hidn, FF, W(p + "feed_forward.w_2.weight"), FF, nullptr, l.fsmn ? t : y, D, n, D, FF, 0, nullptr, 0, nullptr, 0, s)))
+            return rc;
+        if (!l.fsmn) { std::swap(x, y); continue; }  // decoders3: no residual
+        // y = x + fsmn(norm2(t)), xn = norm3(y)
+        if ((rc = launch_fd_fsmn_step(t, x, W(p + "norm2.weight"), W(p + "norm2.bias"), W(p + "self_attn.fsmn_block.weight"),
+                                      h->win_of(h->cur, lf), h->win_of(h->cur ^ 1, lf), parents, pos, n, D, K, h->left_pad(),
+                                      l.cross ? W(p + "norm3.weight") : nullptr, l.cross ? W(p + "norm3.bias") : nullptr, c.ln_eps, y,
+                                      l.cross ? xn : nullptr, s)))
+            return rc;
+        ++lf;
+        std::swap(x, y);
+        if (!l.cross) continue;
+        if ((rc = gemm_simple(xn, D, W(p + "src_attn.linear_q.weight"), D, W(p + "src_attn.linear_q.bias"), q, D, n, D, D, 0, nullptr, 0,
+                              nullptr, 0, s)))
+            return rc;
+        const float* kv = h->ckv.as<float>() + (size_t)lc * T * 2 * D;
+        ++lc;
+        if ((rc = launch_fd_attention(q, kv, kv + D, 2 * D, T, n, H, D / H, a, s))) return rc;
+        if ((rc = gemm_simple(a, D, W(p + "src_attn.linear_out.weight"), D, W(p + "src_attn.linear_out.bias"), y, D, n, D, D, 0, x, D,
+                              nullptr, 0, s)))
+            return rc;
+        std::swap(x, y);
+    }
+    if ((rc = layernorm(x, D, W("after_norm.weight"), W("after_norm.bias"), xn, D, n, D, D, c.ln_eps, s))) return rc;
+    if ((rc = gemm_simple(xn, D, W("output_layer.weight"), D, W("output_layer.bias"), h->logits.as<float>(), V, n, V, D, 0, nullptr, 0, nullptr,
+                          0, s)))
+        return rc;
+    if ((rc = launch_log_softmax(h->logits.as<float>(), V, logp, V, n, V, s))) return rc;
+    h->filled = pos + 1; h->cur ^= 1; h->n_prev = n; h->n_par = 0;
+    return 0;
+}
+int pf_fsmndecoder_reorder(pf_fsmndecoder* hh, const int32_t* parents_host, int32_t n, void* stream) {
+    Fd* h = reinterpret_cast<Fd*>(hh);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    PF_REQUIRE(h && parents_host && h->max_len > 0 && n > 0 && n <= h->max_hyp, "fsmndecoder_reorder: null argument, no begin() or n_hyp > max_hyp");
+    for (int i = 0; i < n; ++i) PF_REQUIRE(parents_host[i] >= 0 && parents_host[i] < h->max_hyp, "fsmndecoder_reorder: parent slot out of range");
+    if (h->filled == 0) return 0;
+    for (int i = 0; i < n; ++i) PF_REQUIRE(parents_host[i] < h->n_prev, "fsmndecoder_reorder: parent slot did not run at the last position");
+    // no launch: the FSMN kernel of the next step reads window parents[k] of the buffer the last step wrote and writes window k of
+    // the other one, so a parent may repeat or be dropped and nothing is overwritten before it is read
+    if (upload_h2d(h->par.p, parents_host, sizeof(int32_t) * n, s)) return -2;
+    h->n_par = n;
+    return 0;
+}
+
 // single-kernel hooks (tests)
+int pf_k_fsmn_step(const float* t, const float* x, const float* g2, const float* b2, const float* w, const float* win_in, float* win_out,
+                   const int32_t* parents_dev, int32_t pos, int32_t n, int32_t D, int32_t K, int32_t left_pad, const float* g3, const float* b3,
+                   float eps, float* x_out, float* xn_out, void* stream) {
+    return launch_fd_fsmn_step(t, x, g2, b2, w, win_in, win_out, parents_dev, pos, n, D, K, left_pad, g3, b3, eps, x_out, xn_out,
+                               reinterpret_cast<hipStream_t>(stream));
+}
+int pf_k_cross_attention_step(const float* q, const float* kv, int32_t T, int32_t n, int32_t H, int32_t dk, float* out, void* stream) {
+    PF_REQUIRE(kv && H > 0 && (dk == 64 || dk == 128), "cross_attention_step: head dim 64 or 128");
+    return launch_fd_attention(q, kv, kv + H * dk, 2 * H * dk, T, n, H, dk, out, reinterpret_cast<hipStream_t>(stream));
+}
 int pf_k_relpos_attention(const float* qkv, const float* P, const float* u, const float* v, const int32_t* klens_dev, int32_t B, int32_t T,
                           int32_t H, int32_t legacy, float* out, void* stream) {
     return launch_cf_relpos_attention(qkv, P, u, v, klens_dev, B, T, H, legacy, out, reinterpret_cast<hipStream_t>(stream));

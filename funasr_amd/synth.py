@@ -407,35 +407,68 @@ def transformer_state_dict(seed: int, model) -> Dict[str, torch.Tensor]:
     return conformer_state_dict(seed, model)
 
 
+def sanm_conf(output_size: int = 128, attention_heads: int = 2, linear_units: int = 64, enc_blocks: int = 2, dec_blocks: int = 3,
+              att_layer_num: int = 2, kernel: int = 11, sanm_shfit="default", enc_kernel: int = 11, ctc_weight: float = 0.3, vocab: int = 60,
+              input_size: int = 80) -> dict:
+    """constructor arguments of a SANM model (the layout of funasr/models/sanm/template.yaml) at a chosen size. sanm_shfit "default"
+    leaves the decoder's key out: the constructor's (kernel - 1) // 2, the causal memory for an odd kernel"""
+    enc = {"output_size": output_size, "attention_heads": attention_heads, "linear_units": linear_units, "num_blocks": enc_blocks,
+           "dropout_rate": 0.1, "positional_dropout_rate": 0.1, "attention_dropout_rate": 0.1, "input_layer": "pe",
+           "pos_enc_class": "SinusoidalPositionEncoder", "normalize_before": True, "kernel_size": enc_kernel, "sanm_shfit": 0,
+           "selfattention_layer_type": "sanm"}
+    dec = {"attention_heads": attention_heads, "linear_units": linear_units, "num_blocks": dec_blocks, "dropout_rate": 0.1,
+           "positional_dropout_rate": 0.1, "self_attention_dropout_rate": 0.1, "src_attention_dropout_rate": 0.1,
+           "att_layer_num": att_layer_num, "kernel_size": kernel}
+    if sanm_shfit != "default":
+        dec["sanm_shfit"] = sanm_shfit
+    return {"encoder": "SANMEncoder", "encoder_conf": enc, "decoder": "FsmnDecoder", "decoder_conf": dec, "ctc_weight": ctc_weight,
+            "lsm_weight": 0.1, "length_normalized_loss": True, "input_size": input_size, "vocab_size": vocab}
+
+
+# funasr/models/sanm/template.yaml: D 512, 4 heads (d_k 128), FFN 2048, 50 encoder and 16 decoder blocks (all with cross-attention),
+# kernel 11 with sanm_shfit 0 (five zero columns between the first token and the second), no CTC head; 7 x 80 LFR features
+SANM_TEMPLATE = dict(output_size=512, attention_heads=4, linear_units=2048, enc_blocks=50, dec_blocks=16, att_layer_num=16, kernel=11,
+                     sanm_shfit=0, ctc_weight=0.0, vocab=8404, input_size=560)
+
+
+def sanm_state_dict(seed: int, model) -> Dict[str, torch.Tensor]:
+    """synthetic weights in the layout of `model` (a SANM module or the reference's): the tensors of conformer_state_dict (the FSMN
+    taps [D, 1, K] fan-in scaled like every other convolution), drawn in the SORTED order of the keys -- this package's modules and
+    the reference's list the same keys in different orders"""
+    g = torch.Generator().manual_seed(seed)
+    shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
+    return {k: _synthetic_tensor(k, shapes[k], g) for k in sorted(shapes)}
+
+
+def _synthetic_tensor(k: str, shp: tuple, g: torch.Generator) -> torch.Tensor:
+    """one tensor of conformer_state_dict, by the name and shape of its key"""
+    if k.endswith("num_batches_tracked"):
+        return torch.tensor(0, dtype=torch.long)
+    if k.endswith("running_mean"):
+        return 0.2 * torch.randn(shp, generator=g)
+    if k.endswith("running_var"):
+        return 0.5 + 1.5 * torch.rand(shp, generator=g)
+    if k.endswith("pos_bias_u") or k.endswith("pos_bias_v"):
+        return 0.1 * torch.randn(shp, generator=g)
+    if k.endswith("embed.0.weight") and len(shp) == 2:
+        return torch.randn(shp, generator=g) * (1.0 / shp[1]) ** 0.5
+    if k.endswith("ctc_lo.weight") or k.endswith("output_layer.weight"):      # logits of order 4: few near-ties between classes
+        return torch.randn(shp, generator=g) * 4.0 * (1.0 / shp[1]) ** 0.5
+    if len(shp) == 1:
+        is_norm = "norm" in k
+        return (1.0 + 0.2 * torch.randn(shp, generator=g)) if (is_norm and k.endswith("weight")) else 0.1 * torch.randn(shp, generator=g)
+    fan_in = 1
+    for d in shp[1:]:
+        fan_in *= d
+    return torch.randn(shp, generator=g) * (1.0 / fan_in) ** 0.5
+
+
 def conformer_state_dict(seed: int, model) -> Dict[str, torch.Tensor]:
     """synthetic weights in the layout of `model` (a Conformer module or the reference's): fan-in scaled convs / linears, LayerNorms
     near identity, NON-trivial BatchNorm statistics (weight near 1, bias / running_mean off zero, running_var in [0.5, 2]),
-    relative-position biases of order 0.1, a token embedding of order 1 / sqrt(D)"""
+    relative-position biases of order 0.1, a token embedding of order 1 / sqrt(D); drawn in the order of the module's state dict"""
     g = torch.Generator().manual_seed(seed)
-    sd = {}
-    for k, v in model.state_dict().items():
-        shp = tuple(v.shape)
-        if k.endswith("num_batches_tracked"):
-            sd[k] = torch.tensor(0, dtype=torch.long)
-        elif k.endswith("running_mean"):
-            sd[k] = 0.2 * torch.randn(shp, generator=g)
-        elif k.endswith("running_var"):
-            sd[k] = 0.5 + 1.5 * torch.rand(shp, generator=g)
-        elif k.endswith("pos_bias_u") or k.endswith("pos_bias_v"):
-            sd[k] = 0.1 * torch.randn(shp, generator=g)
-        elif k.endswith("embed.0.weight") and len(shp) == 2:
-            sd[k] = torch.randn(shp, generator=g) * (1.0 / shp[1]) ** 0.5
-        elif k.endswith("ctc_lo.weight") or k.endswith("output_layer.weight"):      # logits of order 4: few near-ties between classes
-            sd[k] = torch.randn(shp, generator=g) * 4.0 * (1.0 / shp[1]) ** 0.5
-        elif len(shp) == 1:
-            is_norm = "norm" in k
-            sd[k] = (1.0 + 0.2 * torch.randn(shp, generator=g)) if (is_norm and k.endswith("weight")) else 0.1 * torch.randn(shp, generator=g)
-        else:
-            fan_in = 1
-            for d in shp[1:]:
-                fan_in *= d
-            sd[k] = torch.randn(shp, generator=g) * (1.0 / fan_in) ** 0.5
-    return sd
+    return {k: _synthetic_tensor(k, tuple(v.shape), g) for k, v in model.state_dict().items()}
 
 
 def transducer_conf(encoder: str = "ConformerEncoder", output_size: int = 128, attention_heads: int = 2, linear_units: int = 256,

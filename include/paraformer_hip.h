@@ -574,6 +574,46 @@ int pf_tdecoder_step(pf_tdecoder* h, const int32_t* tokens_host, int32_t pos, in
 /* slot k < n_hyp takes the cache of slot parents_host[k] (a gather on the device; a parent may repeat or be dropped). No sync. */
 int pf_tdecoder_reorder(pf_tdecoder* h, const int32_t* parents_host, int32_t n_hyp, void* stream);
 
+/* ---- SAN-M autoregressive decoder (funasr/models/sanm/decoder.py FsmnDecoder.forward_one_step), the same stepper for a beam search
+ * on the host. Tensor names are the module's state_dict keys: "embed.0.weight" (a bare embedding: no scale, no positional row),
+ * "decoders.{i}.*" for i < att_layer_num (norm1, feed_forward.{w_1, norm, w_2} with w_2 without bias, norm2,
+ * self_attn.fsmn_block.weight [D, 1, K], norm3, src_attn.{linear_q, linear_k_v, linear_out}), "decoders2.{j}.*" for the
+ * n_blocks - att_layer_num layers without cross-attention, "decoders3.0.*" (norm1 and feed_forward only; applied WITHOUT a residual),
+ * "after_norm.*", "output_layer.*".
+ * Limits (create refuses with a message naming the field): head dim 64 or 128, d_model <= 2048, ffn_dim % 32 == 0 and <= 2048,
+ * 1 <= kernel_size <= 32, sanm_shift >= 0 with a right padding kernel_size - 1 - (kernel_size - 1) / 2 - sanm_shift >= 0,
+ * 1 <= att_layer_num <= n_blocks. sanm_shift is the RESOLVED value (the module's default None is (kernel_size - 1) / 2).
+ * State on the device: K | V of every cross-attention layer (one GEMM through linear_k_v per layer, by begin) and, per FSMN layer and
+ * hypothesis slot, the K-column window of the memory block in two buffers: the window at step n is the last K columns of
+ * [0] * L + [x_0] + [0] * R + [x_1 .. x_n] with L = (K - 1) / 2 + sanm_shift and R = K - 1 - L -- the reference's cache rule, which
+ * is the causal memory only when R == 0. All GEMMs of a step are the fp32 small-M weight-streaming kernel. */
+typedef struct pf_fsmndecoder pf_fsmndecoder;
+typedef struct pf_fsmndecoder_config {
+    int32_t vocab_size, d_model, n_heads, ffn_dim, n_blocks, att_layer_num, kernel_size, sanm_shift;
+    float ln_eps;
+} pf_fsmndecoder_config;
+pf_fsmndecoder* pf_fsmndecoder_create(const pf_fsmndecoder_config* cfg);
+void pf_fsmndecoder_destroy(pf_fsmndecoder* h);
+int pf_fsmndecoder_set_tensor(pf_fsmndecoder* h, const char* name, const float* data, int64_t numel);
+int pf_fsmndecoder_missing(const pf_fsmndecoder* h);
+/* a new utterance: memory_dev [T, d_model]; the windows of max_hyp slots are zeroed (max_len <= 5000, max_hyp <= 256). No sync. */
+int pf_fsmndecoder_begin(pf_fsmndecoder* h, const float* memory_dev, int32_t T, int32_t max_len, int32_t max_hyp, void* stream);
+/* slot k < n_hyp gets token tokens_host[k] at position pos (every position once, in order: pos == positions run so far); its window
+ * continues the one of slot parents[k] of the last reorder(), or its own when no reorder() came since the last step
+ * -> logp_dev [n_hyp, vocab_size] log-probabilities of the next token. No sync. */
+int pf_fsmndecoder_step(pf_fsmndecoder* h, const int32_t* tokens_host, int32_t pos, int32_t n_hyp, float* logp_dev, void* stream);
+/* slot k < n_hyp of the NEXT step takes the window of slot parents_host[k] of the last one (a parent may repeat or be dropped; every
+ * parent ran at the last position). Records the parents only: the next step's FSMN kernel reads the parent's window. No sync. */
+int pf_fsmndecoder_reorder(pf_fsmndecoder* h, const int32_t* parents_host, int32_t n_hyp, void* stream);
+/* single-kernel hooks of the step (tests; see csrc/conformer.h): the fused norm2 + FSMN window + residual (+ norm3) kernel over
+ * windows win_in_dev / win_out_dev [slots, K, D] (parents_dev NULL: slot k continues its own), and the few-query cross-attention
+ * over kv_dev [T, 2 H dk] (K | V) for dk 64 or 128 */
+int pf_k_fsmn_step(const float* t_dev, const float* x_dev, const float* g2_dev, const float* b2_dev, const float* w_dev,
+                   const float* win_in_dev, float* win_out_dev, const int32_t* parents_dev, int32_t pos, int32_t n, int32_t D, int32_t K,
+                   int32_t left_pad, const float* g3_dev, const float* b3_dev, float eps, float* x_out_dev, float* xn_out_dev, void* stream);
+int pf_k_cross_attention_step(const float* q_dev, const float* kv_dev, int32_t T, int32_t n, int32_t H, int32_t dk, float* out_dev,
+                              void* stream);
+
 /* single-kernel hooks of the two above (tests): the relative-position attention (qkv_dev [B T, 3 D] q | k | v, P_dev [T or 2 T - 1, D],
  * u_dev / v_dev [H, 64], klens_dev [B] -> out_dev [B T, D]; see csrc/conformer.h) and the GLU + depthwise conv + BatchNorm + Swish
  * row kernel (g_dev [B T, 2 D], dw_dev [D, taps], BatchNorm folded to scale / shift [D] -> y_dev [B T, D]) */
