@@ -318,6 +318,7 @@ SIGNATURES = {
     "pf_k_attention_f32": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _f32, _vp]),
     "pf_k_attention_f32_two_source": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32,
                                                 _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
+    "pf_k_attention_f32_dk": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
     "pf_k_attention_small": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
     "pf_k_gather_rows": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp]),
     "pf_k_attention_split3": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _f32, _vp]),

@@ -234,6 +234,43 @@ def load_audio_list(data_in, fs: int = 16000, audio_fs: int = 16000) -> List[tor
     return [load_audio(data_in, fs, audio_fs)]
 
 
+def load_text(item, tokenizer) -> List[int]:
+    """The `"text"` case of `load_audio_text_image_video` (load_utils.py:144-146,156-157): a path to a text file is read and
+    stripped, any other string is the text itself; both go through `tokenizer.encode`. Beyond the reference: a list of ints is taken
+    as token ids that are already encoded (tools/bench_aligner.py feeds transcripts that way)."""
+    if tokenizer is None:
+        raise ValueError("data_type 'text' needs a tokenizer (the model directory names none)")
+    if isinstance(item, (list, tuple)) and all(isinstance(t, int) for t in item):
+        return list(item)                                   # already token ids
+    if not isinstance(item, str):
+        raise TypeError(f"unsupported text input type {type(item)}")
+    if os.path.exists(item):
+        with open(item, "r", encoding="utf-8") as f:
+            item = f.read().strip()
+    return list(tokenizer.encode(item))
+
+
+def load_audio_text(data_in, fs: int = 16000, audio_fs: int = 16000, data_type=("sound", "text"), tokenizer=None) -> List[list]:
+    """The tuple branch of `load_audio_text_image_video` (load_utils.py:67-87): `data_in` is a list of items, every item a tuple
+    with one input per entry of the tuple `data_type`; -> one list per entry (waveforms for "sound", token ids for "text")."""
+    if not isinstance(data_type, (list, tuple)):
+        raise TypeError("load_audio_text: data_type is a tuple such as ('sound', 'text')")
+    if not isinstance(data_in, (list, tuple)):
+        raise TypeError("load_audio_text: the batch is a list of tuples, one per item")
+    out: List[list] = [[] for _ in data_type]
+    for item in data_in:
+        if not isinstance(item, (list, tuple)) or len(item) != len(data_type):
+            raise ValueError(f"load_audio_text: every item holds {len(data_type)} inputs {tuple(data_type)}, got {item!r}")
+        for j, (kind, piece) in enumerate(zip(data_type, item)):
+            if kind in (None, "sound"):
+                out[j].append(load_audio(piece, fs, audio_fs))
+            elif kind == "text":
+                out[j].append(load_text(piece, tokenizer))
+            else:
+                raise NotImplementedError(f"load_audio_text: data_type {kind!r} is not built (sound, text)")
+    return out
+
+
 def batch_to_features(data_in, data_lengths, frontend, kwargs, uploader=None):
     """The head of every model's `inference` (funasr/models/paraformer/model.py:576-595, sense_voice/model.py:948-975): waveforms
     (paths / arrays / tensors / bytes) or ready features -> (speech, speech_lengths, meta_data). `uploader`

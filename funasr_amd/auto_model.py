@@ -51,6 +51,7 @@ from . import ct_transformer as _ct_transformer  # noqa: F401  (registers CTTran
 from . import emotion2vec as _emotion2vec  # noqa: F401  (registers Emotion2vec)
 from . import fsmn_vad as _fsmn_vad  # noqa: F401  (registers FSMN / FsmnVADStreaming)
 from . import kws as _kws  # noqa: F401  (registers FsmnKWS / SanmKWS)
+from . import monotonic_aligner as _monotonic_aligner  # noqa: F401  (registers MonotonicAligner)
 from . import paraformer as _paraformer  # noqa: F401  (registers the model classes)
 from . import paraformer_v2 as _paraformer_v2  # noqa: F401  (registers Paraformer_v2_community + its decoder)
 from . import paraformer_streaming as _paraformer_streaming  # noqa: F401  (WavFrontendOnline)
@@ -101,6 +102,21 @@ def prepare_data_iterator(data_in, input_len=None, data_type=None, key=None) -> 
         else:
             k = key if key is not None else os.path.splitext(os.path.basename(data_in))[0]
             data_list, key_list = [data_in], [k]
+    elif isinstance(data_in, (list, tuple)) and data_type is not None and isinstance(data_type, (list, tuple)):
+        # several inputs per item (:385-394; MonotonicAligner's (sound, text)): every input is expanded on its own and the i-th
+        # items are zipped into one tuple; as there, the keys are those of the LAST input
+        # (`input_len` and `key` do not reach the inputs, as there; unlike there, inputs that do not pair up are an error, not a
+        #  silent truncation to the shortest)
+        if len(data_in) == 0 or len(data_in) != len(data_type):
+            raise ValueError(f"{len(data_in)} inputs for data_type {tuple(data_type)}: pass one input per entry of data_type")
+        columns = []
+        for data_in_i, data_type_i in zip(data_in, data_type):
+            key_list, column = prepare_data_iterator(data_in_i, data_type=data_type_i)
+            columns.append(column)
+        if len({len(c) for c in columns}) != 1:
+            raise ValueError("the inputs of data_type " + str(tuple(data_type)) + " hold " + ", ".join(str(len(c)) for c in columns) +
+                             " items: every item needs one of each")
+        data_list = list(zip(*columns))
     elif isinstance(data_in, (list, tuple)):
         # the reference's loop (:397-405) keeps ONE `key` variable: a given key (whatever object it is) labels every item, a file
         # path sets it to its name, and the first random key is reused for the items after it -- reproduced as it is, the records'

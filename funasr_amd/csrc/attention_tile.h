@@ -1,5 +1,5 @@
 // The tile step of the swapped-MFMA attention kernels: attention_f32_kernel, attention_f32_dma_kernel, attention_bf16_kernel,
-// attention_split3_kernel and relpos_attention_kernel.
+// attention_split3_kernel, relpos_attention_kernel and attention_mid_kernel.
 //
 // Mapping. A wave owns 32 queries and a lane owns ONE of them (q = lane & 31); both products are issued "swapped", so the keys
 // of a 32-key tile and then the output channels run over the lane's accumulator registers:
@@ -103,15 +103,18 @@ __device__ __forceinline__ void tile_pv(const float* Vs, int hh, int idx, const 
 }
 
 // o / l_run -> this query's row at element offset orow: fp32 into O, or with O3 its three bf16 planes (o_plane elements apart:
-// the out-projection's operand in bf16x3 mode)
-template <int ND>
+// the out-projection's operand in bf16x3 mode). CH < 32 ND (a multiple of 8: attention_mid.hip) bounds the channels written:
+// a lane's float4 covers channels [32 d + 8 g + 4 hh, + 4), so whole groups g fall on either side of the bound
+template <int ND, int CH = 32 * ND>
 __device__ __forceinline__ void tile_store(const floatx16 (&o)[ND], float l_run, int hh, size_t orow, float* O, unsigned short* O3,
                                            size_t o_plane) {
+    static_assert(CH % 8 == 0 && CH <= 32 * ND, "tile_store: the channel bound is a multiple of 8");
     const float inv = 1.0f / l_run;
 #pragma unroll
     for (int d = 0; d < ND; ++d)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
+            if (d * 32 + 8 * g >= CH) continue;
             const float t[4] = {o[d][4 * g + 0] * inv, o[d][4 * g + 1] * inv, o[d][4 * g + 2] * inv, o[d][4 * g + 3] * inv};
             const size_t off = orow + d * 32 + 8 * g + 4 * hh;
             if (O3) store_split3x4(O3 + off, o_plane, t);

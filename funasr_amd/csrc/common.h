@@ -546,6 +546,9 @@ int launch_asf_scores(const float* Q, int ldq, const float* K, int ldk, float* P
                       int klen, float scale, hipStream_t stream);
 bool attention_small_applicable(const AttnArgs& a, int dk);
 int launch_attention_small(const AttnArgs& a, int dk, hipStream_t stream);
+// heads of d_k = 80 / 96 in exact fp32 on the matrix cores, any Tk: one key/value source, key-padding mask, fp32 output (attention_mid.hip)
+bool attention_mid_applicable(int dk);
+int launch_attention_mid(const AttnArgs& a, int dk, hipStream_t stream);
 // out[i] = table[ids[i]] (embedding lookup; ids clamped to [0, rows))
 // out[map[i], 0..n_per) = in[i, 0..n_per): int32 rows scattered through a row map (token ids back to the padded [B, N] layout)
 int launch_scatter_i32(const int* in, const int* map, int* out, int n, hipStream_t stream);

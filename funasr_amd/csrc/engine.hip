@@ -169,6 +169,13 @@ int attention(const AttnArgs& a, double flops, hipStream_t s, bool x3, int dk, b
     AttnArgs f = a;
     f.few_q = 0;
     if ((dk != 128 || x3) && (f.fs_in || f.O2)) { set_error("attention: the FSMN rider exists in the few-query fp32 kernel only"); return -1; }
+    if (attention_mid_applicable(dk)) {                                               // MonotonicAligner sized heads: the plain call only
+        const char* missing = x3 ? "a bf16x3 form" : f.K2 ? "a second key/value source" : (f.O3 || f.O2) ? "plane outputs"
+                              : f.mask_mode != 0 ? "the causal / VAD masks" : nullptr;
+        if (missing) { set_error(std::string("attention: heads of d_k = 80 / 96 (attention_mid.hip) have no kernel with ") + missing); return -1; }
+        f.app_rows = 0;
+        return launch_attention_mid(f, dk, s);
+    }
     if (dk != 128) { f.app_rows = 0; return launch_attention_small(f, dk, s); }      // CT-Transformer sized heads
     if (x3) { f.app_rows = 0; return launch_attention_split3(f, s); }
     f.few_q = (g_stream_mode || g_skinny_max_m > 0) ? 1 : 0;   // by caller (streaming step; g_skinny_max_m: test hook)

@@ -415,7 +415,10 @@ int encoder_block(Encoder* e, const EncLayerW& w, float* x_in, int ld_in, float*
     aa.O = ctx; aa.ldo = D; aa.klens = lens; aa.B = B; aa.H = c.n_heads; aa.Tq = T; aa.Tk = T;
     aa.scale = powf((float)(D / c.n_heads), -0.5f);
     if (e->cur_mask_mode && !cc) {
-        if (D / c.n_heads > 64) { set_error("encoder: the causal / VAD masks are built for heads of d_k <= 64 (attention_small.hip)"); return -1; }
+        if (D / c.n_heads > 64) {
+            set_error("encoder: the causal / VAD masks are built for heads of d_k <= 64 (attention_small.hip), not d_k = " + std::to_string(D / c.n_heads));
+            return -1;
+        }
         aa.mask_mode = e->cur_mask_mode; aa.vad_pos = e->vad_dev.as<int>();
     }
     if (cc && cc->cap > 0) {
@@ -481,11 +484,11 @@ pf_encoder* pf_encoder_create(const pf_encoder_config* cfg) {
     if (check_device()) return nullptr;
     const pf_encoder_config& c = *cfg;
     const int dk = (c.n_heads > 0 && c.d_model > 0) ? c.d_model / c.n_heads : 0;
-    if (c.d_model <= 0 || c.n_heads <= 0 || c.d_model % c.n_heads || !(dk == 128 || (dk <= 64 && dk % 4 == 0)) ||
+    if (c.d_model <= 0 || c.n_heads <= 0 || c.d_model % c.n_heads || !(dk == 128 || attention_mid_applicable(dk) || (dk <= 64 && dk % 4 == 0)) ||
         c.input_dim % 4 || c.ffn_dim % 32 || c.d_model % 32 || c.n_blocks < 1 || c.tp_blocks < 0 ||
         c.kernel_size != 11) {
-        set_error("encoder: unsupported config (need d_model/n_heads == 128, or <= 64 for the small-head kernel; "
-                  "kernel_size == 11, dims % 32 == 0)");
+        set_error("encoder: unsupported config (need d_model/n_heads == 128, 80 or 96 (attention_mid.hip, fp32 mode only), or <= 64 for "
+                  "the small-head kernel; kernel_size == 11, dims % 32 == 0)");
         return nullptr;
     }
     std::unique_ptr<Encoder> e(new Encoder());
@@ -535,6 +538,11 @@ int pf_encoder_set_tensor(pf_encoder* eh, const char* name, const float* data, i
 int pf_encoder_set_precision(pf_encoder* eh, int32_t mode) {
     Encoder* e = reinterpret_cast<Encoder*>(eh);
     PF_REQUIRE(e && mode >= 0 && mode <= 3, "encoder_set_precision: mode must be 0 (fp32 MFMA), 1 (bf16 operands), 2 (fp32 via bf16x3) or 3 (fp32 via f16x2)");
+    const int dk = e->cfg.d_model / e->cfg.n_heads;
+    if (mode != 0 && attention_mid_applicable(dk)) {
+        set_error("encoder_set_precision: heads of d_k = " + std::to_string(dk) + " run in the fp32 mode only (attention_mid.hip has no bf16 / bf16x3 / f16x2 form)");
+        return -1;
+    }
     e->precision = mode;
     return 0;
 }

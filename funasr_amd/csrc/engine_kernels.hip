@@ -363,6 +363,16 @@ int pf_k_attention_small(const float* Q, int32_t ldq, const float* K, int32_t ld
     aa.B = B; aa.H = H; aa.Tq = Tq; aa.Tk = Tk; aa.scale = scale;
     return launch_attention_small(aa, d_k, reinterpret_cast<hipStream_t>(stream));
 }
+/* heads of d_k = 80 / 96 (attention_mid.hip), through the dispatch the encoder uses */
+int pf_k_attention_f32_dk(const float* Q, int32_t ldq, const float* K, int32_t ldk, const float* V, int32_t ldv, float* O,
+                          int32_t ldo, const int32_t* klens_dev, int32_t B, int32_t H, int32_t Tq, int32_t Tk, int32_t d_k,
+                          float scale, void* stream) {
+    PF_REQUIRE(attention_mid_applicable(d_k), "attention_f32_dk: d_k is 80 or 96 (128: pf_k_attention_f32; <= 64: pf_k_attention_small)");
+    AttnArgs aa{};
+    aa.Q = Q; aa.ldq = ldq; aa.K = K; aa.ldk = ldk; aa.V = V; aa.ldv = ldv; aa.O = O; aa.ldo = ldo; aa.klens = klens_dev;
+    aa.B = B; aa.H = H; aa.Tq = Tq; aa.Tk = Tk; aa.scale = scale;
+    return attention(aa, 4.0 * B * (double)Tq * Tk * H * d_k, reinterpret_cast<hipStream_t>(stream), false, d_k);
+}
 /* out[i, :] = table[ids[i], :] (embedding lookup), ids int32 on the device, clamped to [0, rows) */
 int pf_k_gather_rows(const float* table, int32_t ld, int32_t rows, const int32_t* ids_dev, float* out, int32_t n, int32_t D,
                      void* stream) {

@@ -446,6 +446,11 @@ pf_stream* pf_stream_create(pf_encoder* eh, pf_predictor* ph, pf_decoder* dh, co
     const pf_stream_config& c = *cfg;
     const int K = d->cfg.kernel_size;
     const int dec_left = (K - 1) / 2 + (d->cfg.sanm_shift > 0 ? d->cfg.sanm_shift : 0);
+    if (attention_mid_applicable(e->cfg.d_model / e->cfg.n_heads)) {
+        set_error("stream: the chunk step has no attention kernel for encoder heads of d_k = " + std::to_string(e->cfg.d_model / e->cfg.n_heads) +
+                  " (attention_mid.hip takes one key/value source; heads of d_k == 128 only)");
+        return nullptr;
+    }
     if (c.n_streams < 1 || c.chunk_left < 0 || c.chunk_cur < 1 || c.chunk_right < 0 || c.enc_look_back < 0 ||
         c.dec_look_back < 0 || c.max_frames < c.chunk_cur || c.max_tokens < 1 || c.max_tokens > 96 ||
         e->cfg.tp_blocks != 0 || e->cfg.d_model != 512 || d->cfg.d_model != 512 || p->cfg.d_model != 512 ||

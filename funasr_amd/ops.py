@@ -202,6 +202,24 @@ def attention_small(q, k, v, klens, n_heads: int, scale: float):
     return out
 
 
+def attention_mid(q, k, v, klens, n_heads: int, scale: float, out=None):
+    """q [B, Tq, H*dk], k/v [B, Tk, H*dk] with dk = 80 or 96 (row-strided views allowed), klens int32 [B] on the device (>= 1)
+    -> [B, Tq, H*dk]: exact fp32 on the matrix cores, any Tk (csrc/attention_mid.hip). `out`: a caller's fp32 buffer
+    [B, Tq, >= H*dk] (contiguous rows, any row stride % 4) whose first H*dk columns are written and nothing else."""
+    lib = _lib.load()
+    B, Tq, D = q.shape
+    Tk = k.shape[1]
+    assert all(t.stride(2) == 1 and t.stride(0) == t.shape[1] * t.stride(1) for t in (q, k, v)) and D % n_heads == 0
+    if out is None:
+        out = torch.empty(B, Tq, D, device=q.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.shape[:2] == (B, Tq) and out.shape[2] >= D and out.stride(2) == 1 \
+        and out.stride(0) == Tq * out.stride(1)
+    _lib.check(lib.pf_k_attention_f32_dk(_ptr(q), q.stride(1), _ptr(k), k.stride(1), _ptr(v), v.stride(1), _ptr(out),
+                                         out.stride(1), _ptr(klens), B, n_heads, Tq, Tk, D // n_heads, float(scale), _stream()),
+               "pf_k_attention_f32_dk")
+    return out
+
+
 def gather_rows(table: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
     """table [rows, D] fp32, ids int32 [n] (device) -> [n, D]: the embedding lookup of the punctuation model."""
     lib = _lib.load()

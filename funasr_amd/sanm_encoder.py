@@ -75,7 +75,8 @@ class _SANMEncoderBase(HipModule):
 
     def _default_precision(self) -> str:
         """The measured mode wherever its kernels exist (heads of d_k = 128, d_model % 256 == 0: Paraformer, SenseVoice and
-        their variants), fp32 otherwise (the CT-Transformer's small heads)."""
+        their variants), fp32 otherwise (the CT-Transformer's small heads; MonotonicAligner's heads of d_k = 80, which like
+        d_k = 96 have the fp32 kernel of csrc/attention_mid.hip and no other mode)."""
         ok = self._output_size % 256 == 0 and self._output_size // self.attention_heads == 128 and self.linear_units % 256 == 0
         return "f16x2" if ok else "fp32"
 
@@ -94,6 +95,9 @@ class _SANMEncoderBase(HipModule):
             return self
         if mode not in ("fp32", "bf16", "bf16x3", "f16x2"):
             raise ValueError("precision must be 'fp32', 'bf16', 'bf16x3' or 'f16x2'")
+        d_k = self._output_size // self.attention_heads
+        if mode != "fp32" and d_k in (80, 96):
+            raise NotImplementedError(f"{type(self).__name__}(HIP): heads of d_k = {d_k} run in the fp32 mode only, not {mode!r}")
         self._precision = mode
         if self._handle is not None:
             _lib.check(_lib.load().pf_encoder_set_precision(self._handle, {"fp32": 0, "bf16": 1, "bf16x3": 2, "f16x2": 3}[mode]),

@@ -440,6 +440,33 @@ def sanm_state_dict(seed: int, model) -> Dict[str, torch.Tensor]:
     return {k: _synthetic_tensor(k, shapes[k], g) for k in sorted(shapes)}
 
 
+def aligner_conf(output_size: int = 320, attention_heads: int = 4, linear_units: int = 1280, num_blocks: int = 30, idim: int = None,
+                 upsample_type: str = "cnn_blstm", use_cif1_cnn: bool = False, input_size: int = 560) -> dict:
+    """constructor arguments of a MonotonicAligner (the layout of funasr/models/monotonic_aligner/template.yaml, which the
+    defaults are: D 320, 4 heads of d_k 80, FFN 1280, 30 blocks, the BLSTM timestamp head on the raw encoder output)"""
+    enc = {"output_size": output_size, "attention_heads": attention_heads, "linear_units": linear_units, "num_blocks": num_blocks,
+           "dropout_rate": 0.1, "positional_dropout_rate": 0.1, "attention_dropout_rate": 0.1, "input_layer": "pe",
+           "pos_enc_class": "SinusoidalPositionEncoder", "normalize_before": True, "kernel_size": 11, "sanm_shfit": 0,
+           "selfattention_layer_type": "sanm"}
+    pred = {"idim": output_size if idim is None else idim, "threshold": 1.0, "l_order": 1, "r_order": 1, "tail_threshold": 0.45,
+            "smooth_factor2": 0.25, "noise_threshold2": 0.01, "upsample_times": 3, "use_cif1_cnn": use_cif1_cnn,
+            "upsample_type": upsample_type}
+    return {"encoder": "SANMEncoder", "encoder_conf": enc, "predictor": "CifPredictorV3", "predictor_conf": pred,
+            "length_normalized_loss": False, "predictor_bias": 1, "input_size": input_size}
+
+
+def aligner_state_dict(seed: int, model) -> Dict[str, torch.Tensor]:
+    """synthetic weights in the layout of `model` (a MonotonicAligner module or the reference's), drawn like sanm_state_dict in the
+    sorted order of the keys. The second alpha head's weight is drawn 4x wider than fan-in scaling and its bias set to -0.5, so that
+    the upsampled weights vary from frame to frame and the scaled integral crosses its threshold well inside a frame"""
+    g = torch.Generator().manual_seed(seed)
+    shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
+    sd = {k: _synthetic_tensor(k, shapes[k], g) for k in sorted(shapes)}
+    sd["predictor.cif_output2.weight"] = sd["predictor.cif_output2.weight"] * 4.0
+    sd["predictor.cif_output2.bias"] = torch.full(shapes["predictor.cif_output2.bias"], -0.5)
+    return sd
+
+
 def _synthetic_tensor(k: str, shp: tuple, g: torch.Generator) -> torch.Tensor:
     """one tensor of conformer_state_dict, by the name and shape of its key"""
     if k.endswith("num_batches_tracked"):

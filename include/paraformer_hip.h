@@ -934,6 +934,11 @@ int pf_k_attention_f32_two_source(const float* Q, int32_t ldq, const float* K, i
 int pf_k_attention_small(const float* Q, int32_t ldq, const float* K, int32_t ldk, const float* V, int32_t ldv,
                          float* O, int32_t ldo, const int32_t* klens_dev, int32_t B, int32_t H, int32_t d_k,
                          int32_t Tq, int32_t Tk, float scale, void* stream);
+/* heads of d_k = 80 or 96 (MonotonicAligner's 4 x 80), any Tk, exact fp32 on the matrix cores (attention_mid.hip): rows hold H
+ * heads of d_k columns; one key/value source, key-padding mask (klens_dev[b] >= 1), fp32 output; columns >= H * d_k of O untouched */
+int pf_k_attention_f32_dk(const float* Q, int32_t ldq, const float* K, int32_t ldk, const float* V, int32_t ldv,
+                          float* O, int32_t ldo, const int32_t* klens_dev, int32_t B, int32_t H, int32_t Tq,
+                          int32_t Tk, int32_t d_k, float scale, void* stream);
 /* embedding lookup: out[i, :] = table[ids_dev[i], :] (ids clamped to [0, rows)); D % 4 == 0 */
 int pf_k_gather_rows(const float* table, int32_t ld, int32_t rows, const int32_t* ids_dev, float* out, int32_t n,
                      int32_t D, void* stream);
