@@ -241,8 +241,55 @@ class ConformerEncoder(Conv2dSubsampledEncoder):
         return c
 
 
+class BeamStepper:
+    """the stepper of funasr_amd.transformer_search.BeamSearchTransformer over the C calls `<_prefix>_begin / _step / _reorder` (a
+    mix-in of the HipModule decoders that hold `vocab_size`); messages carry the class's own name"""
+    _max_len_why = "the positional table holds"
+
+    def set_precision(self, mode=None):
+        """accepted for symmetry: every GEMM of a step has M = n_hyp rows and runs the fp32 weight-streaming kernel in every mode"""
+        return self
+
+    def set_memory(self, memory: torch.Tensor):
+        """memory [T, D]: the encoder output of ONE utterance (its valid frames)"""
+        self._ensure_handle()
+        self._memory = memory.to(device=self._handle_device, dtype=torch.float32).contiguous()
+        return self
+
+    def _check_begin(self, max_len: int, max_hyp: int):
+        """the limits of the handle that the class refuses in its own words"""
+        if max_len > MAX_LEN:
+            raise ValueError(f"{type(self).__name__}: {max_len} output positions; {self._max_len_why} {MAX_LEN}")
+
+    def _call(self, what: str, *args):
+        """`<_prefix>_<what>(handle, *args, stream)` on the handle's device"""
+        lib, h = self._ensure_handle()
+        name = f"{self._prefix}_{what}"
+        with torch.cuda.device(self._handle_device):
+            _lib.check(getattr(lib, name)(h, *args, stream_ptr()), name)
+            if what != "begin":
+                torch.cuda.current_stream(self._handle_device).synchronize()      # the ids / parents are staged asynchronously
+
+    def begin(self, max_len: int, max_hyp: int):
+        if self._memory is None:
+            raise RuntimeError(f"{type(self).__name__}.begin: set_memory(encoder_out) first")
+        self._check_begin(max_len, max_hyp)
+        self._call("begin", self._memory.data_ptr(), int(self._memory.shape[0]), int(max_len), int(max_hyp))
+
+    def step(self, tokens: List[int], pos: int) -> torch.Tensor:
+        self._ensure_handle()                                                     # (the handle's device is known from here on)
+        n = len(tokens)
+        out = torch.empty(n, self.vocab_size, device=self._handle_device)
+        self._call("step", (_lib.C.c_int32 * n)(*[int(t) for t in tokens]), int(pos), n, out.data_ptr())
+        return out
+
+    def reorder(self, parents: List[int]):
+        n = len(parents)
+        self._call("reorder", (_lib.C.c_int32 * n)(*[int(p) for p in parents]), n)
+
+
 @tables.register("decoder_classes", "TransformerDecoder")
-class TransformerDecoder(HipModule):
+class TransformerDecoder(BeamStepper, HipModule):
     _prefix = "pf_tdecoder"
 
     def __init__(self, vocab_size: int, encoder_output_size: int, attention_heads: int = 4, linear_units: int = 2048, num_blocks: int = 6,
@@ -287,45 +334,6 @@ class TransformerDecoder(HipModule):
         c.vocab_size, c.d_model, c.n_heads, c.ffn_dim, c.n_blocks, c.ln_eps = (self.vocab_size, self.d_model, self.attention_heads,
                                                                               self.linear_units, self.num_blocks, 1e-12)
         return c
-
-    def set_precision(self, mode=None):
-        """accepted for symmetry: every GEMM of a step has M = n_hyp rows and runs the fp32 weight-streaming kernel in both modes"""
-        return self
-
-    # ---- the stepper of funasr_amd.transformer_search.BeamSearchTransformer
-    def set_memory(self, memory: torch.Tensor):
-        """memory [T, D]: the encoder output of ONE utterance (its valid frames)"""
-        self._ensure_handle()
-        self._memory = memory.to(device=self._handle_device, dtype=torch.float32).contiguous()
-        return self
-
-    def begin(self, max_len: int, max_hyp: int):
-        if self._memory is None:
-            raise RuntimeError("TransformerDecoder.begin: set_memory(encoder_out) first")
-        if max_len > MAX_LEN:
-            raise ValueError(f"TransformerDecoder: {max_len} output positions; the positional table holds {MAX_LEN}")
-        lib, h = self._ensure_handle()
-        with torch.cuda.device(self._handle_device):
-            _lib.check(lib.pf_tdecoder_begin(h, self._memory.data_ptr(), int(self._memory.shape[0]), int(max_len), int(max_hyp), stream_ptr()),
-                       "pf_tdecoder_begin")
-
-    def step(self, tokens: List[int], pos: int) -> torch.Tensor:
-        lib, h = self._ensure_handle()
-        n = len(tokens)
-        out = torch.empty(n, self.vocab_size, device=self._handle_device)
-        tk = (_lib.C.c_int32 * n)(*[int(t) for t in tokens])
-        with torch.cuda.device(self._handle_device):
-            _lib.check(lib.pf_tdecoder_step(h, tk, int(pos), n, out.data_ptr(), stream_ptr()), "pf_tdecoder_step")
-            torch.cuda.current_stream(self._handle_device).synchronize()      # the token ids are staged asynchronously
-        return out
-
-    def reorder(self, parents: List[int]):
-        lib, h = self._ensure_handle()
-        n = len(parents)
-        pr = (_lib.C.c_int32 * n)(*[int(p) for p in parents])
-        with torch.cuda.device(self._handle_device):
-            _lib.check(lib.pf_tdecoder_reorder(h, pr, n, stream_ptr()), "pf_tdecoder_reorder")
-            torch.cuda.current_stream(self._handle_device).synchronize()
 
 
 class PaddedBatchFront:

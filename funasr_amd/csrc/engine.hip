@@ -1,6 +1,9 @@
 // C-ABI layer (include/paraformer_hip.h), shared state: error string, profiling hooks, the pinned staging ring for per-call
 // metadata, the instrumented launch helpers every module family uses, ABI version. The handle types live in engine_internal.h;
 // the families in engine_{frontend,encoder,decoder,stream,vad,kernels}.hip.
+#include <algorithm>
+#include <optional>
+
 #include "engine_internal.h"
 
 namespace pf {
@@ -151,6 +154,23 @@ int gemm_two_mode(TensorTable& tt, DevBuf& planes, bool x2, const float* A, int 
     g.bias = bias; g.relu = relu; g.R1 = R1; g.ldr1 = N; g.C = C; g.ldc = ldc;
     g.M = M; g.N = N; g.K = K;
     return launch_gemm_f16x2(g, s);
+}
+int gemm_f32_ksliced(const float* A, int lda, const float* W, int ldw, const float* bias, int M, int N, int K, int slice, float* out_a,
+                     float* out_b, const float** last, const char* prof_tag, hipStream_t s) {
+    float *cur = out_a, *prev = out_b;
+    for (int k0 = 0; k0 < K; k0 += slice) {
+        GemmArgs g{};
+        g.A = A + k0; g.lda = lda; g.W = W + k0; g.ldw = ldw;
+        g.bias = k0 == 0 ? bias : nullptr;
+        g.R1 = k0 == 0 ? nullptr : prev; g.ldr1 = N;
+        g.C = cur; g.ldc = N; g.M = M; g.N = N; g.K = std::min(slice, K - k0);
+        std::optional<ProfScope> ps;
+        if (prof_tag) ps.emplace(PROF_GEMM, 2.0 * M * (double)N * g.K, s, prof_tag);
+        if (int rc = launch_gemm_f32(g, s)) return rc;
+        std::swap(cur, prev);
+    }
+    *last = prev;                                            // (after the last swap `prev` is what was written last)
+    return 0;
 }
 int layernorm(const float* x, int ldx, const float* g, const float* b, float* y, int ldy, int M, int D,
                      int Dpad, float eps, hipStream_t s) {

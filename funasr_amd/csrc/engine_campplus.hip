@@ -263,7 +263,7 @@ pf_campplus* pf_campplus_create(const pf_campplus_config* cfg) {
     const int mc = c.m_channels;
     int rc = 0;
     auto bn = [&](const std::string& p, int C, bool affine) {
-        if (affine) { rc |= h->tt.add(p + "weight", C); rc |= h->tt.add(p + "bias", C); }
+        if (affine) rc |= h->tt.add_linear(p, C, 1);
         rc |= h->tt.add(p + "running_mean", C);
         rc |= h->tt.add(p + "running_var", C);
     };
@@ -295,10 +295,8 @@ pf_campplus* pf_campplus_create(const pf_campplus_config* cfg) {
             rc |= h->tt.add(p + "linear1.weight", (int64_t)BNC * Cin);
             bn(p + "nonlinear2.batchnorm.", BNC, true);
             rc |= h->tt.add(p + "cam_layer.linear_local.weight", G * BNC * 3);
-            rc |= h->tt.add(p + "cam_layer.linear1.weight", BNC / 2 * BNC);
-            rc |= h->tt.add(p + "cam_layer.linear1.bias", BNC / 2);
-            rc |= h->tt.add(p + "cam_layer.linear2.weight", G * BNC / 2);
-            rc |= h->tt.add(p + "cam_layer.linear2.bias", G);
+            rc |= h->tt.add_linear(p + "cam_layer.linear1.", BNC / 2, BNC);
+            rc |= h->tt.add_linear(p + "cam_layer.linear2.", G, BNC / 2);
         }
         ch += kLayers[blk] * G;
         const std::string p = "xvector.transit" + std::to_string(blk + 1) + ".";

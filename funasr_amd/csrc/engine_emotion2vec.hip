@@ -320,37 +320,23 @@ pf_emotion2vec* pf_emotion2vec_create(const pf_emotion2vec_config* cfg) {
     for (int l = 0; l < c.n_conv; ++l) {
         if (l == 0) rc |= h->tt.add(conv_name(0, ".0.weight"), (int64_t)512 * c.conv_kernel[0]);
         else rc |= h->tt.add_conv(conv_name(l, ".0.weight"), 512, 512, c.conv_kernel[l]);
-        rc |= h->tt.add(conv_name(l, ".2.1.weight"), 512);
-        rc |= h->tt.add(conv_name(l, ".2.1.bias"), 512);
+        rc |= h->tt.add_linear(conv_name(l, ".2.1."), 512, 1);
     }
-    rc |= h->tt.add(A + "project_features.1.weight", 512);
-    rc |= h->tt.add(A + "project_features.1.bias", 512);
-    rc |= h->tt.add(A + "project_features.2.weight", (int64_t)D * 512);
-    rc |= h->tt.add(A + "project_features.2.bias", D);
-    for (int l = 0; l < c.conv_pos_depth; ++l) {
-        const std::string p = A + "relative_positional_encoder." + std::to_string(l + 1) + ".0.";
-        rc |= h->tt.add(p + "weight", (int64_t)D * (D / c.conv_pos_groups) * c.conv_pos_kernel);
-        rc |= h->tt.add(p + "bias", D);
-    }
-    rc |= h->tt.add(A + "context_encoder.norm.weight", D);
-    rc |= h->tt.add(A + "context_encoder.norm.bias", D);
+    rc |= h->tt.add_linear(A + "project_features.1.", 512, 1);
+    rc |= h->tt.add_linear(A + "project_features.2.", D, 512);
+    for (int l = 0; l < c.conv_pos_depth; ++l)
+        rc |= h->tt.add_linear(A + "relative_positional_encoder." + std::to_string(l + 1) + ".0.", D, (int64_t)(D / c.conv_pos_groups) * c.conv_pos_kernel);
+    rc |= h->tt.add_linear(A + "context_encoder.norm.", D, 1);
     for (int i = 0; i < c.prenet_depth; ++i) h->blocks.push_back(A + "context_encoder.blocks." + std::to_string(i) + ".");
     for (int i = 0; i < c.depth; ++i) h->blocks.push_back("blocks." + std::to_string(i) + ".");
     for (const std::string& p : h->blocks) {
-        for (const char* nm : {"norm1.", "norm2."}) { rc |= h->tt.add(p + nm + "weight", D); rc |= h->tt.add(p + nm + "bias", D); }
-        rc |= h->tt.add(p + "attn.qkv.weight", (int64_t)3 * D * D);
-        rc |= h->tt.add(p + "attn.qkv.bias", 3 * D);
-        rc |= h->tt.add(p + "attn.proj.weight", (int64_t)D * D);
-        rc |= h->tt.add(p + "attn.proj.bias", D);
-        rc |= h->tt.add(p + "mlp.fc1.weight", (int64_t)c.ffn_dim * D);
-        rc |= h->tt.add(p + "mlp.fc1.bias", c.ffn_dim);
-        rc |= h->tt.add(p + "mlp.fc2.weight", (int64_t)D * c.ffn_dim);
-        rc |= h->tt.add(p + "mlp.fc2.bias", D);
+        for (const char* nm : {"norm1.", "norm2."}) rc |= h->tt.add_linear(p + nm, D, 1);
+        rc |= h->tt.add_linear(p + "attn.qkv.", 3 * D, D);
+        rc |= h->tt.add_linear(p + "attn.proj.", D, D);
+        rc |= h->tt.add_linear(p + "mlp.fc1.", c.ffn_dim, D);
+        rc |= h->tt.add_linear(p + "mlp.fc2.", D, c.ffn_dim);
     }
-    if (c.vocab_size > 0) {
-        rc |= h->tt.add("proj.weight", (int64_t)c.vocab_size * D);
-        rc |= h->tt.add("proj.bias", c.vocab_size);
-    }
+    if (c.vocab_size > 0) rc |= h->tt.add_linear("proj.", c.vocab_size, D);
     if (rc) return nullptr;
     return reinterpret_cast<pf_emotion2vec*>(h.release());
 }

@@ -127,6 +127,11 @@ struct TensorTable {
         PF_HIP_TRY(hipMalloc((void**)&x.d, sizeof(float) * (size_t)numel));
         t[name] = x; return 0;
     }
+    // a Linear (LayerNorm, convolution: anything with this pair) named `prefix`: "weight" [out, in] and, with `bias`, "bias" [out]
+    int add_linear(const std::string& prefix, int64_t out, int64_t in, bool bias = true) {
+        const int rc = add(prefix + "weight", out * in);
+        return bias ? rc | add(prefix + "bias", out) : rc;
+    }
     int add_padded(const std::string& name, int rows, int cols, int cols_pad) {
         Tensor x; x.numel = (int64_t)rows * cols; x.kind = 1; x.rows = rows; x.cols = cols; x.cols_pad = cols_pad;
         PF_HIP_TRY(hipMalloc((void**)&x.d, sizeof(float) * (size_t)rows * cols_pad));
@@ -720,6 +725,12 @@ int argmax_f16x2(const unsigned short* A2, int lda, size_t a_plane, const unsign
 // runs on the fp16 matrix cores with fp32 results.
 int gemm_two_mode(TensorTable& tt, DevBuf& planes, bool x2, const float* A, int width, size_t a_rows, int lda, int M, int K,
                   const std::string& wname, int N, const float* bias, const float* R1, float* C, int ldc, int e_a, int relu, hipStream_t s);
+// C[M, N] = A W^T + bias on the exact-fp32 MFMA with K in slices of `slice` (a multiple of the GEMM's 32). One fp32 fma chain over
+// thousands of terms drifts several times further from the exact sum than a blocked CPU GEMM does, so a slice's chain starts at zero
+// and the running sum rides in as the addend of the next launch: ping-pong between out_a (the first slice) and out_b, no in-place
+// addend. *last = the buffer the last slice wrote. `prof_tag`: every launch in a ProfScope of that tag (nullptr: none).
+int gemm_f32_ksliced(const float* A, int lda, const float* W, int ldw, const float* bias, int M, int N, int K, int slice, float* out_a,
+                     float* out_b, const float** last, const char* prof_tag, hipStream_t s);
 int gemm3_simple(const unsigned short* A3, int lda, int M, const unsigned short* W3, const float* bias, float* C,
                         int ldc, int N, int K, int relu, hipStream_t s);
 int gemm2_simple(const unsigned short* A2, int lda, int M, int ea, const unsigned short* W2, int ew, const float* bias,

@@ -54,36 +54,33 @@ static int pe_logits(PosteriorEmbed* h, Ctc* c, bool x2, const float* hidden, si
 }
 
 // E[r0 .. r0 + m) = probs W0^T in K slices of PE_K_SLICE: a slice's chain starts at zero and the running sum rides in as the addend
-// of the next launch (ping-pong between Ea and Eb: no in-place addend). Returns the buffer the last slice wrote.
+// of the next launch (ping-pong between Ea and Eb: no in-place addend; fp32: gemm_f32_ksliced). Returns the buffer the last slice wrote.
 static int pe_project(PosteriorEmbed* h, bool x2, size_t r0, int m, const float** out, hipStream_t s) {
     const int D = h->D, Vp = h->Vp;
     float* cur = h->Ea.as<float>() + r0 * D;
     float* prev = h->Eb.as<float>() + r0 * D;
-    const unsigned short* P = nullptr; const unsigned short* W2 = nullptr;
     int ew = 0, rc;
-    const int e_a = exp_for_bound(1.f);                   // probabilities: |p| <= 1
-    if (x2) {
-        const size_t plane = (size_t)m * Vp;
-        if ((rc = launch_split2(h->probs.as<float>(), Vp, h->planes.as<unsigned short>(), Vp, plane, m, Vp, pow2f(e_a), s))) return rc;
-        P = h->planes.as<unsigned short>();
-        if (!(W2 = h->tt.get_split2("embed.0.weight", D, Vp, &ew, s))) return -2;
+    if (!x2) {
+        if ((rc = gemm_f32_ksliced(h->probs.as<float>(), Vp, h->tt.get("embed.0.weight"), Vp, nullptr, m, D, Vp, PE_K_SLICE, cur, prev, out,
+                                   "pe.project", s)))
+            return rc;
+        *out -= r0 * D;
+        return 0;
     }
+    const int e_a = exp_for_bound(1.f);                   // probabilities: |p| <= 1
+    const size_t plane = (size_t)m * Vp;
+    unsigned short* P = h->planes.as<unsigned short>();
+    if ((rc = launch_split2(h->probs.as<float>(), Vp, P, Vp, plane, m, Vp, pow2f(e_a), s))) return rc;
+    const unsigned short* W2 = h->tt.get_split2("embed.0.weight", D, Vp, &ew, s);
+    if (!W2) return -2;
     for (int k0 = 0; k0 < Vp; k0 += PE_K_SLICE) {
         const int K = std::min(PE_K_SLICE, Vp - k0);
-        ProfScope ps(x2 ? PROF_GEMM3 : PROF_GEMM, 2.0 * m * (double)D * K, s, "pe.project");
-        if (x2) {
-            Gemm2Args g{};
-            g.A = P + k0; g.lda = Vp; g.a_plane = (size_t)m * Vp; g.W = W2 + k0; g.ldw = Vp; g.w_plane = (size_t)D * Vp;
-            g.oscale = pow2f(-(e_a + ew)); g.R1 = k0 == 0 ? nullptr : prev; g.ldr1 = D;
-            g.C = cur; g.ldc = D; g.M = m; g.N = D; g.K = K;
-            if ((rc = launch_gemm_f16x2(g, s))) return rc;
-        } else {
-            GemmArgs g{};
-            g.A = h->probs.as<float>() + k0; g.lda = Vp; g.W = h->tt.get("embed.0.weight") + k0; g.ldw = Vp;
-            g.R1 = k0 == 0 ? nullptr : prev; g.ldr1 = D;
-            g.C = cur; g.ldc = D; g.M = m; g.N = D; g.K = K;
-            if ((rc = launch_gemm_f32(g, s))) return rc;
-        }
+        ProfScope ps(PROF_GEMM3, 2.0 * m * (double)D * K, s, "pe.project");
+        Gemm2Args g{};
+        g.A = P + k0; g.lda = Vp; g.a_plane = plane; g.W = W2 + k0; g.ldw = Vp; g.w_plane = (size_t)D * Vp;
+        g.oscale = pow2f(-(e_a + ew)); g.R1 = k0 == 0 ? nullptr : prev; g.ldr1 = D;
+        g.C = cur; g.ldc = D; g.M = m; g.N = D; g.K = K;
+        if ((rc = launch_gemm_f16x2(g, s))) return rc;
         std::swap(cur, prev);
     }
     *out = prev - r0 * D;                                  // (after the last swap `prev` is what was written last)

@@ -17,15 +17,13 @@ and equal to the teacher-forced `forward`, only when R == 0 (the constructor's d
 """
 from __future__ import annotations
 
-from typing import List
-
 import torch
 import torch.nn as nn
 
 from . import _lib
 from . import sanm_encoder as _sanm_encoder  # noqa: F401  (registers SANMEncoder)
-from .conformer import MAX_LEN, AttentionEncoderDecoder
-from .hip_module import HipModule, Holder, ParamHolder, _truthy, layer_norm, linear, stream_ptr
+from .conformer import AttentionEncoderDecoder, BeamStepper
+from .hip_module import HipModule, Holder, ParamHolder, _truthy, layer_norm, linear
 from .paraformer_decoder import _block, _block2, _ffn
 from .register import tables
 
@@ -41,8 +39,9 @@ def fsmn_paddings(kernel_size: int, sanm_shfit) -> "tuple[int, int]":
 
 
 @tables.register("decoder_classes", "FsmnDecoder")
-class FsmnDecoder(HipModule):
+class FsmnDecoder(BeamStepper, HipModule):
     _prefix = "pf_fsmndecoder"
+    _max_len_why = "one utterance holds at most"          # (no positional table: the embedding is bare)
 
     def __init__(self, vocab_size: int, encoder_output_size: int, attention_heads: int = 4, linear_units: int = 2048, num_blocks: int = 6,
                  dropout_rate: float = 0.1, positional_dropout_rate: float = 0.1, self_attention_dropout_rate: float = 0.0,
@@ -96,46 +95,10 @@ class FsmnDecoder(HipModule):
         c.att_layer_num, c.kernel_size, c.sanm_shift, c.ln_eps = self.att_layer_num, self.kernel_size, self.sanm_shfit, 1e-12
         return c
 
-    def set_precision(self, mode=None):
-        """accepted for symmetry: every GEMM of a step has M = n_hyp rows and runs the fp32 weight-streaming kernel in every mode"""
-        return self
-
-    # ---- the stepper of funasr_amd.transformer_search.BeamSearchTransformer
-    def set_memory(self, memory: torch.Tensor):
-        """memory [T, D]: the encoder output of ONE utterance (its valid frames)"""
-        self._ensure_handle()
-        self._memory = memory.to(device=self._handle_device, dtype=torch.float32).contiguous()
-        return self
-
-    def begin(self, max_len: int, max_hyp: int):
-        if self._memory is None:
-            raise RuntimeError("FsmnDecoder.begin: set_memory(encoder_out) first")
-        if max_len > MAX_LEN:
-            raise ValueError(f"FsmnDecoder: {max_len} output positions; one utterance holds at most {MAX_LEN}")
+    def _check_begin(self, max_len: int, max_hyp: int):
+        super()._check_begin(max_len, max_hyp)
         if max_hyp > MAX_HYP:
             raise ValueError(f"FsmnDecoder: {max_hyp} hypotheses; one handle holds at most {MAX_HYP}")
-        lib, h = self._ensure_handle()
-        with torch.cuda.device(self._handle_device):
-            _lib.check(lib.pf_fsmndecoder_begin(h, self._memory.data_ptr(), int(self._memory.shape[0]), int(max_len), int(max_hyp), stream_ptr()),
-                       "pf_fsmndecoder_begin")
-
-    def step(self, tokens: List[int], pos: int) -> torch.Tensor:
-        lib, h = self._ensure_handle()
-        n = len(tokens)
-        out = torch.empty(n, self.vocab_size, device=self._handle_device)
-        tk = (_lib.C.c_int32 * n)(*[int(t) for t in tokens])
-        with torch.cuda.device(self._handle_device):
-            _lib.check(lib.pf_fsmndecoder_step(h, tk, int(pos), n, out.data_ptr(), stream_ptr()), "pf_fsmndecoder_step")
-            torch.cuda.current_stream(self._handle_device).synchronize()      # the token ids are staged asynchronously
-        return out
-
-    def reorder(self, parents: List[int]):
-        lib, h = self._ensure_handle()
-        n = len(parents)
-        pr = (_lib.C.c_int32 * n)(*[int(p) for p in parents])
-        with torch.cuda.device(self._handle_device):
-            _lib.check(lib.pf_fsmndecoder_reorder(h, pr, n, stream_ptr()), "pf_fsmndecoder_reorder")
-            torch.cuda.current_stream(self._handle_device).synchronize()      # the parents are staged asynchronously
 
 
 @tables.register("model_classes", "SANM")
