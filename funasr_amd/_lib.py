@@ -246,6 +246,19 @@ SIGNATURES = {
     "pf_fsmndecoder_reorder": (C.c_int, [_vp, _pi32, _i32, _vp]),
     "pf_k_fsmn_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _f32, _vp, _vp, _vp]),
     "pf_k_cross_attention_step": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "pf_encoder_set_chunk_mask": (C.c_int, [_vp, _i32, _i32, _i32, _i32]),
+    "pf_uniasr_gather_rows": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp]),
+    "pf_uniasr_stride_conv": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
+    "pf_scamadecoder_create": (_vp, [C.POINTER(pf_fsmndecoder_config)]),
+    "pf_scamadecoder_destroy": (None, [_vp]),
+    "pf_scamadecoder_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),
+    "pf_scamadecoder_missing": (C.c_int, [_vp]),
+    "pf_scamadecoder_begin": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "pf_scamadecoder_step": (C.c_int, [_vp, _pi32, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "pf_scamadecoder_reorder": (C.c_int, [_vp, _pi32, _i32, _vp]),
+    "pf_k_chunk_attention": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "pf_k_chunk_fsmn": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "pf_k_scama_attention": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "pf_k_relpos_attention": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "pf_k_conformer_glu_dw": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "pf_transducer_create": (_vp, [C.POINTER(pf_transducer_config)]),

@@ -35,6 +35,7 @@
 
 #include "engine_internal.h"
 #include "conformer.h"
+#include "uniasr.h"
 
 using namespace pf;
 
@@ -753,9 +754,10 @@ int pf_fsmndecoder_begin(pf_fsmndecoder* hh, const float* memory, int32_t T, int
     }
     return 0;
 }
-int pf_fsmndecoder_step(pf_fsmndecoder* hh, const int32_t* tokens_host, int32_t pos, int32_t n, float* logp, void* stream) {
-    Fd* h = reinterpret_cast<Fd*>(hh);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+// The step of both SAN-M steppers. `win` == nullptr: pf_fsmndecoder_step, every cross-attention over the whole memory. Otherwise
+// pf_scamadecoder_step: the cross-attention of every `decoders` layer restricted to the keys of the window that the mask row admits.
+struct FdWindow { const float* mask; int lo, hi; };
+static int fd_step(Fd* h, const int32_t* tokens_host, int32_t pos, int32_t n, float* logp, const FdWindow* win, hipStream_t s) {
     int rc;
     if ((rc = step_common_checks(h, "fsmndecoder", tokens_host, logp, n, [&] {
              PF_REQUIRE(n > 0 && n <= h->max_hyp && pos >= 0 && pos < h->max_len && pos == h->filled,
@@ -794,12 +796,19 @@ int pf_fsmndecoder_step(pf_fsmndecoder* hh, const int32_t* tokens_host, int32_t 
         if (!l.cross) continue;
         const float* kv = h->ckv.as<float>() + (size_t)lc * T * 2 * D;
         ++lc;
-        if ((rc = h->cross_attention(p, xn, x, y, [&] { return launch_fd_attention(q, kv, kv + D, 2 * D, T, n, H, D / H, a, s); }))) return rc;
+        if ((rc = h->cross_attention(p, xn, x, y, [&] {
+                 return win ? launch_scama_attention(q, kv, kv + D, 2 * D, T, win->mask, win->lo, win->hi, n, H, D / H, a, s)
+                            : launch_fd_attention(q, kv, kv + D, 2 * D, T, n, H, D / H, a, s);
+             })))
+            return rc;
         std::swap(x, y);
     }
     if ((rc = h->output_tail(x, logp))) return rc;
     h->filled = pos + 1; h->cur ^= 1; h->n_prev = n; h->n_par = 0;
     return 0;
+}
+int pf_fsmndecoder_step(pf_fsmndecoder* hh, const int32_t* tokens_host, int32_t pos, int32_t n, float* logp, void* stream) {
+    return fd_step(reinterpret_cast<Fd*>(hh), tokens_host, pos, n, logp, nullptr, reinterpret_cast<hipStream_t>(stream));
 }
 int pf_fsmndecoder_reorder(pf_fsmndecoder* hh, const int32_t* parents_host, int32_t n, void* stream) {
     Fd* h = reinterpret_cast<Fd*>(hh);
@@ -812,6 +821,29 @@ int pf_fsmndecoder_reorder(pf_fsmndecoder* hh, const int32_t* parents_host, int3
     if (rc) return rc < 0 ? rc : 0;
     h->n_par = n;
     return 0;
+}
+
+// ---- SCAMA decoder step (FsmnDecoderSCAMAOpt.forward_one_step, scama/decoder.py:455-524): the SAN-M stepper above behind entry points
+// of its own; the step takes the memory mask of its position
+pf_scamadecoder* pf_scamadecoder_create(const pf_fsmndecoder_config* cfg) { return reinterpret_cast<pf_scamadecoder*>(pf_fsmndecoder_create(cfg)); }
+void pf_scamadecoder_destroy(pf_scamadecoder* h) { pf_fsmndecoder_destroy(reinterpret_cast<pf_fsmndecoder*>(h)); }
+int pf_scamadecoder_set_tensor(pf_scamadecoder* h, const char* name, const float* data, int64_t numel) {
+    return pf_fsmndecoder_set_tensor(reinterpret_cast<pf_fsmndecoder*>(h), name, data, numel);
+}
+int pf_scamadecoder_missing(const pf_scamadecoder* h) { return pf_fsmndecoder_missing(reinterpret_cast<const pf_fsmndecoder*>(h)); }
+int pf_scamadecoder_begin(pf_scamadecoder* h, const float* memory, int32_t T, int32_t max_len, int32_t max_hyp, void* stream) {
+    return pf_fsmndecoder_begin(reinterpret_cast<pf_fsmndecoder*>(h), memory, T, max_len, max_hyp, stream);
+}
+int pf_scamadecoder_step(pf_scamadecoder* hh, const int32_t* tokens_host, int32_t pos, int32_t n, const float* mask_row_dev, int32_t key_lo,
+                         int32_t key_hi, float* logp, void* stream) {
+    Fd* h = reinterpret_cast<Fd*>(hh);
+    PF_REQUIRE(h && h->max_len > 0, "scamadecoder_step: null handle or no begin()");
+    PF_REQUIRE(key_lo >= 0 && key_lo <= key_hi && key_hi <= h->T, "scamadecoder_step: key window outside 0 <= key_lo <= key_hi <= T");
+    const FdWindow win{mask_row_dev, key_lo, key_hi};
+    return fd_step(h, tokens_host, pos, n, logp, &win, reinterpret_cast<hipStream_t>(stream));
+}
+int pf_scamadecoder_reorder(pf_scamadecoder* h, const int32_t* parents_host, int32_t n, void* stream) {
+    return pf_fsmndecoder_reorder(reinterpret_cast<pf_fsmndecoder*>(h), parents_host, n, stream);
 }
 
 // single-kernel hooks (tests)

@@ -407,7 +407,10 @@ int encoder_block(Encoder* e, const EncLayerW& w, float* x_in, int ld_in, float*
     // streaming step: the memory block rides in the attention launch (AttnArgs.fs_*: same bits, one launch less in the chain)
     const bool fsmn_rides = cc && cc->fsmn_rides && g_stream_mode && T <= 32 && D / c.n_heads == 128 && c.kernel_size == 11 &&
                             fa.left_pad == 5 && D <= 1024;
-    if (!fsmn_rides && (rc = fsmn(fa, s))) return rc;
+    const bool chunked = e->chunk_mask.chunk > 0 && !cc;          // the offline chunked forward (uniasr.hip)
+    if (chunked) {
+        if ((rc = launch_chunk_fsmn(fa, e->chunk_mask, s))) return rc;
+    } else if (!fsmn_rides && (rc = fsmn(fa, s))) return rc;
     // scaled dot-product attention over valid keys (attention.py:284-306,324-326)
     AttnArgs aa{};
     if (fsmn_rides) { aa.fs_in = fa.in; aa.fs_ldin = fa.ldin; aa.fs_w = fa.w; aa.fs_out = fa.out; aa.fs_ldo = fa.ldo; aa.fs_T = T; }
@@ -435,7 +438,9 @@ int encoder_block(Encoder* e, const EncLayerW& w, float* x_in, int ld_in, float*
     // f16x2 step: the attention writes the out-projection's operand planes itself (no split2 launch)
     const bool o2 = x2c && cc->x2_attn_planes && g_stream_mode && T <= 32 && D / c.n_heads == 128;
     if (o2) { aa.O2 = ctx2c; aa.ldo2 = D; aa.o2_plane = (size_t)M * D; aa.o2_scale = pow2f(w.e_v); }
-    if ((rc = attention(aa, 4.0 * B * (double)T * T * D, s, false, D / c.n_heads, &appended))) return rc;
+    if (chunked) {
+        if ((rc = launch_chunk_attention(aa, D / c.n_heads, e->chunk_mask, s))) return rc;
+    } else if ((rc = attention(aa, 4.0 * B * (double)T * T * D, s, false, D / c.n_heads, &appended))) return rc;
     if (cc && cc->cap > 0 && cc->append_rows > 0 && !appended) {
         RingAppendArgs ra{};
         ra.src = qkv + D; ra.ldsrc = 3 * D; ra.src_T = T; ra.r0 = 0; ra.rows = cc->append_rows; ra.cols = 2 * D;
@@ -622,6 +627,18 @@ int pf_encoder_set_vad_mask(pf_encoder* eh, const int32_t* vad_pos_host, int32_t
     e->h_vad.assign(vad_pos_host ? vad_pos_host : nullptr, vad_pos_host ? vad_pos_host + B : nullptr);
     return 0;
 }
+/* SANMEncoderChunkOpt.forward(xs, lens, ind) (scama/encoder.py:393-478): chunk > 0 makes the next forwards treat their rows as the
+ * chunked layout of overlap_chunk (chunk + shift rows per chunk, the first `shift` of them the FSMN shift rows): every block's
+ * attention is masked by mask_att_chunk_encoder and its FSMN memory by mask_shfit_chunk, both derived from the geometry on the device.
+ * chunk == 0 switches the masks off. fp32 mode; not with the VAD masks. */
+int pf_encoder_set_chunk_mask(pf_encoder* eh, int32_t chunk, int32_t stride, int32_t shift, int32_t look_back) {
+    Encoder* e = reinterpret_cast<Encoder*>(eh);
+    PF_REQUIRE(e, "encoder_set_chunk_mask: null handle");
+    PF_REQUIRE(chunk == 0 || (chunk >= 1 && stride >= 1 && stride <= chunk && shift >= 0 && look_back >= 0 && chunk + shift <= (1 << 20)),
+               "encoder_set_chunk_mask: 1 <= stride <= chunk, shift >= 0, look_back >= 0 (chunk 0: off)");
+    e->chunk_mask = ChunkGeom{chunk, chunk ? stride : 0, chunk ? shift : 0, chunk ? look_back : 0};
+    return 0;
+}
 int pf_encoder_missing(const pf_encoder* eh) {
     const Encoder* e = reinterpret_cast<const Encoder*>(eh);
     return e ? e->tt.missing() : -1;
@@ -706,6 +723,8 @@ int pf_encoder_forward(pf_encoder* eh, const float* xs, const int32_t* lens_host
         e->cur_fs = e->fs_grp.as<int>(); e->cur_fs_groups = G;
     }
     e->cur_mask_mode = 0;
+    if (e->chunk_mask.chunk > 0)
+        PF_REQUIRE(e->precision == 0 && !e->vad_mask && !pack, "encoder: the chunk-masked forward runs in the fp32 mode, without the VAD masks");
     if (e->vad_mask) {
         PF_REQUIRE(e->precision == 0 && (int)e->h_vad.size() == B, "encoder: the VAD-masked encoder runs in the fp32 mode with one vad position per sequence");
         if ((rc = upload_lens(e->vad_dev, e->h_vad.data(), B, s))) return rc;

@@ -36,6 +36,7 @@
 #include "common.h"
 #include "frontend.h"
 #include "stream.h"
+#include "uniasr.h"
 #include "engine_tables.h"
 
 
@@ -451,6 +452,9 @@ struct Encoder {
     std::vector<int32_t> h_vad;
     DevBuf vad_dev;
     int cur_mask_mode = 0;              // mask mode of the block being enqueued (AttnArgs.mask_mode)
+    // SANMEncoderChunkOpt.forward with `ind` (pf_encoder_set_chunk_mask): the rows are the chunked layout of overlap_chunk; every
+    // block's attention takes mask_att_chunk_encoder and its FSMN memory mask_shfit_chunk from this geometry (chunk == 0: off)
+    ChunkGeom chunk_mask{0, 0, 0, 0};
     // mode 3: the N = 512 projections (linear_out, w_2) run in their full-row form (gemm_f16x2_row.hip) whose epilogue does
     // the residual adds AND the LayerNorm that follows (norm2; the NEXT block's norm1), bitwise equal to the separate kernels.
     // fuse_row = 0 restores the separate launches (A/B measurements, tests)

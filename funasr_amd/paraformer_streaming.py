@@ -123,6 +123,18 @@ class SANMEncoderChunkOpt(SANMEncoder):
         self.encoder_att_look_back_factor = encoder_att_look_back_factor
         self.decoder_att_look_back_factor = decoder_att_look_back_factor
 
+    def forward(self, xs_pad: torch.Tensor, ilens, prev_states=None, ctc=None, ind: Optional[int] = None):
+        """ind None: SANMEncoder.forward, the whole utterance without chunk masks (what this class computed before it took `ind`).
+        ind given: the reference's offline chunked forward (scama/encoder.py:393-478) with geometry `ind` of chunk_size / stride /
+        pad_left / encoder_att_look_back_factor -> (xs [1, Tc, output_size] in the chunked layout, [Tc], None); one sequence, fp32 mode
+        (funasr_amd.uniasr.chunked_forward)."""
+        if ind is None:
+            return super().forward(xs_pad, ilens, prev_states, ctc)
+        from .uniasr import chunked_forward
+
+        out, olens, _ = chunked_forward(self, xs_pad, ilens, ind)
+        return out, torch.tensor(olens, dtype=torch.int32), None
+
     def forward_chunk(self, *a, **k):
         raise RuntimeError("the chunk state lives in the stream handle: use ParaformerStreaming.inference / StreamBatch")
 

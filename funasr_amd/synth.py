@@ -440,6 +440,48 @@ def sanm_state_dict(seed: int, model) -> Dict[str, torch.Tensor]:
     return {k: _synthetic_tensor(k, shapes[k], g) for k in sorted(shapes)}
 
 
+def uniasr_conf(output_size: int = 128, attention_heads: int = 2, linear_units: int = 64, enc_blocks: int = 2, enc2_blocks: int = 1,
+                dec_blocks: int = 2, att_layer_num: int = 2, att_layer_num2: int = 1, kernel: int = 11, chunk_size=(4, 6), stride=(2, 4),
+                pad_left=(1, 2), encoder_att_look_back_factor=(0, 1), decoder_att_look_back_factor=(1, 2), conv_kernel: int = 2,
+                conv_stride: int = 2, conv_pad=(0, 1), vocab: int = 30, input_size: int = 80) -> dict:
+    """constructor arguments of a UniASR model (the layout of the model zoo's 2-pass config.yaml files) at a chosen size: both
+    encoders SANMEncoderChunkOpt with the same chunk geometries, both decoders FsmnDecoderSCAMAOpt -- the first with sanm_shfit 0 as
+    the zoo has it and cross-attention in `att_layer_num` layers, the second with the constructor's default shift and
+    `att_layer_num2` -- both predictors CifPredictorV2 without a tail"""
+    def enc(blocks):
+        return {"output_size": output_size, "attention_heads": attention_heads, "linear_units": linear_units, "num_blocks": blocks,
+                "dropout_rate": 0.1, "positional_dropout_rate": 0.1, "attention_dropout_rate": 0.1, "input_layer": "pe",
+                "pos_enc_class": "SinusoidalPositionEncoder", "normalize_before": True, "kernel_size": 11, "sanm_shfit": 0,
+                "selfattention_layer_type": "sanm", "chunk_size": list(chunk_size), "stride": list(stride), "pad_left": list(pad_left),
+                "encoder_att_look_back_factor": list(encoder_att_look_back_factor),
+                "decoder_att_look_back_factor": list(decoder_att_look_back_factor)}
+
+    def dec(att, **extra):
+        return dict({"attention_heads": attention_heads, "linear_units": linear_units, "num_blocks": dec_blocks, "dropout_rate": 0.1,
+                     "positional_dropout_rate": 0.1, "self_attention_dropout_rate": 0.1, "src_attention_dropout_rate": 0.1,
+                     "att_layer_num": att, "kernel_size": kernel}, **extra)
+
+    pred = {"idim": output_size, "threshold": 1.0, "l_order": 1, "r_order": 1}
+    return {"encoder": "SANMEncoderChunkOpt", "encoder_conf": enc(enc_blocks), "encoder2": "SANMEncoderChunkOpt",
+            "encoder2_conf": enc(enc2_blocks), "decoder": "FsmnDecoderSCAMAOpt", "decoder_conf": dec(att_layer_num, sanm_shfit=0),
+            "decoder2": "FsmnDecoderSCAMAOpt", "decoder2_conf": dec(att_layer_num2), "predictor": "CifPredictorV2",
+            "predictor_conf": dict(pred), "predictor2": "CifPredictorV2", "predictor2_conf": dict(pred),
+            "stride_conv": "stride_conv1d", "stride_conv_conf": {"kernel_size": conv_kernel, "stride": conv_stride, "pad": list(conv_pad)},
+            "ctc_weight": 0.0, "ctc2_weight": 0.0, "lsm_weight": 0.1, "length_normalized_loss": True, "input_size": input_size,
+            "vocab_size": vocab}
+
+
+def uniasr_state_dict(seed: int, model) -> Dict[str, torch.Tensor]:
+    """synthetic weights in the layout of `model` (a UniASR module or the reference's), drawn like sanm_state_dict in the sorted order
+    of the keys. The alpha heads' biases are set to 0.5 so that a frame weighs about 0.6: the predictor's mask keeps `stride` frames
+    of a chunk, and a clip of a few dozen frames should still fire a handful of tokens"""
+    sd = sanm_state_dict(seed, model)
+    for k in sd:
+        if k.endswith("cif_output.bias"):
+            sd[k] = torch.full_like(sd[k], 0.5)
+    return sd
+
+
 def aligner_conf(output_size: int = 320, attention_heads: int = 4, linear_units: int = 1280, num_blocks: int = 30, idim: int = None,
                  upsample_type: str = "cnn_blstm", use_cif1_cnn: bool = False, input_size: int = 560) -> dict:
     """constructor arguments of a MonotonicAligner (the layout of funasr/models/monotonic_aligner/template.yaml, which the

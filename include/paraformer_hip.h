@@ -614,6 +614,48 @@ int pf_k_fsmn_step(const float* t_dev, const float* x_dev, const float* g2_dev, 
 int pf_k_cross_attention_step(const float* q_dev, const float* kv_dev, int32_t T, int32_t n, int32_t H, int32_t dk, float* out_dev,
                               void* stream);
 
+/* ---- UniASR two-pass ASR (funasr/models/uniasr/model.py): the offline chunked SAN-M encoder, `stride_conv`, the SCAMA decoder step.
+ * Chunked encoder (SANMEncoderChunkOpt.forward with `ind`, scama/encoder.py:393-478): the caller lays the frames out as overlap_chunk
+ * does (scama/chunk_utilis.py: per chunk `shift` FSMN shift rows, then `chunk` frames; pf_uniasr_gather_rows with the host's index
+ * map, -1 for a zero row, for the features AND for the positional table) and runs pf_encoder_forward over those rows after
+ * pf_encoder_set_chunk_mask(e, chunk, stride, shift, look_back): every block's attention then takes mask_att_chunk_encoder -- a row
+ * sees its own chunk and, when it is one of the chunk's first `stride` frames, the first `stride` frames of each of the `look_back`
+ * chunks before -- and its FSMN memory mask_shfit_chunk, both worked out from the geometry on the device (no [Tc, Tc] mask).
+ * chunk == 0 switches the masks off. fp32 mode only (pf_encoder_set_precision(e, 0)); not together with pf_encoder_set_vad_mask. */
+int pf_encoder_set_chunk_mask(pf_encoder* e, int32_t chunk, int32_t stride, int32_t shift, int32_t look_back);
+/* out_dev[r] = idx_dev[r] >= 0 ? src_dev[idx_dev[r]] : 0 for r < n: rows of D floats (D % 4 == 0), source rows ld_src floats apart,
+ * n_src of them (an index at or past n_src reads as a zero row). split_chunk and remove_chunk as gathers. No sync. */
+int pf_uniasr_gather_rows(const float* src_dev, int32_t ld_src, int32_t n_src, const int32_t* idx_dev, float* out_dev, int32_t n, int32_t D,
+                          void* stream);
+/* Conv1dSubsampling (transformer/utils/subsampling.py:332-388) over the concatenation [a | b] along the features, read from its two
+ * sources: out_dev [Tout, Cout] = relu(conv1d(pad(x, (pad_left, pad_right)), w [Cout, Da + Db, taps], stride) + bias), x = [a [T, Da] |
+ * b [T, Db]]; Tout at most (T + pad_left + pad_right - taps) / stride + 1. taps <= 8, taps (Da + Db) floats within 48 KiB. No sync. */
+int pf_uniasr_stride_conv(const float* a_dev, int32_t Da, const float* b_dev, int32_t Db, int32_t T, const float* w_dev, const float* bias_dev,
+                          int32_t Cout, int32_t taps, int32_t stride, int32_t pad_left, int32_t pad_right, float* out_dev, int32_t Tout,
+                          void* stream);
+/* SCAMA decoder step (scama/decoder.py FsmnDecoderSCAMAOpt.forward_one_step without concat_embeds): pf_fsmndecoder's stepper -- the
+ * same config, tensor names, limits, begin and reorder -- whose step restricts the softmax of every `decoders.{i}` cross-attention to
+ * the keys j with key_lo <= j < key_hi and mask_row_dev[j] != 0 (mask_row_dev [T] floats on the device, NULL: the whole window); no
+ * other K / V row is read. A position without a visible key gets a zero context (the reference fills the scores with the dtype's
+ * minimum, takes the softmax and fills the masked probabilities with 0). */
+typedef struct pf_scamadecoder pf_scamadecoder;
+pf_scamadecoder* pf_scamadecoder_create(const pf_fsmndecoder_config* cfg);
+void pf_scamadecoder_destroy(pf_scamadecoder* h);
+int pf_scamadecoder_set_tensor(pf_scamadecoder* h, const char* name, const float* data, int64_t numel);
+int pf_scamadecoder_missing(const pf_scamadecoder* h);
+int pf_scamadecoder_begin(pf_scamadecoder* h, const float* memory_dev, int32_t T, int32_t max_len, int32_t max_hyp, void* stream);
+int pf_scamadecoder_step(pf_scamadecoder* h, const int32_t* tokens_host, int32_t pos, int32_t n_hyp, const float* mask_row_dev,
+                         int32_t key_lo, int32_t key_hi, float* logp_dev, void* stream);
+int pf_scamadecoder_reorder(pf_scamadecoder* h, const int32_t* parents_host, int32_t n_hyp, void* stream);
+/* single-kernel hooks (tests; see csrc/uniasr.h): the chunk-masked attention over qkv_dev [B T, 3 H dk] (q | k | v), the chunk-masked
+ * FSMN memory, and the masked few-query cross-attention over kv_dev [T, 2 H dk] */
+int pf_k_chunk_attention(const float* qkv_dev, const int32_t* klens_dev, int32_t B, int32_t T, int32_t H, int32_t dk, int32_t chunk,
+                         int32_t stride, int32_t shift, int32_t look_back, float* out_dev, void* stream);
+int pf_k_chunk_fsmn(const float* in_dev, int32_t ldin, const float* w_dev, const int32_t* lens_dev, int32_t B, int32_t T, int32_t C, int32_t K,
+                    int32_t left_pad, int32_t chunk, int32_t stride, int32_t shift, float* out_dev, void* stream);
+int pf_k_scama_attention(const float* q_dev, const float* kv_dev, int32_t T, const float* mask_row_dev, int32_t key_lo, int32_t key_hi,
+                         int32_t n, int32_t H, int32_t dk, float* out_dev, void* stream);
+
 /* single-kernel hooks of the two above (tests): the relative-position attention (qkv_dev [B T, 3 D] q | k | v, P_dev [T or 2 T - 1, D],
  * u_dev / v_dev [H, 64], klens_dev [B] -> out_dev [B T, D]; see csrc/conformer.h) and the GLU + depthwise conv + BatchNorm + Swish
  * row kernel (g_dev [B T, 2 D], dw_dev [D, taps], BatchNorm folded to scale / shift [D] -> y_dev [B T, D]) */
