@@ -8,6 +8,9 @@ and the chunk loop itself -- over a seeded clip fed in two calls (mid-stream + f
 The only substitution: `torchaudio.compliance.kaldi.fbank` (third-party, absent) is the oracle's `kaldi_fbank`,
 itself pinned to the reference-vendored kaldi-native-fbank in tests/test_oracle.py.
 Per chunk it records the online features, the encoder output, the CIF state and the token ids.
+--geometries / --right0: other chunk sizes and look-backs of the same clip (streaming_geometries.npz, streaming_right0.npz).
+--sparse: the predictor's cif_output.bias lowered to -3.0 / -2.5, so that most chunks fire no token and the reference skips its
+decoder there (streaming_sparse.npz).
 """
 from __future__ import annotations
 
@@ -198,8 +201,47 @@ def main_right0():
     print(f"wrote {path} ({os.path.getsize(path) / 1024:.1f} KB)")
 
 
+SPARSE = (([0, 10, 5], 4, 1, -3.0),
+          ([5, 10, 5], 1, 2, -2.5))       # the first-chunk-untrimmed encoder ring, decoder look-back over two chunks
+
+
+def main_sparse():
+    """sessions in which most chunks fire NO token: the predictor's cif_output.bias lowered on the reference model (and in the synth
+    state dict a test builds), so that generate_chunk skips the decoder (paraformer_streaming/model.py:589-590) on chunks
+    interleaved with decoding ones -> tests/golden/streaming_sparse.npz (per chunk what streaming.npz records)"""
+    model, frontend, cfg, enc_conf = build()
+    _, wav, n1 = clip()
+    arrs, sessions = {}, []
+    for si, (chunk, enc_lb, dec_lb, bias) in enumerate(SPARSE):
+        want = synth.paraformer_state_dict(cfg, seed=SEED, cif_bias=bias)["predictor.cif_output.bias"]
+        with torch.no_grad():
+            model.predictor.cif_output.bias.copy_(want)
+        assert torch.equal(model.predictor.cif_output.bias.detach(), want)
+        records = run(model, frontend, enc_conf, wav, n1, chunk, enc_lb, dec_lb)
+        empty = [len(r["tokens"]) == 0 for r in records]
+        # what makes the file worth having
+        assert sum(empty) >= 3, ("fewer than three chunks whose decode returns nothing", chunk, empty)
+        assert any(e and not p for p, e in zip(empty, empty[1:])), ("no empty chunk directly after a decoding one", chunk, empty)
+        assert records[-1]["tail"], ("no tail chunk", chunk)
+        sessions.append(dict(chunk=chunk, enc_lb=enc_lb, dec_lb=dec_lb, cif_bias=bias, n_chunks=len(records)))
+        for i, r in enumerate(records):
+            arrs[f"s{si}_feats_{i}"] = r["feats"].astype(np.float32)
+            arrs[f"s{si}_enc_{i}"] = r["enc"].astype(np.float32)
+            arrs[f"s{si}_tokens_{i}"] = np.asarray(r["tokens"], dtype=np.int64)
+            arrs[f"s{si}_cif_alphas_{i}"] = r["cif_alphas"].astype(np.float32)
+            arrs[f"s{si}_cif_hidden_{i}"] = r["cif_hidden"].astype(np.float32)
+            arrs[f"s{si}_flags_{i}"] = np.asarray([r["is_final"], r["tail"], r["start_idx"]], dtype=np.int64)
+    path = os.path.join(GOLD, "streaming_sparse.npz")
+    np.savez_compressed(path, sessions=json.dumps(sessions), seed=np.int64(SEED), **arrs)
+    size = os.path.getsize(path)
+    print(f"wrote {path} ({size / 1024:.1f} KB)")
+    assert size < os.path.getsize(os.path.join(GOLD, "streaming_right0.npz")) and size <= 1 << 20, size
+
+
 if __name__ == "__main__":
-    if "--geometries" in sys.argv:
+    if "--sparse" in sys.argv:
+        main_sparse()
+    elif "--geometries" in sys.argv:
         main_geometries()
     elif "--right0" in sys.argv:
         main_right0()

@@ -248,9 +248,10 @@ def generate_chunk(feats: Tensor, st: dict, sd: SD, cfg: dict, is_final: bool, t
     ids: List[int] = []
     if n >= 1:
         logits = decoder_chunk(enc, embeds, st, sd, cfg["decoder"])
-        raw = torch.log_softmax(logits, dim=-1)[0].argmax(-1).tolist()
+        logp = torch.log_softmax(logits, dim=-1)[0]
+        raw = logp.argmax(-1).tolist()
         ids = [t for t in raw if t not in (0, 1, 2)]
-        rec.update(embeds=embeds, raw_ids=raw)
+        rec.update(embeds=embeds, raw_ids=raw, logp=logp)
     if trace is not None:
         trace.append(rec)
     return ids

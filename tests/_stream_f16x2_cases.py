@@ -5,7 +5,9 @@ an assertion prints its message and exits 1.
 The streaming step in its f16x2 form (StreamBatch(precision="f16x2"), pf_stream_set_option("gemm_mode", 3)): every GEMM of
 the step on the fp16 matrix cores with two-plane operands (fp32-class results), everything else as in the default step.
 Bars are the default step's: token ids / counts / position counter equal to the REFERENCE's ParaformerStreaming sessions
-(tests/golden/streaming.npz, streaming_geometries.npz), encoder window and carried CIF state within 1e-3."""
+(tests/golden/streaming.npz, streaming_geometries.npz, streaming_sparse.npz), encoder window and carried CIF state within 1e-3.
+The batch_* / sparse_* cases hold EVERY stream of a batch, and steps in which a stream fires no token, to the per-stream oracle and
+to the one-stream session (inputs, their preconditions and the bars: tests/_stream_batch_common.py)."""
 import json
 import os
 import sys
@@ -221,6 +223,123 @@ def case_oracle_geometry_many_tokens(dev):
         assert [t for t in ids[0] if t not in (0, 1, 2)] == oids, (i, ids[0], oids)
         assert len(ids[0]) == trace[0]["n"], i
     sb.close()
+
+
+# ---- every stream of a batch, and steps that fire no token (tests/_stream_batch_common.py; the fp32 step: tests/test_streaming_batch_gpu.py)
+def case_sparse_reference_eager(dev):
+    from tests import _stream_batch_common as B
+    worst, zeros = B.reference_sparse_sessions(dev, "f16x2", False)
+    print(f"f16x2 eager: max |enc - reference| = {worst:.3e}, zero-fire steps = {zeros}")
+
+
+def case_sparse_reference_graph(dev):
+    from tests import _stream_batch_common as B
+    worst, zeros = B.reference_sparse_sessions(dev, "f16x2", True)
+    print(f"f16x2 graph: max |enc - reference| = {worst:.3e}, zero-fire steps = {zeros}")
+
+
+def _batch_vs_oracle(dev, name, S):
+    from tests import _stream_batch_common as B
+    seeds = B.GEOMETRIES[name]["seeds"][:S]
+    assert len(seeds) == S
+    B.check_inputs(name, seeds)
+    out, rows = B.run_batch(dev, name, seeds, "f16x2")
+    if name == "rows96":
+        assert rows > 48, rows                      # the 96-row instance of dec_fsmn_chunk_kernel
+    worst, zeros = B.check_vs_oracle(out, name, seeds, "f16x2")
+    assert zeros > 0 or not B.GEOMETRIES[name]["sparse"]
+    print(f"f16x2 {name} S={S}: max |enc - oracle| = {worst:.3e}, zero-fire (stream, step) pairs = {zeros}, token rows = {rows}")
+
+
+def case_batch_vs_oracle_sparse_a(dev):
+    _batch_vs_oracle(dev, "sparse_a", 4)
+
+
+def case_batch_vs_oracle_sparse_b(dev):
+    _batch_vs_oracle(dev, "sparse_b", 4)
+
+
+def case_batch_vs_oracle_sparse_c(dev):
+    _batch_vs_oracle(dev, "sparse_c", 4)
+
+
+def case_batch_vs_oracle_sparse_d(dev):
+    _batch_vs_oracle(dev, "sparse_d", 4)
+
+
+def case_batch_vs_oracle_rows96(dev):
+    _batch_vs_oracle(dev, "rows96", 2)
+
+
+def case_batch_streams_equal_their_one_stream_sessions(dev):
+    """stream k of a 4-stream batch == the 1-stream session on stream k's features, bitwise (ids, encoder window, carried CIF state);
+    the batch with its streams reversed gives the reversed results -- under the default options too: the f16x2 GEMMs give the same bits
+    at every block shape"""
+    from tests import _stream_batch_common as B
+    for name, options in (("sparse_a", ({"ln_carry": 0}, {"ln_carry": 2}, None)), ("sparse_d", (None,))):
+        seeds = B.GEOMETRIES[name]["seeds"][:4]
+        B.check_inputs(name, seeds)
+        for opts in options:
+            batch, _ = B.run_batch(dev, name, seeds, "f16x2", opts)
+            for k, s in enumerate(seeds):
+                one, _ = B.run_batch(dev, name, [s], "f16x2", opts)
+                B.assert_same(one, batch, f"{name} {opts}: stream {k} alone / in the batch", streams_b=[k])
+            rev, _ = B.run_batch(dev, name, seeds[::-1], "f16x2", opts)
+            B.assert_same(batch, rev, f"{name} {opts}: streams reversed", streams_b=[3, 2, 1, 0])
+
+
+def case_batch_gate_forms_agree(dev):
+    """"kv_batched" 1 (one GEMM over the concatenated K | V weights, one gated append) / 0 (per layer, the append gated inside the
+    cross-attention or its fallback launch) and "ln_folded" 0 / 1: bitwise on every stream of the sparse session"""
+    from tests import _stream_batch_common as B
+    for name in ("sparse_a", "sparse_d"):
+        seeds = B.GEOMETRIES[name]["seeds"][:4]
+        zeros = B.check_inputs(name, seeds)
+        assert zeros >= 8
+        plain, _ = B.run_batch(dev, name, seeds, "f16x2", {"ln_folded": 0, "kv_batched": 0, "short_k": 0})
+        B.check_vs_oracle(plain, name, seeds, "plain launches")
+        for folded, kv in ((0, 1), (1, 0), (1, 1)):
+            other, _ = B.run_batch(dev, name, seeds, "f16x2", {"ln_folded": folded, "kv_batched": kv, "short_k": 0})
+            B.assert_same(plain, other, f"{name} ln_folded {folded} kv_batched {kv}")
+        print(f"f16x2 {name}: zero-fire (stream, step) pairs = {zeros}")
+
+
+def case_batch_graph_and_reset_with_diverged_streams(dev):
+    from tests import _stream_batch_common as B
+    name, seeds = "sparse_a", B.GEOMETRIES["sparse_a"]["seeds"][:4]
+    B.check_inputs(name, seeds)
+    eager, _ = B.run_batch(dev, name, seeds, "f16x2", graph=False)
+    graph, _ = B.run_batch(dev, name, seeds, "f16x2", graph=True)
+    B.assert_same(eager, graph, "graph replay / eager")
+    again, _ = B.run_batch(dev, name, seeds, "f16x2", graph=True, reset_after=4)
+    B.assert_same(graph, again, "after reset() / fresh")
+
+
+def case_batch_66_streams(dev):
+    """66 streams (the precision such a batch gets by default; the second block of stream_advance_dec_kernel): six sparse feature
+    sequences, each eleven times in a shuffled order -- every stream bitwise equal to the 1-stream session on its sequence, and those
+    six sessions against the oracle"""
+    from funasr_amd.paraformer_streaming import StreamBatch
+    from tests import _stream_batch_common as B
+    name, six = "sparse_a", B.GEOMETRIES["sparse_a"]["seeds"]
+    assert len(six) == 6 and 66 >= StreamBatch.AUTO_F16X2_MIN_STREAMS
+    zeros = B.check_inputs(name, six)
+    order = torch.randperm(66, generator=torch.Generator().manual_seed(66)).tolist()
+    which = [i % 6 for i in order]                               # stream k carries sequence which[k]
+    assert sorted(which) == sorted(list(range(6)) * 11) and which[:6] != list(range(6))
+    ones = []
+    for s in six:
+        one, _ = B.run_batch(dev, name, [s], "f16x2")
+        B.check_vs_oracle(one, name, [s], "f16x2, one stream")
+        ones.append(one)
+    batch, _ = B.run_batch(dev, name, [six[w] for w in which], "f16x2")
+    for k, w in enumerate(which):
+        for i, ((ia, ea, pa), (ib, eb, pb)) in enumerate(zip(ones[w], batch)):
+            at = ("stream", k, "sequence", w, "step", i)
+            assert ia[0] == ib[k], (at, ia[0], ib[k])
+            assert torch.equal(ea[0], eb[k]), (at, (ea[0] - eb[k]).abs().max().item())
+            assert pa["cif_alphas"][0] == pb["cif_alphas"][k] and torch.equal(pa["cif_hidden"][0], pb["cif_hidden"][k]), at
+    print(f"f16x2 S=66: zero-fire (stream, step) pairs = {zeros * 11}")
 
 
 CASES = {k[5:]: v for k, v in globals().items() if k.startswith("case_")}

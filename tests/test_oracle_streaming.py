@@ -136,6 +136,58 @@ def test_streaming_oracle_reproduces_the_reference_when_chunk_right_is_zero():
     assert len(gg["s1_tokens_6"]) == 43 and gg["s1_feats_6"].shape[1] == 9          # the growing-window quirk at work
 
 
+def test_streaming_oracle_reproduces_the_reference_sessions_in_which_chunks_fire_nothing():
+    """cif_output.bias lowered to -3.0 / -2.5 on the reference's ParaformerStreaming (oracle/make_golden_streaming.py --sparse,
+    tests/golden/streaming_sparse.npz): most chunks fire no token, the reference skips the decoder there
+    (paraformer_streaming/model.py:589-590) and the decoder's caches stay as they were. Pins the oracle's `if n >= 1` branch:
+    token ids and position counter equal, encoder window 2e-5 and carried CIF weight 1e-5 on every chunk (the bars of
+    streaming.npz above); the carried CIF frame, a weighted mean of encoder rows, meets the encoder window's bar."""
+    g, cfg, _, wav, cmvn = load()
+    gg = np.load(os.path.join(GOLD, "streaming_sparse.npz"), allow_pickle=False)
+    sessions = json.loads(str(gg["sessions"]))
+    assert [(s["chunk"], s["enc_lb"], s["dec_lb"], s["cif_bias"]) for s in sessions] == [([0, 10, 5], 4, 1, -3.0), ([5, 10, 5], 1, 2, -2.5)]
+    for si, s in enumerate(sessions):
+        sd = synth.paraformer_state_dict(cfg, seed=int(gg["seed"]), cif_bias=s["cif_bias"])
+        st = S.model_init(cfg, tuple(s["chunk"]), s["enc_lb"], s["dec_lb"])
+        fired = []
+        for i in range(s["n_chunks"]):
+            fin, tail, start_idx = (int(v) for v in gg[f"s{si}_flags_{i}"])
+            if tail:
+                st["tail_chunk"] = True
+                feats = st["feats"]
+            else:
+                feats = torch.from_numpy(gg[f"s{si}_feats_{i}"])
+            trace = []
+            with torch.no_grad():
+                ids = S.generate_chunk(feats, st, sd, cfg, bool(fin), trace)
+            assert ids == gg[f"s{si}_tokens_{i}"].tolist(), (s, i)
+            assert st["start_idx"] == start_idx, (s, i)
+            enc_ref = torch.from_numpy(gg[f"s{si}_enc_{i}"])
+            assert trace[0]["enc"].shape == enc_ref.shape, (s, i)
+            assert (trace[0]["enc"] - enc_ref).abs().max().item() < 2e-5, (s, i)
+            assert abs(float(st["cif_alphas"]) - float(gg[f"s{si}_cif_alphas_{i}"][0])) < 1e-5, (s, i)
+            assert (st["cif_hidden"].reshape(-1) - torch.from_numpy(gg[f"s{si}_cif_hidden_{i}"])).abs().max().item() < 2e-5, (s, i)
+            fired.append(trace[0]["n"])
+            # (in these sessions the reference returns no token exactly where nothing fired: the GPU tests rely on it for the counts)
+            assert (trace[0]["n"] == 0) == (len(ids) == 0), (s, i)
+        assert sum(n == 0 for n in fired) >= 3, (s, fired)
+        assert any(a >= 1 and b == 0 for a, b in zip(fired, fired[1:])), (s, fired)
+        assert int(gg[f"s{si}_flags_{s['n_chunks'] - 1}"][1]) == 1                 # ends with a tail chunk
+
+
+def test_batch_session_inputs_meet_the_conditions_their_seeds_were_chosen_by():
+    """the inputs of tests/test_streaming_batch_gpu.py and of the batch cases of tests/_stream_f16x2_cases.py (fixed with the oracle
+    alone): zero-fire steps interleaved with decoding ones and different from stream to stream, every integrate-and-fire decision
+    2e-4 from the threshold, every decoded row's top-two log-probabilities 1e-3 apart -- so that "token ids equal" is a fair
+    demand of an fp32-class step. The GPU tests assert the same before they run."""
+    from tests import _stream_batch_common as C
+    for name, g in C.GEOMETRIES.items():
+        zeros = C.check_inputs(name)
+        assert (zeros >= 2 * len(g["seeds"])) == g["sparse"], (name, zeros)
+    C.check_inputs("sparse_a", C.GEOMETRIES["sparse_a"]["seeds"][:4])
+    assert 6 <= min(g["steps"] for g in C.GEOMETRIES.values()) and max(g["steps"] for g in C.GEOMETRIES.values()) <= 10
+
+
 def test_stream_batch_refuses_the_geometry_whose_reference_window_is_the_whole_history():
     from funasr_amd.paraformer_streaming import ParaformerStreaming, StreamBatch
     g, cfg, sd, wav, cmvn = load()
