@@ -99,6 +99,14 @@ class pf_tfencoder_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("input_dim", "d_model", "n_heads", "ffn_dim", "n_blocks", "precision")] + [("ln_eps", C.c_float)]
 
 
+class pf_textencoder_config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("vocab_size", "d_model", "n_heads", "ffn_dim", "n_blocks")] + [("ln_eps", C.c_float)]
+
+
+class pf_fusion_config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("d_model", "n_heads", "ffn_dim")] + [("ln_eps", C.c_float)]
+
+
 class pf_transducer_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("vocab", "enc_dim", "embed_dim", "hidden", "n_layers", "joint_dim", "blank_id")]
 
@@ -230,6 +238,18 @@ SIGNATURES = {
     "pf_tfencoder_forward": (C.c_int, [_vp, _vp, _pi32, _i32, _i32, _vp, _pi32, _vp]),
     "pf_k_tf_attention": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "pf_k_tf_embed_rows": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _f32, _vp, _vp]),
+    "pf_textencoder_create": (_vp, [C.POINTER(pf_textencoder_config)]),
+    "pf_textencoder_destroy": (None, [_vp]),
+    "pf_textencoder_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),
+    "pf_textencoder_missing": (C.c_int, [_vp]),
+    "pf_textencoder_forward": (C.c_int, [_vp, _pi32, _pi32, _i32, _i32, _vp, _vp]),
+    "pf_fusion_create": (_vp, [C.POINTER(pf_fusion_config)]),
+    "pf_fusion_destroy": (None, [_vp]),
+    "pf_fusion_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),
+    "pf_fusion_missing": (C.c_int, [_vp]),
+    "pf_fusion_forward": (C.c_int, [_vp, _vp, _pi32, _vp, _pi32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "pf_k_tf_cross_attention": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "pf_k_text_embed_rows": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp]),
     "pf_tdecoder_create": (_vp, [C.POINTER(pf_tdecoder_config)]),
     "pf_tdecoder_destroy": (None, [_vp]),
     "pf_tdecoder_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),

@@ -46,6 +46,7 @@ from . import conformer as _conformer  # noqa: F401  (registers Conformer / Conf
 from . import transformer as _transformer  # noqa: F401  (registers Transformer / TransformerEncoder)
 from . import sanm as _sanm  # noqa: F401  (registers SANM / FsmnDecoder)
 from . import uniasr as _uniasr  # noqa: F401  (registers UniASR / FsmnDecoderSCAMAOpt)
+from . import lcbnet as _lcbnet  # noqa: F401  (registers LCBNet / TransformerTextEncoder / FusionSANEncoder / ConvBiasPredictor)
 from . import transducer as _transducer  # noqa: F401  (registers Transducer / rnnt_decoder / joint_network)
 from . import contextual_paraformer as _contextual_paraformer  # noqa: F401  (registers ContextualParaformer + its decoder)
 from . import ct_transformer as _ct_transformer  # noqa: F401  (registers CTTransformer)

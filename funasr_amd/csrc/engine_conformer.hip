@@ -7,7 +7,9 @@
 // enc_set_precision and enc_num_frames are the entry points of both, worded by the family. Stepper is the base of both decoder
 // steppers: their state, the named Linear / LayerNorm of a step (lin / norm), the cross-attention sub-block and the output tail;
 // begin_common, step_common_checks and reorder_common are the argument checks of both. Cf, Tf, Td and Fd add what is their own: the
-// block loops, the K / V cache with its device reorder, the FSMN windows with their position rule.
+// block loops, the K / V cache with its device reorder, the FSMN windows with their position rule. The LCB-Net handles (pf_textencoder_*,
+// pf_fusion_*; kernels in lcbnet.hip) sit on the same base: the text encoder is the Transformer encoder's block loop (SubEnc::tf_blocks)
+// behind token rows instead of the subsampling, the fusion layer that block with a cross-attention between its two halves.
 //
 // Encoder forward over the zero-padded batch [B, Tin, F] (the reference runs Conv2dSubsampling and the convolution module over
 // the padded tensor without masking, so every row of the batch is computed and a clip's frames depend on the batch's length):
@@ -36,6 +38,7 @@
 #include "engine_internal.h"
 #include "conformer.h"
 #include "uniasr.h"
+#include "lcbnet.h"
 
 using namespace pf;
 
@@ -114,8 +117,12 @@ template <class H> int table_set(H* h, const char* null_msg, const char* name, c
 }
 template <class H> int table_missing(const H* h) { return h ? h->tt.missing() : -1; }
 
-// What the two encoders over the Conv2dSubsampling front share. Cfg: pf_conformer_config / pf_tfencoder_config (the fields read here
-// carry the same names in both).
+// the a-priori plane exponents of one Transformer encoder block (precision 3)
+struct TfBlockX { int e_mha_in = 0, e_att = 0, e_ff_in = 0, e_ff_h = 0; };
+
+// What the encoders of the family share: the two over the Conv2dSubsampling front, and the LCB-Net handles, whose rows come from
+// token ids (text encoder) or from the caller (fusion layer). Cfg: pf_conformer_config / pf_tfencoder_config / LcbCfg (the fields
+// read here carry the same names in all).
 template <class Cfg> struct SubEnc {
     Cfg cfg;
     TensorTable tt;
@@ -137,23 +144,29 @@ template <class Cfg> struct SubEnc {
         if (out_bound) *out_bound = hb;
         return 0;
     }
-    // The prologue of a forward: frame counts, the clips' encoder frames into klens (and olens), the buffers (hid: hid_w floats per
-    // row), the subsampling, and its rows x sqrt(D) (+ pe) as the [B T, D] rows of xa.
-    int front(const float* feats, const int32_t* lens, int B, int Tin, int hid_w, const float* pe, int32_t* olens, hipStream_t fs) {
+    // What every front begins with: B sequences of T_ rows are in flight on fs; the buffers (hid: hid_w floats per row), the valid
+    // rows kl [B] into klens.
+    int rows(int B, int T_, int hid_w, const int32_t* kl, hipStream_t fs) {
         const int D = cfg.d_model;
-        const int T1 = (Tin - 3) / 2 + 1;
-        T = (T1 - 3) / 2 + 1; Mi = B * T; s = fs;
-        std::vector<int32_t> kl(B);
-        for (int b = 0; b < B; ++b) {
-            kl[b] = CfSub::out_len(lens[b], Tin);
-            if (olens) olens[b] = kl[b];
-        }
+        T = T_; Mi = B * T; s = fs;
         const size_t M = (size_t)Mi;
         if (xa.ensure(sizeof(float) * M * D) || xb.ensure(sizeof(float) * M * D) || xn.ensure(sizeof(float) * M * D) ||
             qkv.ensure(sizeof(float) * M * 3 * D) || att.ensure(sizeof(float) * M * D) || hid.ensure(sizeof(float) * M * hid_w) ||
             klens.ensure(sizeof(int32_t) * B))
             return -2;
-        if (upload_h2d(klens.p, kl.data(), sizeof(int32_t) * B, s)) return -2;
+        return upload_h2d(klens.p, kl, sizeof(int32_t) * B, s) ? -2 : 0;
+    }
+    // The prologue of a forward behind the subsampling: frame counts, the clips' encoder frames into klens (and olens), the buffers,
+    // the subsampling, and its rows x sqrt(D) (+ pe) as the [B T, D] rows of xa.
+    int front(const float* feats, const int32_t* lens, int B, int Tin, int hid_w, const float* pe, int32_t* olens, hipStream_t fs) {
+        const int D = cfg.d_model;
+        const int T1 = (Tin - 3) / 2 + 1;
+        std::vector<int32_t> kl(B);
+        for (int b = 0; b < B; ++b) {
+            kl[b] = CfSub::out_len(lens[b], Tin);
+            if (olens) olens[b] = kl[b];
+        }
+        if (int rc = rows(B, (T1 - 3) / 2 + 1, hid_w, kl.data(), fs)) return rc;
         const float* rows;
         if (int rc = sub_.forward(tt, planes, feats, B, Tin, cfg.input_dim, D, D, &rows, s)) return rc;
         return launch_cf_scale_rows(rows, T + 1, xa.as<float>(), B, T, D, sqrtf((float)D), pe, s);
@@ -169,6 +182,32 @@ template <class Cfg> struct SubEnc {
     int ln(const std::string& p, const float* in, float* o) {
         const int D = cfg.d_model;
         return layernorm(in, D, tt.get(p + "weight"), tt.get(p + "bias"), o, D, Mi, D, D, cfg.ln_eps, s);
+    }
+    // The block loop of the Transformer encoders behind either front (the subsampling of the audio encoder, the token rows of the
+    // LCB-Net text encoder), over the rows the front left in xa: per block `encoders.i.` x += linear_out(attention(LN1 x)), keys at or
+    // past klens masked; x += w_2(relu(w_1(LN2 x))); then after_norm -> out [B T, D].
+    int tf_blocks(const std::vector<TfBlockX>& bx, int B, float* out) {
+        const int D = cfg.d_model, FF = cfg.ffn_dim;
+        float *x = xa.as<float>(), *y = xb.as<float>(), *xn_ = xn.as<float>(), *qkv_ = qkv.as<float>(), *att_ = att.as<float>(),
+              *hid_ = hid.as<float>();
+        int rc;
+        for (int i = 0; i < cfg.n_blocks; ++i) {
+            const std::string p = blk(i);
+            const TfBlockX& e = bx[i];
+            if ((rc = ln(p + "norm1.", x, xn_))) return rc;
+            const char* names[3] = {"self_attn.linear_q.", "self_attn.linear_k.", "self_attn.linear_v."};
+            for (int j = 0; j < 3; ++j)
+                if ((rc = lin(xn_, D, p + names[j], D, nullptr, qkv_ + (size_t)j * D, 3 * D, e.e_mha_in))) return rc;
+            if ((rc = launch_tf_attention(qkv_, klens.as<int>(), B, T, cfg.n_heads, att_, s))) return rc;
+            if ((rc = lin(att_, D, p + "self_attn.linear_out.", D, x, y, D, e.e_att))) return rc;
+            std::swap(x, y);
+            if ((rc = ln(p + "norm2.", x, xn_))) return rc;
+            if ((rc = lin(xn_, D, p + "feed_forward.w_1.", FF, nullptr, hid_, FF, e.e_ff_in))) return rc;
+            if ((rc = launch_cf_act(hid_, (size_t)Mi * FF, 0, s))) return rc;
+            if ((rc = lin(hid_, FF, p + "feed_forward.w_2.", D, x, y, D, e.e_ff_h))) return rc;
+            std::swap(x, y);
+        }
+        return ln("after_norm.", x, out);
     }
 };
 
@@ -311,8 +350,6 @@ int Cf::forward(const float* feats, const int32_t* lens, int B, int Tin, float* 
 // w_1, ReLU, w_2 (+ residual); after_norm. precision 3: the block GEMMs from two-plane fp16 operands, exponents from a-priori
 // bounds: the LayerNorm bounds for the q / k / v and w_1 operands, the row-L1 bound of linear_v for the attention output (a convex
 // combination of value rows) and the row-L1 bound of w_1 for the hidden rows (ReLU does not enlarge it).
-struct TfBlockX { int e_mha_in = 0, e_att = 0, e_ff_in = 0, e_ff_h = 0; };
-
 struct Tf : SubEnc<pf_tfencoder_config> {
     std::vector<TfBlockX> bx;
     int prepare(hipStream_t s);
@@ -335,29 +372,42 @@ int Tf::prepare(hipStream_t s) {
 }
 
 int Tf::forward(const float* feats, const int32_t* lens, int B, int Tin, float* out, int32_t* olens, hipStream_t s) {
-    const pf_tfencoder_config& c = cfg;
-    const int D = c.d_model, FF = c.ffn_dim;
-    int rc;
-    if ((rc = front(feats, lens, B, Tin, FF, tt.get("pos_table"), olens, s))) return rc;
-    float *x = xa.as<float>(), *y = xb.as<float>(), *xn = this->xn.as<float>(), *qkv = this->qkv.as<float>(), *att = this->att.as<float>(),
-          *hid = this->hid.as<float>();
-    for (int i = 0; i < c.n_blocks; ++i) {
-        const std::string p = blk(i);
-        const TfBlockX& e = bx[i];
-        if ((rc = ln(p + "norm1.", x, xn))) return rc;
-        const char* names[3] = {"self_attn.linear_q.", "self_attn.linear_k.", "self_attn.linear_v."};
-        for (int j = 0; j < 3; ++j)
-            if ((rc = lin(xn, D, p + names[j], D, nullptr, qkv + (size_t)j * D, 3 * D, e.e_mha_in))) return rc;
-        if ((rc = launch_tf_attention(qkv, klens.as<int>(), B, T, c.n_heads, att, s))) return rc;
-        if ((rc = lin(att, D, p + "self_attn.linear_out.", D, x, y, D, e.e_att))) return rc;
-        std::swap(x, y);
-        if ((rc = ln(p + "norm2.", x, xn))) return rc;
-        if ((rc = lin(xn, D, p + "feed_forward.w_1.", FF, nullptr, hid, FF, e.e_ff_in))) return rc;
-        if ((rc = launch_cf_act(hid, (size_t)Mi * FF, 0, s))) return rc;
-        if ((rc = lin(hid, FF, p + "feed_forward.w_2.", D, x, y, D, e.e_ff_h))) return rc;
-        std::swap(x, y);
-    }
-    return ln("after_norm.", x, out);
+    if (int rc = front(feats, lens, B, Tin, cfg.ffn_dim, tt.get("pos_table"), olens, s)) return rc;
+    return tf_blocks(bx, B, out);
+}
+
+// ================================================================================================ LCB-Net: text encoder, fusion layer
+// funasr/models/lcbnet/encoder.py. TransformerTextEncoder: Embedding x sqrt(D) + pe -> the block loop of the Transformer encoder ->
+// after_norm; its front is the token rows instead of the subsampling. FusionSANEncoder (SelfSrcAttention), ONE layer over the audio
+// encoder's rows x and the text encoder's rows mem: the block above with a cross-attention between its two halves,
+//   x += self_attn(norm1 x); x += src_attn(norm2 x, mem, mem); x += ffn(norm3 x).
+// Both handles run exact-fp32 GEMMs (precision 0 of the shared helpers): no a-priori bound crosses the handles (the text encoder's
+// after_norm feeds the fusion layer's K / V projections), and the rows are few and run once per utterance.
+struct LcbCfg { int vocab_size = 0, d_model = 0, n_heads = 0, ffn_dim = 0, n_blocks = 0, precision = 0, input_dim = 0; float ln_eps = 0.f; };
+
+struct Te : SubEnc<LcbCfg> {
+    std::vector<TfBlockX> bx;
+    DevBuf ids;
+};
+
+struct Fu : SubEnc<LcbCfg> {
+    DevBuf kv, mlens;
+};
+
+bool lcb_shape_ok(int d_model, int n_heads, int ffn_dim, float ln_eps) {
+    return d_model > 0 && d_model <= 2048 && n_heads > 0 && d_model == 64 * n_heads && ffn_dim > 0 && ffn_dim % 32 == 0 && ln_eps > 0.f;
+}
+
+// the tensors of one block of plain attention + feed-forward: `attns` attention groups, `norms` LayerNorms
+int add_tf_block(TensorTable& tt, const std::string& p, std::initializer_list<const char*> attns, std::initializer_list<const char*> norms,
+                 int D, int FF) {
+    int rc = 0;
+    for (const char* a : attns)
+        for (const char* n : {"linear_q.", "linear_k.", "linear_v.", "linear_out."}) rc |= tt.add_linear(p + a + n, D, D);
+    rc |= tt.add_linear(p + "feed_forward.w_1.", FF, D);
+    rc |= tt.add_linear(p + "feed_forward.w_2.", D, FF);
+    for (const char* n : norms) rc |= tt.add_linear(p + n, D, 1);
+    return rc;
 }
 
 // ================================================================================================ decoder steppers
@@ -559,13 +609,7 @@ pf_tfencoder* pf_tfencoder_create(const pf_tfencoder_config* cfg) {
     rc |= tt.add_linear("embed.conv.2.", D, (int64_t)D * 9);
     rc |= tt.add_linear("embed.out.0.", D, (int64_t)D * CfSub::F2(c.input_dim));
     rc |= tt.add("pos_table", (int64_t)5000 * D);
-    for (int i = 0; i < c.n_blocks; ++i) {
-        const std::string p = blk(i);
-        for (const char* n : {"linear_q.", "linear_k.", "linear_v.", "linear_out."}) rc |= tt.add_linear(p + "self_attn." + n, D, D);
-        rc |= tt.add_linear(p + "feed_forward.w_1.", FF, D);
-        rc |= tt.add_linear(p + "feed_forward.w_2.", D, FF);
-        for (const char* n : {"norm1.", "norm2."}) rc |= tt.add_linear(p + n, D, 1);
-    }
+    for (int i = 0; i < c.n_blocks; ++i) rc |= add_tf_block(tt, blk(i), {"self_attn."}, {"norm1.", "norm2."}, D, FF);
     rc |= tt.add_linear("after_norm.", D, 1);
     if (rc) return nullptr;
     return reinterpret_cast<pf_tfencoder*>(h.release());
@@ -846,6 +890,123 @@ int pf_scamadecoder_reorder(pf_scamadecoder* h, const int32_t* parents_host, int
     return pf_fsmndecoder_reorder(reinterpret_cast<pf_fsmndecoder*>(h), parents_host, n, stream);
 }
 
+// ---- LCB-Net (funasr/models/lcbnet): the text encoder over token ids and the audio-text fusion layer
+pf_textencoder* pf_textencoder_create(const pf_textencoder_config* cfg) {
+    if (!cfg) { set_error("textencoder: null config"); return nullptr; }
+    if (!(cfg->vocab_size > 0 && cfg->n_blocks >= 0 && lcb_shape_ok(cfg->d_model, cfg->n_heads, cfg->ffn_dim, cfg->ln_eps))) {
+        set_error("textencoder: unsupported config (vocab_size > 0, head dim 64, d_model <= 2048, ffn_dim % 32)");
+        return nullptr;
+    }
+    if (check_device()) return nullptr;
+    std::unique_ptr<Te> h(new Te());
+    LcbCfg& c = h->cfg;
+    c.vocab_size = cfg->vocab_size; c.d_model = cfg->d_model; c.n_heads = cfg->n_heads; c.ffn_dim = cfg->ffn_dim; c.n_blocks = cfg->n_blocks;
+    c.ln_eps = cfg->ln_eps;
+    h->bx.assign(c.n_blocks, TfBlockX());
+    TensorTable& tt = h->tt;
+    int rc = 0;
+    rc |= tt.add("embed.0.weight", (int64_t)c.vocab_size * c.d_model);
+    rc |= tt.add("pos_table", (int64_t)5000 * c.d_model);
+    for (int i = 0; i < c.n_blocks; ++i) rc |= add_tf_block(tt, blk(i), {"self_attn."}, {"norm1.", "norm2."}, c.d_model, c.ffn_dim);
+    rc |= tt.add_linear("after_norm.", c.d_model, 1);
+    if (rc) return nullptr;
+    return reinterpret_cast<pf_textencoder*>(h.release());
+}
+void pf_textencoder_destroy(pf_textencoder* h) { delete reinterpret_cast<Te*>(h); }
+int pf_textencoder_set_tensor(pf_textencoder* h, const char* name, const float* data, int64_t numel) {
+    return table_set(reinterpret_cast<Te*>(h), "textencoder_set_tensor: null", name, data, numel);
+}
+int pf_textencoder_missing(const pf_textencoder* h) { return table_missing(reinterpret_cast<const Te*>(h)); }
+int pf_textencoder_forward(pf_textencoder* hh, const int32_t* ids_host, const int32_t* lens_host, int32_t B, int32_t L, float* out,
+                           void* stream) {
+    Te* h = reinterpret_cast<Te*>(hh);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    PF_REQUIRE(h && ids_host && lens_host && out && B > 0 && B <= 65535, "textencoder_forward: null/empty argument");
+    if (L < 1 || L > 5000) { set_error("textencoder: " + std::to_string(L) + " tokens; 1 .. 5000 (the positional table holds 5000)"); return -1; }
+    const LcbCfg& c = h->cfg;
+    for (int b = 0; b < B; ++b) PF_REQUIRE(lens_host[b] >= 0 && lens_host[b] <= L, "textencoder_forward: a length exceeds the padded length");
+    for (size_t i = 0; i < (size_t)B * L; ++i)
+        if (ids_host[i] < 0 || ids_host[i] >= c.vocab_size) {
+            set_error("textencoder: token id " + std::to_string(ids_host[i]) + " outside the vocabulary of " + std::to_string(c.vocab_size));
+            return -1;
+        }
+    int rc;
+    if ((rc = h->tt.require_all("textencoder"))) return rc;
+    if ((rc = h->rows(B, L, c.ffn_dim, lens_host, s))) return rc;
+    if (h->ids.ensure(sizeof(int32_t) * (size_t)B * L) || upload_h2d(h->ids.p, ids_host, sizeof(int32_t) * (size_t)B * L, s)) return -2;
+    if ((rc = launch_text_embed_rows(h->tt.get("embed.0.weight"), h->ids.as<int>(), h->tt.get("pos_table"), sqrtf((float)c.d_model),
+                                     h->xa.as<float>(), B, L, c.d_model, s)))
+        return rc;
+    return h->tf_blocks(h->bx, B, out);
+}
+
+pf_fusion* pf_fusion_create(const pf_fusion_config* cfg) {
+    if (!cfg) { set_error("fusion: null config"); return nullptr; }
+    if (!lcb_shape_ok(cfg->d_model, cfg->n_heads, cfg->ffn_dim, cfg->ln_eps)) {
+        set_error("fusion: unsupported config (head dim 64, d_model <= 2048, ffn_dim % 32)");
+        return nullptr;
+    }
+    if (check_device()) return nullptr;
+    std::unique_ptr<Fu> h(new Fu());
+    LcbCfg& c = h->cfg;
+    c.d_model = cfg->d_model; c.n_heads = cfg->n_heads; c.ffn_dim = cfg->ffn_dim; c.ln_eps = cfg->ln_eps;
+    if (add_tf_block(h->tt, "", {"self_attn.", "src_attn."}, {"norm1.", "norm2.", "norm3."}, c.d_model, c.ffn_dim)) return nullptr;
+    return reinterpret_cast<pf_fusion*>(h.release());
+}
+void pf_fusion_destroy(pf_fusion* h) { delete reinterpret_cast<Fu*>(h); }
+int pf_fusion_set_tensor(pf_fusion* h, const char* name, const float* data, int64_t numel) {
+    return table_set(reinterpret_cast<Fu*>(h), "fusion_set_tensor: null", name, data, numel);
+}
+int pf_fusion_missing(const pf_fusion* h) { return table_missing(reinterpret_cast<const Fu*>(h)); }
+int pf_fusion_forward(pf_fusion* hh, const float* x_in, const int32_t* x_lens_host, const float* mem, const int32_t* mem_lens_host, int32_t B,
+                      int32_t T, int32_t L, int32_t add_input, float* out, void* stream) {
+    Fu* h = reinterpret_cast<Fu*>(hh);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    PF_REQUIRE(h && x_in && mem && out && x_in != out && B > 0 && B <= 65535, "fusion_forward: null/empty argument");
+    PF_REQUIRE(T >= 1 && T <= 12000 && L >= 1 && L <= 5000, "fusion_forward: 1 .. 12000 rows, 1 .. 5000 memory rows");
+    PF_REQUIRE(((uintptr_t)x_in & 15) == 0 && ((uintptr_t)mem & 15) == 0 && ((uintptr_t)out & 15) == 0, "fusion_forward: 16-B alignment");
+    std::vector<int32_t> xl(B, T), ml(B, L);               // NULL lengths: every row and every key
+    for (int b = 0; b < B; ++b) {
+        if (x_lens_host) xl[b] = x_lens_host[b];
+        if (mem_lens_host) ml[b] = mem_lens_host[b];
+        PF_REQUIRE(xl[b] >= 0 && xl[b] <= T && ml[b] >= 0 && ml[b] <= L, "fusion_forward: a length exceeds the padded length");
+    }
+    const LcbCfg& c = h->cfg;
+    const int D = c.d_model, FF = c.ffn_dim;
+    int rc;
+    if ((rc = h->tt.require_all("fusion"))) return rc;
+    if ((rc = h->rows(B, T, FF, xl.data(), s))) return rc;
+    if (h->kv.ensure(sizeof(float) * (size_t)B * L * 2 * D) || h->mlens.ensure(sizeof(int32_t) * B) ||
+        upload_h2d(h->mlens.p, ml.data(), sizeof(int32_t) * B, s))
+        return -2;
+    float *x = h->xa.as<float>(), *xn = h->xn.as<float>(), *q = h->qkv.as<float>(), *att = h->att.as<float>(), *hid = h->hid.as<float>(),
+          *kv = h->kv.as<float>();
+    // x1 = x + self_attn(norm1 x)
+    if ((rc = h->ln("norm1.", x_in, xn))) return rc;
+    const char* names[3] = {"self_attn.linear_q.", "self_attn.linear_k.", "self_attn.linear_v."};
+    for (int j = 0; j < 3; ++j)
+        if ((rc = h->lin(xn, D, names[j], D, nullptr, q + (size_t)j * D, 3 * D, 0))) return rc;
+    if ((rc = launch_tf_attention(q, h->klens.as<int>(), B, T, c.n_heads, att, s))) return rc;
+    if ((rc = h->lin(att, D, "self_attn.linear_out.", D, x_in, x, D, 0))) return rc;
+    // x2 = x1 + src_attn(norm2 x1, mem, mem): q [B T, D] into the q | k | v buffer (row stride D), K | V of the memory rows by two
+    // GEMMs with ldc = 2 D
+    float* x2 = h->xb.as<float>();
+    if ((rc = h->ln("norm2.", x, xn))) return rc;
+    if ((rc = h->lin(xn, D, "src_attn.linear_q.", D, nullptr, q, D, 0))) return rc;
+    if ((rc = h->gm(false, mem, B * L, D, "src_attn.linear_k.weight", h->tt.get("src_attn.linear_k.bias"), D, nullptr, kv, 2 * D, 0))) return rc;
+    if ((rc = h->gm(false, mem, B * L, D, "src_attn.linear_v.weight", h->tt.get("src_attn.linear_v.bias"), D, nullptr, kv + D, 2 * D, 0))) return rc;
+    if ((rc = launch_tf_cross_attention(q, D, kv, h->mlens.as<int>(), B, T, L, c.n_heads, att, s))) return rc;
+    if ((rc = h->lin(att, D, "src_attn.linear_out.", D, x, x2, D, 0))) return rc;
+    // out = (x +) x2 + ffn(norm3 x2): both addends ride in the last GEMM
+    if ((rc = h->ln("norm3.", x2, xn))) return rc;
+    if ((rc = h->lin(xn, D, "feed_forward.w_1.", FF, nullptr, hid, FF, 0))) return rc;
+    if ((rc = launch_cf_act(hid, (size_t)h->Mi * FF, 0, s))) return rc;
+    GemmArgs g{};
+    g.A = hid; g.lda = FF; g.W = h->tt.get("feed_forward.w_2.weight"); g.ldw = FF; g.bias = h->tt.get("feed_forward.w_2.bias");
+    g.R1 = x2; g.ldr1 = D; g.R2 = add_input ? x_in : nullptr; g.ldr2 = D; g.C = out; g.ldc = D; g.M = h->Mi; g.N = D; g.K = FF;
+    return launch_gemm_f32(g, s);
+}
+
 // single-kernel hooks (tests)
 int pf_k_fsmn_step(const float* t, const float* x, const float* g2, const float* b2, const float* w, const float* win_in, float* win_out,
                    const int32_t* parents_dev, int32_t pos, int32_t n, int32_t D, int32_t K, int32_t left_pad, const float* g3, const float* b3,
@@ -866,6 +1027,14 @@ int pf_k_tf_attention(const float* qkv, const int32_t* klens_dev, int32_t B, int
 }
 int pf_k_tf_embed_rows(const float* x, int32_t NE, const float* pe, int32_t B, int32_t T, int32_t D, float scale, float* y, void* stream) {
     return launch_cf_scale_rows(x, NE, y, B, T, D, scale, pe, reinterpret_cast<hipStream_t>(stream));
+}
+int pf_k_tf_cross_attention(const float* q, int32_t ldq, const float* kv, const int32_t* klens_dev, int32_t B, int32_t Tq, int32_t L, int32_t H,
+                            float* out, void* stream) {
+    return launch_tf_cross_attention(q, ldq, kv, klens_dev, B, Tq, L, H, out, reinterpret_cast<hipStream_t>(stream));
+}
+int pf_k_text_embed_rows(const float* table, const int32_t* ids_dev, const float* pe, int32_t B, int32_t L, int32_t D, float scale, float* y,
+                         void* stream) {
+    return launch_text_embed_rows(table, ids_dev, pe, scale, y, B, L, D, reinterpret_cast<hipStream_t>(stream));
 }
 int pf_k_conformer_glu_dw(const float* g,const float* dw, const float* dw_bias, const float* bn_scale, const float* bn_shift, int32_t B,
                           int32_t T, int32_t D, int32_t taps, float* y, void* stream) {

@@ -407,6 +407,49 @@ def transformer_state_dict(seed: int, model) -> Dict[str, torch.Tensor]:
     return conformer_state_dict(seed, model)
 
 
+def lcbnet_conf(output_size: int = 128, attention_heads: int = 2, linear_units: int = 256, enc_blocks: int = 2, dec_blocks: int = 2,
+                text_blocks: int = 2, vocab: int = 300, input_size: int = 80) -> dict:
+    """constructor arguments of an LCBNet model at a chosen size: transformer_conf plus the text encoder, the one fusion layer and the
+    bias predictor (funasr/models/lcbnet/model.py; every width is the audio encoder's). The default ids of a decode without text
+    need a vocabulary of at least 296 tokens."""
+    c = transformer_conf(output_size, attention_heads, linear_units, enc_blocks, dec_blocks, vocab, input_size)
+    c.update({
+        "text_encoder": "TransformerTextEncoder",
+        "text_encoder_conf": {"output_size": output_size, "attention_heads": attention_heads, "linear_units": linear_units,
+                              "num_blocks": text_blocks, "dropout_rate": 0.1, "positional_dropout_rate": 0.1, "attention_dropout_rate": 0.0},
+        "fusion_encoder": "FusionSANEncoder",
+        "fusion_encoder_conf": {"size": output_size, "attention_heads": attention_heads, "attention_dim": output_size,
+                                "linear_units": linear_units, "self_attention_dropout_rate": 0.0, "src_attention_dropout_rate": 0.0,
+                                "positional_dropout_rate": 0.1, "dropout_rate": 0.1},
+        "bias_predictor": "ConvBiasPredictor",
+        "bias_predictor_conf": {"size": output_size, "l_order": 3, "r_order": 3, "attention_heads": attention_heads,
+                                "attention_dropout_rate": 0.1, "linear_units": linear_units},
+        "select_num": 2, "select_length": 3, "insert_blank": True})
+    return c
+
+
+LCBNET_ZOO_LIKE = dict(output_size=256, attention_heads=4, linear_units=2048, enc_blocks=12, dec_blocks=6, text_blocks=6, vocab=5000)
+
+
+def lcbnet_state_dict(seed: int, model, ctc_gain: float = 0.5, blank_bias: float = 18.0, eos_bias: float = 12.0,
+                      fusion_gain: float = 1.5) -> Dict[str, torch.Tensor]:
+    """synthetic weights in the layout of `model` (an LCBNet module or the reference's), drawn like sanm_state_dict in the sorted order
+    of the keys, then made "trained-like" in the three places where plain random weights leave the joint search of a 300-token
+    vocabulary without a usable answer (no hypothesis ever ends on its own, every hypothesis runs to the frame count, and the CTC
+    prefix scores of such hypotheses are the infeasible -1e10):
+      * the CTC head is confident and mostly blank: its logits x `ctc_gain`, the blank's bias + `blank_bias`, as after training;
+      * the decoder keeps `eos` (= vocab - 1) among its candidates: the output layer's bias of that row + `eos_bias`, so that a
+        hypothesis can end where the CTC prefix score says the sequence is complete;
+      * the text matters: the output projection of the fusion layer's cross-attention x `fusion_gain`."""
+    sd = sanm_state_dict(seed, model)
+    V = sd["ctc.ctc_lo.weight"].shape[0]
+    sd["ctc.ctc_lo.weight"] = sd["ctc.ctc_lo.weight"] * ctc_gain
+    sd["ctc.ctc_lo.bias"][0] += blank_bias
+    sd["decoder.output_layer.bias"][V - 1] += eos_bias
+    sd["fusion_encoder.src_attn.linear_out.weight"] = sd["fusion_encoder.src_attn.linear_out.weight"] * fusion_gain
+    return sd
+
+
 def sanm_conf(output_size: int = 128, attention_heads: int = 2, linear_units: int = 64, enc_blocks: int = 2, dec_blocks: int = 3,
               att_layer_num: int = 2, kernel: int = 11, sanm_shfit="default", enc_kernel: int = 11, ctc_weight: float = 0.3, vocab: int = 60,
               input_size: int = 80) -> dict:

@@ -670,6 +670,54 @@ int pf_k_tf_attention(const float* qkv_dev, const int32_t* klens_dev, int32_t B,
 int pf_k_tf_embed_rows(const float* x_dev, int32_t NE, const float* pe_dev, int32_t B, int32_t T, int32_t D, float scale, float* y_dev,
                        void* stream);
 
+/* ---- LCB-Net (funasr/models/lcbnet: long-context biasing ASR, audio plus the OCR text of the slides). The audio side is pf_tfencoder /
+ * pf_tdecoder / pf_ctc; these two handles are the text side. Both run exact-fp32 GEMMs: the rows are few, run once per utterance, and no
+ * a-priori bound crosses the handles (the text encoder's output feeds the fusion layer's K / V projections).
+ *
+ * pf_textencoder: TransformerTextEncoder (lcbnet/encoder.py:130-241): Embedding x sqrt(D) + pe[t], pre-LayerNorm blocks of masked
+ * self-attention and a ReLU feed-forward (the block loop of pf_tfencoder behind another front), after_norm. Tensor names: the reference's
+ * keys below `text_encoder.` -- "embed.0.weight" [vocab, D], "encoders.<i>.self_attn.linear_{q,k,v,out}.{weight,bias}",
+ * "encoders.<i>.feed_forward.w_{1,2}.{weight,bias}", "encoders.<i>.norm{1,2}.{weight,bias}", "after_norm.{weight,bias}" -- plus
+ * "pos_table" [5000, D]. */
+typedef struct pf_textencoder pf_textencoder;
+typedef struct pf_textencoder_config {
+    int32_t vocab_size, d_model, n_heads, ffn_dim, n_blocks;
+    float ln_eps;
+} pf_textencoder_config;
+pf_textencoder* pf_textencoder_create(const pf_textencoder_config* cfg);
+void pf_textencoder_destroy(pf_textencoder* h);
+int pf_textencoder_set_tensor(pf_textencoder* h, const char* name, const float* data, int64_t numel);
+int pf_textencoder_missing(const pf_textencoder* h);
+/* ids_host [B, L] (every id in [0, vocab_size), checked here before any launch), lens_host [B] (keys at or past lens_host[b] are
+ * masked; every row is computed) -> out_dev [B, L, D]. Fails unless 1 <= L <= 5000. No sync. */
+int pf_textencoder_forward(pf_textencoder* h, const int32_t* ids_host, const int32_t* lens_host, int32_t B, int32_t L, float* out_dev,
+                           void* stream);
+
+/* pf_fusion: FusionSANEncoder = ONE SelfSrcAttention layer (lcbnet/encoder.py:244-370):
+ *   x += self_attn(norm1 x); x += src_attn(norm2 x, mem, mem); x += feed_forward(norm3 x)
+ * Tensor names: the reference's keys below `fusion_encoder.` ("self_attn.*", "src_attn.*", "feed_forward.w_{1,2}.*", "norm{1,2,3}.*"). */
+typedef struct pf_fusion pf_fusion;
+typedef struct pf_fusion_config {
+    int32_t d_model, n_heads, ffn_dim;
+    float ln_eps;
+} pf_fusion_config;
+pf_fusion* pf_fusion_create(const pf_fusion_config* cfg);
+void pf_fusion_destroy(pf_fusion* h);
+int pf_fusion_set_tensor(pf_fusion* h, const char* name, const float* data, int64_t numel);
+int pf_fusion_missing(const pf_fusion* h);
+/* x_dev [B, T, D], mem_dev [B, L, D] -> out_dev [B, T, D] (another buffer than x_dev). x_lens_host / mem_lens_host [B] or NULL: NULL
+ * means every row / every key (what the reference's inference passes: both masks None). add_input != 0: out = x + layer(x, mem), the
+ * model's `encoder_out + fusion_out`, the addend riding in the last GEMM. 1 <= T <= 12000, 1 <= L <= 5000. No sync. */
+int pf_fusion_forward(pf_fusion* h, const float* x_dev, const int32_t* x_lens_host, const float* mem_dev, const int32_t* mem_lens_host,
+                      int32_t B, int32_t T, int32_t L, int32_t add_input, float* out_dev, void* stream);
+/* single-kernel hooks (tests): the cross-attention of many queries over a second sequence (q_dev [B Tq, >= 64 H] rows ldq floats apart,
+ * kv_dev [B L, 128 H] K | V, klens_dev [B] -> out_dev [B Tq, 64 H]; keys >= klens_dev[b] masked, no row at or past them read) and
+ * the token rows y[b L + t] = table[ids[b L + t]] * scale + pe[t] (ids_dev inside the table: not checked on the device) */
+int pf_k_tf_cross_attention(const float* q_dev, int32_t ldq, const float* kv_dev, const int32_t* klens_dev, int32_t B, int32_t Tq, int32_t L,
+                            int32_t H, float* out_dev, void* stream);
+int pf_k_text_embed_rows(const float* table_dev, const int32_t* ids_dev, const float* pe_dev, int32_t B, int32_t L, int32_t D, float scale,
+                         float* y_dev, void* stream);
+
 /* ---- Transducer (RNN-T) search (funasr/models/transducer: RNNTDecoder + JointNetwork + BeamSearchTransducer.default_beam_search,
  * the one decoding path the reference's Transducer builds: one utterance, is_final, no LM, no length normalisation). One handle
  * holds the prediction network (embedding, n_layers LSTM cells) and the joint network; the search loop runs on the host side of the
