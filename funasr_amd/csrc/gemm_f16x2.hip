@@ -1,7 +1,7 @@
 // fp32-accurate GEMM on the fp16 matrix cores with THREE products per result instead of the six of gemm_split3.hip:
 // C = epilogue(A[M,K] * W[N,K]^T) with both operands held as TWO fp16 planes of the pre-scaled tensor
 //     x * 2^e = hi + lo,   hi = f16(x * 2^e),  lo = f16(x * 2^e - hi)        (11 + 11 significand bits + lo's sign)
-// and v_mfma_f32_32x32x16_f16 products  hi*hi + hi*lo + lo*hi  into ONE fp32 accumulator (each f16 x f16 product is
+// and v_mfma_f32_16x16x32_f16 products  hi*hi + hi*lo + lo*hi  into ONE fp32 accumulator (each f16 x f16 product is
 // exact in fp32). What is dropped or rounded away is <= 2^-24 |a||w| per term (lo*lo, and lo's own rounding): the size
 // of fp32's product rounding, like the terms gemm_split3.hip drops. fp16 has 5 exponent bits, so the planes carry a
 // per-tensor power-of-two scale 2^e chosen from an a-priori bound (weights: max |w| at load; activations: the LayerNorm
@@ -12,10 +12,16 @@
 //
 // Design (gfx950): as gemm_split3.hip -- 8 waves in a 4 x 2 grid, 32-deep K stages of 64-B LDS rows moved HBM -> LDS by
 // asm-issued global_load_lds_dwordx4 pieces (double buffered, one piece per group of MFMAs), chunk swizzle
-// c ^ ((r >> 2) & 3), XCD-aware block order, LDS-slab float4 epilogue -- in two block shapes:
-//   256 x 128 (wave = 2 x 2 MFMA tiles):  8 ds_read_b128 + 12 MFMA per 16-deep step, 48-KB stages
-//   256 x 256 (wave = 2 x 4 MFMA tiles): 12 ds_read_b128 + 24 MFMA per 16-deep step, 64-KB stages, 2/3 of the L2 -> LDS
-//                                         bytes per flop: the shape for N >= 1024
+// c ^ (-(r >> 2) & 3), XCD-aware block order, LDS-slab float4 epilogue -- in two block shapes:
+//   256 x 128 (wave = 64 x  64 = 4 x 4 tiles of 16 x 16): 16 ds_read_b128 + 48 MFMA per 32-deep stage, 48-KB stages
+//   256 x 256 (wave = 64 x 128 = 4 x 8 tiles of 16 x 16): 24 ds_read_b128 + 96 MFMA per 32-deep stage, 64-KB stages, 2/3 of the
+//                                         L2 -> LDS bytes per flop: the shape for N >= 1024
+// The instruction is the 16x16x32 shape because the K loops run at the part's power wall and that wall moves with the MFMA shape:
+// the register-resident three-product chain sustains 1.17 x the FLOP/s on 16x16x32 that it does on 32x32x16 (higher held clock at
+// the same power; tools/bench_mfma_shape.py, profiles/r07a_mfma_shape_probe.jsonl). One 16x16x32 gives the bits of two
+// chained 32x32x16; the k ORDER changed with it (per accumulator and 32-deep stage lo*hi, hi*lo, hi*hi each over 32 k; before: the
+// three products per 16 k), so all shapes of the product switched together. The 16-deep measurement shapes (tiles 5 / 6) keep the
+// old instruction and order and are no longer bit-equal to the rest.
 #include "common.h"
 #include <cstdlib>
 #include <type_traits>
@@ -74,7 +80,8 @@ __device__ __forceinline__ void gemm2_tile_body(Gemm2Args& p, const int m0, cons
     const unsigned short* src[PPW];
     {
         const int prow = lane / CPR;
-        const int chunk = (lane % CPR) ^ ((prow >> G::SWZ) & (CPR - 1));
+        // (32-deep stages: the swizzle of the 16x16x32 fragment read, see the K loop)
+        const int chunk = (lane % CPR) ^ ((KS == 32 ? 0 - (prow >> 2) : (prow >> G::SWZ)) & (CPR - 1));
 #pragma unroll
         for (int i = 0; i < PPW; ++i) {
             const int q = wave + G::NW * i;
@@ -100,13 +107,16 @@ __device__ __forceinline__ void gemm2_tile_body(Gemm2Args& p, const int m0, cons
         glds16(src[i] + kt * (i < G::A_PIECES / G::NW ? a_step : w_step), lds0 + (unsigned)buf * STAGE_B + (unsigned)i * (G::NW * 1024));
     };
 
-    floatx16 acc[WM][WN];
+    // 32-deep stages: floatx4 tiles of the 16x16x32 MFMA; the 16-deep measurement shapes stay on 32x32x16
+    constexpr bool S16 = KS_ == 32;
+    constexpr int AM = S16 ? 2 * WM : WM, AN = S16 ? 2 * WN : WN, AR = S16 ? 4 : 16;
+    typename std::conditional<S16, floatx4, floatx16>::type acc[AM][AN];
 #pragma unroll
-    for (int i = 0; i < WM; ++i)
+    for (int i = 0; i < AM; ++i)
 #pragma unroll
-        for (int jj = 0; jj < WN; ++jj)
+        for (int jj = 0; jj < AN; ++jj)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][jj][r] = 0.f;
+            for (int r = 0; r < AR; ++r) acc[i][jj][r] = 0.f;
 
     const int f = (idx >> G::SWZ) & (CPR - 1);
     const int aoff = (wr * (WM * 32) + idx) * ROWB;
@@ -255,6 +265,22 @@ __device__ __forceinline__ void gemm2_tile_body(Gemm2Args& p, const int m0, cons
 #undef PF_PROD16
         }
     } else {
+    // 32-deep stages on v_mfma_f32_16x16x32_f16: one instruction takes a stage's whole depth. Operand lane map: lane l holds row
+    // l & 15 of a 16-row tile, k = 8 (l >> 4) .. + 7 = logical 16-B chunk l >> 4 of the 64-B LDS row.
+    // A stage is consumed in column pairs (NPH phases): the A fragments of the stage (2 WM tiles x 2 planes) stay in registers,
+    // every phase reads two 16-column W tiles x 2 planes -- (2 WM + 2) x 2 fragments alive, what one 16-deep step of the 32x32
+    // form held for WN = 4 -- and issues lo*hi, hi*lo, hi*hi on its 2 WM x 2 accumulators (consecutive MFMAs write different
+    // accumulators). Per accumulator and stage: lo*hi, hi*lo, hi*hi, each over the stage's 32 k, stages in ascending k.
+    static_assert(CPR == 4 && G::SWZ == 2, "64-B LDS rows");
+    constexpr int NPH = WN, NG = 3 * NPH;
+    const int q16 = lane >> 4, l16 = lane & 15;
+    // Chunk swizzle for the 16x16x32 fragment read: ds_read_b128 is served in four NON-contiguous 16-lane groups ({0-3, 12-15, 20-27},
+    // {4-11, 16-19, 28-31}, ...), so a group holds rows 0-3 and 12-15 at logical chunk a and rows 4-11 at chunk a ^ 1; physical chunk
+    // c ^ ((-(row >> 2)) & 3) puts the four rows of one (row & 3) on a, a ^ 2, a ^ 3, a ^ 1: sixteen different 16-B slots of the 256-B bank
+    // row (the 32x32 form's c ^ ((row >> 2) & 3) is 2-way here). The DMA source address applies the same permutation.
+    const int coff16 = (q16 ^ ((0 - (l16 >> 2)) & 3)) * 16;
+    const int aoff16 = (wr * (WM * 32) + l16) * ROWB + coff16;
+    const int boff16 = 2 * A_PLANE_B + (wc * (WN * 32) + l16) * ROWB + coff16;
 #pragma unroll
     for (int i = 0; i < PPW; ++i) piece(i, 0, 0);
     for (int kt = 0; kt < nk; ++kt) {
@@ -263,54 +289,37 @@ __device__ __forceinline__ void gemm2_tile_body(Gemm2Args& p, const int m0, cons
         const bool nxt = kt + 1 < nk;
         const int nb = (kt + 1) & 1;
         const unsigned char* sb = smem + (kt & 1) * STAGE_B;
-#define PF_PIECE(I) do { if ((I) < PPW && nxt) piece((I) < PPW ? (I) : 0, nb, kt + 1); } while (0)
-#define PF_PROD(PA, PB)                                                                                               \
-    _Pragma("unroll") for (int i = 0; i < WM; ++i) _Pragma("unroll") for (int jj = 0; jj < WN; ++jj)                  \
-        acc[i][jj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][PA], b[jj][PB], acc[i][jj], 0, 0, 0)
-#define PF_LOAD(S)                                                                                                    \
-    _Pragma("unroll") for (int pl = 0; pl < 2; ++pl) {                                                                \
-        _Pragma("unroll") for (int i = 0; i < WM; ++i)                                                                \
-            a[i][pl] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(sb + pl * A_PLANE_B + aoff + i * 32 * ROWB + coff[S]));   \
-        _Pragma("unroll") for (int jj = 0; jj < WN; ++jj)                                                             \
-            b[jj][pl] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(sb + pl * B_PLANE_B + boff + jj * 32 * ROWB + coff[S])); \
-    }
-        if constexpr (SCHED == 0 || SCHED == 3) {
-            f16x8 a[WM][2], b[WN][2];
-            // the two small products first, hi*hi last (fixed order: results do not depend on the block shape's schedule)
-            PF_LOAD(0)
-            PF_PROD(1, 0); PF_PIECE(0); PF_PIECE(1);
-            PF_PROD(0, 1); PF_PIECE(2); PF_PIECE(3);
-            PF_PROD(0, 0); PF_PIECE(4);
-            PF_LOAD(1)
-            PF_PROD(1, 0); PF_PIECE(5); PF_PIECE(6);
-            PF_PROD(0, 1); PF_PIECE(7);
-            PF_PROD(0, 0);
-        } else {
-            // both k-steps' fragments are requested before the first MFMA: one LDS-latency bubble per stage instead of two
-            f16x8 a[WM][2], b[WN][2], a1[WM][2], b1[WN][2];
-            PF_LOAD(0)
-            {
-#define a a1
-#define b b1
-                PF_LOAD(1)
-#undef a
-#undef b
+        f16x8 a[2 * WM][2];
+#pragma unroll
+        for (int pl = 1; pl >= 0; --pl)            // the lo plane first: the first product is lo * hi
+#pragma unroll
+            for (int i = 0; i < 2 * WM; ++i)
+                a[i][pl] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(sb + pl * A_PLANE_B + aoff16 + i * 16 * ROWB));
+#pragma unroll
+        for (int ph = 0; ph < NPH; ++ph) {
+            f16x8 b[2][2];
+#pragma unroll
+            for (int pl = 0; pl < 2; ++pl)
+#pragma unroll
+                for (int jj = 0; jj < 2; ++jj)
+                    b[jj][pl] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(sb + pl * B_PLANE_B + boff16 + (2 * ph + jj) * 16 * ROWB));
+#pragma unroll
+            for (int pr = 0; pr < 3; ++pr) {       // the two small products first, hi*hi last (fixed order in every shape)
+                const int PA = pr == 0 ? 1 : 0, PB = pr == 1 ? 1 : 0;
+#pragma unroll
+                for (int i = 0; i < 2 * WM; ++i)
+#pragma unroll
+                    for (int jj = 0; jj < 2; ++jj)
+                        acc[i][2 * ph + jj] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i][PA], b[jj][PB], acc[i][2 * ph + jj], 0, 0, 0);
+                // the next stage's DMA pieces, spread over the gaps between the product groups (none behind the last)
+                const int g = 3 * ph + pr;
+                if (g < NG - 1 && nxt) {
+#pragma unroll
+                    for (int i = 0; i < PPW; ++i)
+                        if (i >= g * PPW / (NG - 1) && i < (g + 1) * PPW / (NG - 1)) piece(i, nb, kt + 1);
+                }
             }
-            if constexpr (SCHED == 2) { PF_PIECE(0); PF_PIECE(1); PF_PIECE(2); PF_PIECE(3); }
-            PF_PROD(1, 0); if constexpr (SCHED == 1) { PF_PIECE(0); PF_PIECE(1); } else { PF_PIECE(4); PF_PIECE(5); }
-            PF_PROD(0, 1); if constexpr (SCHED == 1) { PF_PIECE(2); PF_PIECE(3); } else { PF_PIECE(6); PF_PIECE(7); }
-            PF_PROD(0, 0); if constexpr (SCHED == 1) { PF_PIECE(4); }
-#define a a1
-#define b b1
-            PF_PROD(1, 0); if constexpr (SCHED == 1) { PF_PIECE(5); PF_PIECE(6); }
-            PF_PROD(0, 1); if constexpr (SCHED == 1) { PF_PIECE(7); }
-            PF_PROD(0, 0);
-#undef a
-#undef b
         }
-#undef PF_PROD
-#undef PF_LOAD
-#undef PF_PIECE
     }
     }
 
@@ -596,6 +605,10 @@ int launch_rowl1_bound(const float* W, int rows, int cols, int ld, const float* 
 // audio-s/s; the headline shape (768 blocks = 3 whole rounds) is left alone (50.59 / 50.68 ms with the form forced on). Same bits either
 // way. PF_QKV_PS=0 / 1 (environment) forces never / always for A/B runs.
 static bool qkv_form_prefers_ps(const Gemm2Args& a) {
+#if !defined(PF_MEASUREMENT_KERNELS)
+    (void)a;
+    return false;                               // (the persistent shape is not on the 16x16x32 MFMA: see launch_gemm_f16x2)
+#endif
     static const int mode = [] { const char* e = getenv("PF_QKV_PS"); return e ? atoi(e) : 2; }();
     if (mode == 0 || !gemm_f16x2_ps_ok(a)) return false;
     if (mode == 1) return true;
@@ -664,8 +677,13 @@ int launch_gemm_f16x2(const Gemm2Args& a, hipStream_t stream) {
     }
     // the four-wave 256 x 256 shape (gemm_f16x2_w4.hip): tile 7; bits 4.. = its measurement builds
     // the persistent wave-specialised shape (gemm_f16x2_ps.hip): tile 10; shapes it does not take are chosen by shape instead
+    // The persistent shape (gemm_f16x2_ps.hip) still issues v_mfma_f32_32x32x16_f16 with the three products per 16 k, which is not
+    // the bits of the 16x16x32 loops: no id of the product reaches it -- tile 10 is chosen by shape among the converted
+    // kernels. The measurement library keeps it reachable under its ids (not bit-equal to the rest there).
     if ((a.tile & 15) == 10 || (a.tile & 15) == 12) {         // 10: the persistent shape; 12: its finisher form (measurement library only)
+#if defined(PF_MEASUREMENT_KERNELS)
         if (gemm_f16x2_ps_ok(a)) return launch_gemm_f16x2_ps(a, stream);
+#endif
         Gemm2Args b = a;
         b.tile = 0;
         return launch_gemm_f16x2(b, stream);

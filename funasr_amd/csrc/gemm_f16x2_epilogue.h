@@ -1,5 +1,7 @@
-// Epilogue of the f16x2 tile GEMMs (gemm_f16x2.hip, gemm_f16x2_w4.hip): one wave's WM x WN accumulator tiles of 32 x 32 ->
-// fp32 rows / two fp16 planes / the QKV form / the fused row arg-max. Shared so that every block shape evaluates exactly the
+// Epilogue of the f16x2 tile GEMMs (gemm_f16x2.hip, gemm_f16x2_w4.hip): one wave's WM x WN accumulator tiles of 32 x 32 --
+// held either as floatx16 [WM][WN] in the C/D layout of the 32x32x16 MFMA or as floatx4 [2 WM][2 WN] in the C/D layout of the
+// 16x16x32 MFMA (col = lane & 15, row = 4 (lane >> 4) + r); only the slab writes and the arg-max form read that layout --
+// -> fp32 rows / two fp16 planes / the QKV form / the fused row arg-max. Shared so that every block shape evaluates exactly the
 // same expressions in the same order per output element (the shapes are bitwise equal, tested). The code was the tail of
 // gemm_f16x2_kernel until round 5 and is unchanged.
 //   NW   waves per workgroup (each owns a 32 x ELD float slab at `smem`)
@@ -9,25 +11,68 @@
 
 namespace pf {
 
-template <int WM, int WN, int NW, int MODE, int OUT, int ABL>
-__device__ __forceinline__ void gemm2_epilogue(const Gemm2Args& p, floatx16 (&acc)[WM][WN], unsigned char* smem, int m0, int n0, int nblk,
+template <int WM, int WN, int NW, int MODE, int OUT, int ABL, typename AT, int AM, int AN>
+__device__ __forceinline__ void gemm2_epilogue(const Gemm2Args& p, AT (&acc)[AM][AN], unsigned char* smem, int m0, int n0, int nblk,
                                                int wave, int wr, int wc, int lane) {
+    constexpr bool S16 = AM == 2 * WM;       // accumulators of the 16x16x32 MFMA
+    static_assert((S16 && AN == 2 * WN && sizeof(AT) == 16) || (!S16 && AM == WM && AN == WN && sizeof(AT) == 64), "accumulator tiles");
+    constexpr int AR = S16 ? 4 : 16;
     const int hh = lane >> 5, idx = lane & 31;
+    const int q16 = lane >> 4, l16 = lane & 15;
     constexpr int ELD_ = WN * 32 + 4;
     // ---- epilogue (C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)):
     //      through a wave-private LDS slab so that every global access is a 16-B piece of a contiguous row segment
     if constexpr (ABL == 2) {
         float t = 0.f;
 #pragma unroll
-        for (int i = 0; i < WM; ++i)
+        for (int i = 0; i < AM; ++i)
 #pragma unroll
-            for (int jj = 0; jj < WN; ++jj)
+            for (int jj = 0; jj < AN; ++jj)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) t += acc[i][jj][r];
+                for (int r = 0; r < AR; ++r) t += acc[i][jj][r];
         if (t == 123.456f) p.C[0] = t;
         return;
     }
-    if constexpr (OUT == 3) {
+    if constexpr (OUT == 3 && S16) {
+        // fused row arg-max over this wave's WN * 32 columns, straight from the accumulators (C/D layout of the 16x16 tile: col =
+        // lane & 15, row = 4 (lane >> 4) + r); ties go to the lowest column like torch.argmax
+        const float osc = p.oscale_dev ? p.oscale * *p.oscale_dev : p.oscale;
+        float bv[AN];
+#pragma unroll
+        for (int jj = 0; jj < AN; ++jj) {
+            const int col = n0 + wc * (WN * 32) + jj * 16 + l16;
+            bv[jj] = (p.bias && col < p.N) ? p.bias[col] : 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < AM; ++i) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = m0 + wr * (WM * 32) + i * 16 + 4 * q16 + r;
+                float best = -INFINITY;
+                int besti = 0x7fffffff;
+#pragma unroll
+                for (int jj = 0; jj < AN; ++jj) {
+                    const int col = n0 + wc * (WN * 32) + jj * 16 + l16;
+                    if (col < p.N) {
+                        const float v = acc[i][jj][r] * osc + bv[jj];
+                        if (v > best) { best = v; besti = col; }
+                    }
+                }
+#pragma unroll
+                for (int o = 8; o > 0; o >>= 1) {   // stays inside the 16-lane group (same row)
+                    const float ov = __shfl_xor(best, o, 64);
+                    const int oi = __shfl_xor(besti, o, 64);
+                    if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
+                }
+                if (l16 == 0 && row < p.M) {
+                    const size_t o = (size_t)row * p.amax_ld + 2 * nblk + wc;
+                    p.amax_val[o] = best;
+                    p.amax_idx[o] = besti;
+                }
+            }
+        }
+        return;
+    } else if constexpr (OUT == 3) {
         // fused row arg-max over this wave's WN * 32 columns, straight from the accumulators (C/D layout: col = lane & 31,
         // row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)); ties go to the lowest column like torch.argmax
         const float osc = p.oscale_dev ? p.oscale * *p.oscale_dev : p.oscale;
@@ -74,6 +119,8 @@ __device__ __forceinline__ void gemm2_epilogue(const Gemm2Args& p, floatx16 (&ac
     constexpr int NPASS = 32 / RPS;
     __syncthreads();
     float* slab = reinterpret_cast<float*>(smem) + wave * (32 * ELD);
+    int sw16 = 4 * q16 * ELD + l16;              // this lane's first slab word in the 16 x 16 layout
+    asm volatile("" : "+v"(sw16));               // (one base register, constant offsets behind it)
     const int c4 = lane % LPR, rsub = lane / LPR;
     const int col = n0 + wc * (WN * 32) + c4 * 4;
     const bool colok = col + 3 < p.N;
@@ -84,11 +131,21 @@ __device__ __forceinline__ void gemm2_epilogue(const Gemm2Args& p, floatx16 (&ac
     if (p.bias && colok) bias4 = *reinterpret_cast<const float4*>(p.bias + col);
 #pragma unroll
     for (int i = 0; i < WM; ++i) {
+        if constexpr (S16) {
 #pragma unroll
-        for (int jj = 0; jj < WN; ++jj)
+            for (int si = 0; si < 2; ++si)
 #pragma unroll
-            for (int r = 0; r < 16; ++r)
-                slab[((r & 3) + 8 * (r >> 2) + 4 * hh) * ELD + jj * 32 + idx] = acc[i][jj][r];
+                for (int jj = 0; jj < AN; ++jj)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        slab[sw16 + (si * 16 + r) * ELD + jj * 16] = acc[2 * i + si][jj][r];
+        } else {
+#pragma unroll
+            for (int jj = 0; jj < WN; ++jj)
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    slab[((r & 3) + 8 * (r >> 2) + 4 * hh) * ELD + jj * 32 + idx] = acc[i][jj][r];
+        }
         const int row0 = m0 + wr * (WM * 32) + i * 32 + rsub;
         if (!colok) continue;
         // QKV form: this block's 256 columns lie inside one of q | k | v (qkv_D % 256 == 0)

@@ -25,6 +25,10 @@
 //   * ONE s_barrier per stage for all eight waves, in the middle of the stage (it publishes stage g + 1 and frees buffer g % 3).
 // Price: 256 x 128 tiles move 1.5x the L2 -> LDS bytes per flop of a 256 x 256 tile, and a wave's 64 x 128 quadrant needs 12
 // ds_read_b128 per 24 MFMAs (the eight-wave shape's ratio), placed by hand one per two MFMAs like gemm_f16x2_w4.hip.
+//
+// MEASUREMENT LIBRARY ONLY since the other shapes moved to v_mfma_f32_16x16x32_f16: this kernel's epilogue is tied to the
+// 32 x 32 C/D layout (v_permlane32_swap) and its loop keeps the three products per 16 k, which is no longer the k order -- and so not
+// the bits -- of the product's shapes. Tile 10 of the product is chosen by shape among the converted kernels.
 #include "common.h"
 
 namespace pf {

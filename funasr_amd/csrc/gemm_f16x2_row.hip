@@ -17,10 +17,11 @@
 // statistics are summed in layernorm_kernel's order (common.h ln_*: 4-column chunks, chunk l + chunk l + 64, xor butterfly
 // 32, 16 .. 1 over l). The fused result is therefore BITWISE the result of gemm_f16x2 followed by layernorm_kernel (tested).
 //
-// Design (gfx950): 8 waves as 2 (M) x 4 (N), a wave owns 64 x 128 = 2 x 4 MFMA tiles of 32 x 32 (the per-wave shape of the
-// 256 x 256 kernel: 12 ds_read_b128 + 24 v_mfma_f32_32x32x16_f16 per 16-deep step); 32-deep K stages of 64-B LDS rows --
+// Design (gfx950): 8 waves as 2 (M) x 4 (N), a wave owns 64 x 128 = 4 x 8 MFMA tiles of 16 x 16 (the per-wave shape of the
+// 256 x 256 kernel: 24 ds_read_b128 + 96 v_mfma_f32_16x16x32_f16 per 32-deep stage, consumed in four column pairs so that no more
+// fragments are alive than a 16-deep step of the 32x32x16 form held); 32-deep K stages of 64-B LDS rows --
 // 2 planes x (128 + 512) rows = 80 KB per stage, double buffered = all 160 KB of LDS, one workgroup per CU -- moved
-// HBM / L2 -> LDS by asm-issued global_load_lds_dwordx4 pieces (10 per wave and stage), chunk swizzle c ^ ((row >> 2) & 3) on
+// HBM / L2 -> LDS by asm-issued global_load_lds_dwordx4 pieces (10 per wave and stage), chunk swizzle c ^ (-(row >> 2) & 3) on
 // the DMA source address and on the read. Epilogue: accumulators -> wave-private LDS slab -> row-major float4 pieces kept in
 // registers (64 x 128 per wave = 128 VGPRs), statistics exchanged through LDS in three rounds, 16-B plane stores.
 #include "common.h"
@@ -54,7 +55,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f16x2_row_kernel(GemmRowArgs p) {
     const unsigned short* src[RW_PPW];
     {
         const int prow = lane >> 2;
-        const int chunk = (lane & 3) ^ ((prow >> 2) & 3);
+        const int chunk = (lane & 3) ^ ((0 - (prow >> 2)) & 3);       // the swizzle of the 16x16x32 fragment read (gemm_f16x2.hip)
         int row = m0 + wave * 16 + prow;
         row = row < p.M ? row : p.M - 1;
         src[0] = p.A + (size_t)row * p.lda + chunk * 8;
@@ -73,20 +74,20 @@ __global__ __launch_bounds__(512, 2) void gemm_f16x2_row_kernel(GemmRowArgs p) {
         else glds16(src[i] + kt * RW_KS, dst);
     };
 
-    floatx16 acc[WM][WN];
+    floatx4 acc[2 * WM][2 * WN];                 // 16 x 16 tiles of v_mfma_f32_16x16x32_f16
 #pragma unroll
-    for (int i = 0; i < WM; ++i)
+    for (int i = 0; i < 2 * WM; ++i)
 #pragma unroll
-        for (int jj = 0; jj < WN; ++jj)
+        for (int jj = 0; jj < 2 * WN; ++jj)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][jj][r] = 0.f;
+            for (int r = 0; r < 4; ++r) acc[i][jj][r] = 0.f;
 
-    const int f = (idx >> 2) & 3;
-    const int aoff = (wr * 64 + idx) * RW_ROWB;
-    const int boff = 2 * RW_A_PLANE_B + (wc * 128 + idx) * RW_ROWB;
-    int coff[2];
-#pragma unroll
-    for (int st = 0; st < 2; ++st) coff[st] = ((2 * st + hh) ^ f) * 16;
+    // operand lane map of the 16x16x32 MFMA: lane l holds row l & 15 of a 16-row tile, k = 8 (l >> 4) .. + 7 = logical chunk l >> 4
+    // of the 64-B LDS row, physical chunk c ^ (-(row >> 2) & 3) (conflict-free for the four lane groups of ds_read_b128: gemm_f16x2.hip)
+    const int q16 = lane >> 4, l16 = lane & 15;
+    const int coff16 = (q16 ^ ((0 - (l16 >> 2)) & 3)) * 16;
+    const int aoff = (wr * 64 + l16) * RW_ROWB + coff16;
+    const int boff = 2 * RW_A_PLANE_B + (wc * 128 + l16) * RW_ROWB + coff16;
 
 #if defined(PF_MEASUREMENT_KERNELS)
     const int nk = (p.a_nt & 128) ? 0 : p.K / RW_KS;                      // bit 7: no K loop (the epilogue alone)
@@ -146,45 +147,36 @@ __global__ __launch_bounds__(512, 2) void gemm_f16x2_row_kernel(GemmRowArgs p) {
 #else
         constexpr bool early = false;
 #endif
-#define RW_PIECE(I) do { if (nxt && !early) piece(I, nb, kt + 1); } while (0)
-#define RW_PROD(AF, BF, PA, PB)                                                                                       \
-    _Pragma("unroll") for (int i = 0; i < WM; ++i) _Pragma("unroll") for (int jj = 0; jj < WN; ++jj)                  \
-        acc[i][jj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AF[i][PA], BF[jj][PB], acc[i][jj], 0, 0, 0)
-#define RW_LOAD(AF, BF, S)                                                                                            \
-    _Pragma("unroll") for (int pl = 0; pl < 2; ++pl) {                                                                \
-        _Pragma("unroll") for (int i = 0; i < WM; ++i)                                                                \
-            AF[i][pl] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(sb + pl * RW_A_PLANE_B + aoff + i * 32 * RW_ROWB + coff[S]));   \
-        _Pragma("unroll") for (int jj = 0; jj < WN; ++jj)                                                             \
-            BF[jj][pl] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(sb + pl * RW_B_PLANE_B + boff + jj * 32 * RW_ROWB + coff[S])); \
-    }
-        // both k-steps' fragments are requested before the first MFMA (one LDS-latency bubble per stage), the next stage's
-        // DMA pieces early; per k-step the two small products first, hi * hi last: the order of gemm_f16x2_kernel
-        f16x8 a0[WM][2], b0[WN][2], a1[WM][2], b1[WN][2];
-        if constexpr (SCHED == 2) {
-            RW_LOAD(a0, b0, 0)
-            RW_LOAD(a1, b1, 1)
-            RW_PIECE(0); RW_PIECE(1); RW_PIECE(2); RW_PIECE(3);
-            RW_PROD(a0, b0, 1, 0); RW_PIECE(4); RW_PIECE(5);
-            RW_PROD(a0, b0, 0, 1); RW_PIECE(6); RW_PIECE(7);
-            RW_PROD(a0, b0, 0, 0); RW_PIECE(8); RW_PIECE(9);
-            RW_PROD(a1, b1, 1, 0);
-            RW_PROD(a1, b1, 0, 1);
-            RW_PROD(a1, b1, 0, 0);
-        } else {
-            // the plain order (round 5: what the wide tile GEMM now runs, profiles/r05s): a k-step's fragments, its products with
-            // the next stage's pieces between them, then the next k-step's fragments
-            RW_LOAD(a0, b0, 0)
-            RW_PROD(a0, b0, 1, 0); RW_PIECE(0); RW_PIECE(1); RW_PIECE(2);
-            RW_PROD(a0, b0, 0, 1); RW_PIECE(3); RW_PIECE(4); RW_PIECE(5);
-            RW_PROD(a0, b0, 0, 0); RW_PIECE(6); RW_PIECE(7);
-            RW_LOAD(a1, b1, 1)
-            RW_PROD(a1, b1, 1, 0); RW_PIECE(8); RW_PIECE(9);
-            RW_PROD(a1, b1, 0, 1);
-            RW_PROD(a1, b1, 0, 0);
+        // The stage's A fragments (4 row tiles x 2 planes) stay in registers; the stage is consumed in four column pairs, each
+        // reading two 16-column W tiles x 2 planes (12 fragments alive, as in a 16-deep step of the 32x32 form) and issuing
+        // lo*hi, hi*lo, hi*hi on its 4 x 2 accumulators; the next stage's DMA pieces go between the product groups. Per
+        // accumulator and stage: lo*hi, hi*lo, hi*hi over the stage's 32 k -- the order of gemm_f16x2_kernel.
+        f16x8 a[2 * WM][2];
+#pragma unroll
+        for (int pl = 1; pl >= 0; --pl)
+#pragma unroll
+            for (int i = 0; i < 2 * WM; ++i)
+                a[i][pl] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(sb + pl * RW_A_PLANE_B + aoff + i * 16 * RW_ROWB));
+#pragma unroll
+        for (int ph = 0; ph < WN; ++ph) {
+            f16x8 b[2][2];
+#pragma unroll
+            for (int pl = 0; pl < 2; ++pl)
+#pragma unroll
+                for (int jj = 0; jj < 2; ++jj)
+                    b[jj][pl] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(sb + pl * RW_B_PLANE_B + boff + (2 * ph + jj) * 16 * RW_ROWB));
+#pragma unroll
+            for (int pr = 0; pr < 3; ++pr) {
+                const int PA = pr == 0 ? 1 : 0, PB = pr == 1 ? 1 : 0;
+#pragma unroll
+                for (int i = 0; i < 2 * WM; ++i)
+#pragma unroll
+                    for (int jj = 0; jj < 2; ++jj)
+                        acc[i][2 * ph + jj] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i][PA], b[jj][PB], acc[i][2 * ph + jj], 0, 0, 0);
+                const int g = 3 * ph + pr;             // 12 product groups, the 10 pieces behind the first ten
+                if (g < RW_PPW && nxt && !early) piece(g, nb, kt + 1);
+            }
         }
-#undef RW_PROD
-#undef RW_LOAD
-#undef RW_PIECE
     }
 #if defined(PF_MEASUREMENT_KERNELS)
     if (p.a_nt & 256) {                                    // bit 8: the K loop alone (one store so that the accumulators stay live)
@@ -194,7 +186,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f16x2_row_kernel(GemmRowArgs p) {
 #pragma unroll
             for (int jj = 0; jj < WN; ++jj)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) sacc += acc[i][jj][r];
+                for (int r = 0; r < 16; ++r) sacc += acc[2 * i + (r >> 3)][2 * jj + ((r >> 2) & 1)][r & 3];
         if (sacc == 12345.678f && p.C) p.C[tid] = sacc;
         return;
     }

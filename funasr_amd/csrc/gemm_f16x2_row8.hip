@@ -7,8 +7,9 @@
 //     LayerNorm                                                       funasr/models/transformer/layer_norm.py:13-38
 //     fsmn_memory = mask (conv_k11(pad(mask v)) + mask v)             funasr/models/sanm/attention.py:216-239
 //
-// Design (gfx950): 8 waves as 1 (M) x 8 (N): a wave owns ALL 32 WM rows x 64 columns = WM x 2 MFMA tiles of 32 x 32 (WM = 4:
-// 12 ds_read_b128 + 24 MFMAs per 16-deep step like the 2 x 4 grid; WM = 3: 10 + 18), 32-deep K stages of 64-B LDS rows --
+// Design (gfx950): 8 waves as 1 (M) x 8 (N): a wave owns ALL 32 WM rows x 64 columns = 2 WM x 4 MFMA tiles of 16 x 16 on
+// v_mfma_f32_16x16x32_f16 (WM = 4: 24 ds_read_b128 + 96 MFMAs per 32-deep stage like the 2 x 4 grid; WM = 3: 20 + 72), 32-deep K
+// stages of 64-B LDS rows --
 // 2 planes x (32 WM + 512) rows, double buffered (WM = 3: 152 KB) -- by asm-issued global_load_lds_dwordx4 pieces (the A
 // planes are 4 WM pieces: waves 0 .. 4 WM - 9 carry two of them). Epilogue: per 32-row tile the waves 2 c, 2 c + 1 put their
 // 32 x 64 halves side by side in one LDS slab (columns 128 c ..), then wave 2 c + q finishes rows 16 q .. 16 q + 15 of the tile
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f16x2_row8_kernel(GemmRowArgs p) 
     const unsigned short* src_w[8];
     {
         const int prow = lane >> 2;
-        const int chunk = (lane & 3) ^ ((prow >> 2) & 3);
+        const int chunk = (lane & 3) ^ ((0 - (prow >> 2)) & 3);       // the swizzle of the 16x16x32 fragment read (gemm_f16x2.hip)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int a = (wave + 8 * j) < NA ? wave + 8 * j : wave;
@@ -91,20 +92,20 @@ __global__ __launch_bounds__(512, 2) void gemm_f16x2_row8_kernel(GemmRowArgs p) 
         glds16(src_w[j] + kt * R8_KS, lds0 + (unsigned)buf * STAGE_B + 2 * A_PLANE_B + (unsigned)(wave + 8 * j) * 1024);
     };
 
-    floatx16 acc[WM][2];
+    floatx4 acc[2 * WM][4];                      // 16 x 16 tiles of v_mfma_f32_16x16x32_f16
 #pragma unroll
-    for (int i = 0; i < WM; ++i)
+    for (int i = 0; i < 2 * WM; ++i)
 #pragma unroll
-        for (int jj = 0; jj < 2; ++jj)
+        for (int jj = 0; jj < 4; ++jj)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][jj][r] = 0.f;
+            for (int r = 0; r < 4; ++r) acc[i][jj][r] = 0.f;
 
-    const int f = (idx >> 2) & 3;
-    const int aoff = idx * R8_ROWB;
-    const int boff = 2 * A_PLANE_B + (wave * 64 + idx) * R8_ROWB;
-    int coff[2];
-#pragma unroll
-    for (int st = 0; st < 2; ++st) coff[st] = ((2 * st + hh) ^ f) * 16;
+    // operand lane map of the 16x16x32 MFMA: lane l holds row l & 15 of a 16-row tile, k = 8 (l >> 4) .. + 7 = logical chunk l >> 4
+    // of the 64-B LDS row, physical chunk c ^ (-(row >> 2) & 3) (conflict-free for the four lane groups of ds_read_b128: gemm_f16x2.hip)
+    const int q16 = lane >> 4, l16 = lane & 15;
+    const int coff16 = (q16 ^ ((0 - (l16 >> 2)) & 3)) * 16;
+    const int aoff = l16 * R8_ROWB + coff16;
+    const int boff = 2 * A_PLANE_B + (wave * 64 + l16) * R8_ROWB + coff16;
 
     const int nk = p.K / R8_KS;
     piece_a(0, 0, 0);
@@ -117,34 +118,32 @@ __global__ __launch_bounds__(512, 2) void gemm_f16x2_row8_kernel(GemmRowArgs p) 
         const bool nxt = kt + 1 < nk;
         const int nb = (kt + 1) & 1;
         const unsigned char* sb = smem + (kt & 1) * STAGE_B;
-#define R8_PROD(AF, BF, PA, PB)                                                                                       \
-    _Pragma("unroll") for (int i = 0; i < WM; ++i) _Pragma("unroll") for (int jj = 0; jj < 2; ++jj)                   \
-        acc[i][jj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AF[i][PA], BF[jj][PB], acc[i][jj], 0, 0, 0)
-#define R8_LOAD(AF, BF, S)                                                                                            \
-    _Pragma("unroll") for (int pl = 0; pl < 2; ++pl) {                                                                \
-        _Pragma("unroll") for (int i = 0; i < WM; ++i)                                                                \
-            AF[i][pl] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(sb + pl * A_PLANE_B + aoff + i * 32 * R8_ROWB + coff[S]));     \
-        _Pragma("unroll") for (int jj = 0; jj < 2; ++jj)                                                              \
-            BF[jj][pl] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(sb + pl * R8_B_PLANE_B + boff + jj * 32 * R8_ROWB + coff[S])); \
-    }
-        // both k-steps' fragments are requested before the first MFMA, the next stage's DMA pieces early; per k-step the two
-        // small products first, hi * hi last: the order of gemm_f16x2_kernel and of the other row kernel
-        f16x8 a0[WM][2], b0[2][2], a1[WM][2], b1[2][2];
-        R8_LOAD(a0, b0, 0)
-        R8_LOAD(a1, b1, 1)
+#define R8_PROD(PA, PB)                                                                                               \
+    _Pragma("unroll") for (int i = 0; i < 2 * WM; ++i) _Pragma("unroll") for (int jj = 0; jj < 4; ++jj)               \
+        acc[i][jj] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i][PA], b[jj][PB], acc[i][jj], 0, 0, 0)
+        // the stage's fragments (2 WM + 4 tiles of 16 rows x 32 k, two planes: as many registers as the two 16-deep steps of the
+        // 32x32 form held) are requested before the first MFMA, the next stage's DMA pieces early; the two small products first,
+        // hi * hi last, each over the stage's 32 k: the order of gemm_f16x2_kernel and of the other row kernel
+        f16x8 a[2 * WM][2], b[4][2];
+#pragma unroll
+        for (int pl = 1; pl >= 0; --pl)
+#pragma unroll
+            for (int i = 0; i < 2 * WM; ++i)
+                a[i][pl] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(sb + pl * A_PLANE_B + aoff + i * 16 * R8_ROWB));
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl)
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj)
+                b[jj][pl] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(sb + pl * R8_B_PLANE_B + boff + jj * 16 * R8_ROWB));
         if (nxt) { piece_a(0, nb, kt + 1); if (has_a1) piece_a(1, nb, kt + 1); piece_w(0, nb, kt + 1); piece_w(1, nb, kt + 1); }
-        R8_PROD(a0, b0, 1, 0); if (nxt) { piece_w(2, nb, kt + 1); piece_w(3, nb, kt + 1); }
-        R8_PROD(a0, b0, 0, 1); if (nxt) { piece_w(4, nb, kt + 1); piece_w(5, nb, kt + 1); }
-        R8_PROD(a0, b0, 0, 0); if (nxt) { piece_w(6, nb, kt + 1); piece_w(7, nb, kt + 1); }
-        R8_PROD(a1, b1, 1, 0);
-        R8_PROD(a1, b1, 0, 1);
-        R8_PROD(a1, b1, 0, 0);
+        R8_PROD(1, 0); if (nxt) { piece_w(2, nb, kt + 1); piece_w(3, nb, kt + 1); piece_w(4, nb, kt + 1); }
+        R8_PROD(0, 1); if (nxt) { piece_w(5, nb, kt + 1); piece_w(6, nb, kt + 1); piece_w(7, nb, kt + 1); }
+        R8_PROD(0, 0);
 #undef R8_PROD
-#undef R8_LOAD
     }
 
-    // ---- epilogue, part 1, one 32-row tile at a time: accumulators (C/D layout of the 32 x 32 MFMA: col = lane & 31, row =
-    //      (r & 3) + 8 (r >> 2) + 4 (lane >> 5)) -> the wave pair's slab [32][128] -> float4 pieces of rows: wave 2 c + q
+    // ---- epilogue, part 1, one 32-row tile at a time: accumulators (C/D layout of the 16 x 16 MFMA tile: col = lane & 15, row =
+    //      4 (lane >> 4) + r) -> the wave pair's slab [32][128] -> float4 pieces of rows: wave 2 c + q
     //      takes rows 16 q .. 16 q + 15 of the tile, its half-wave h rows 8 h .. 8 h + 7 of those, lane c4 the columns
     //      4 c4 .. 4 c4 + 3 of the pair's 128; the finished values stay in registers
     constexpr bool HAS_R1 = (MODE & 1) != 0, HAS_R2 = (MODE & 2) != 0, FSMN = (MODE & 4) != 0;
@@ -158,6 +157,8 @@ __global__ __launch_bounds__(512, 2) void gemm_f16x2_row8_kernel(GemmRowArgs p) 
     float4 bias4 = make_float4(0.f, 0.f, 0.f, 0.f);
     if (p.bias) bias4 = *reinterpret_cast<const float4*>(p.bias + col);
     float4 ov[WM][8];
+    int sw16 = 4 * q16 * R8_ELD + q * 64 + l16;   // this lane's first slab word in the 16 x 16 layout
+    asm volatile("" : "+v"(sw16));                // (one base register, constant offsets behind it)
 #pragma unroll
     for (int i = 0; i < WM; ++i) {
         __syncthreads();                       // the stage buffers (i = 0) / the previous tile's slab reads are done
@@ -170,10 +171,12 @@ __global__ __launch_bounds__(512, 2) void gemm_f16x2_row8_kernel(GemmRowArgs p) 
             }
         }
 #pragma unroll
-        for (int jj = 0; jj < 2; ++jj)
+        for (int si = 0; si < 2; ++si)
 #pragma unroll
-            for (int r = 0; r < 16; ++r)
-                slab[((r & 3) + 8 * (r >> 2) + 4 * hh) * R8_ELD + q * 64 + jj * 32 + idx] = acc[i][jj][r];
+            for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    slab[sw16 + (si * 16 + r) * R8_ELD + jj * 16] = acc[2 * i + si][jj][r];
         __syncthreads();
         const int rl0 = q * 16 + rsub * 8;                 // first of this half-wave's 8 rows inside the tile
         const int row0 = m0 + i * 32 + rl0;

@@ -3,6 +3,8 @@
 // stream -> LayerNorm over the 512-column row -> the two fp16 planes the next GEMM reads. Shared so that both wave grids
 // evaluate exactly the same expressions in the same order (bitwise equal, tested). The code was the tail of
 // gemm_f16x2_row_kernel until round 5 and is unchanged except for what the parameters below replace:
+// The accumulators come as floatx16 [AM][4] (32x32x16 MFMA) or as floatx4 [2 AM][8] (16x16x32 MFMA: col = lane & 15, row =
+// 4 (lane >> 4) + r); only the slab writes read that layout.
 //   NT      threads in the workgroup (512 / 256): the FSMN taps are staged by NT threads, the slabs belong to NT / 64 waves
 //   AM, I0  the accumulator array has AM row tiles; this call finishes tiles I0, I0 + 1 (rows 64 wr .. 64 wr + 63 of the block)
 //   wave    slab owner (0 .. NT / 64 - 1); wr / wc: the row half / column quarter of the block this call covers
@@ -26,12 +28,16 @@ constexpr int RW_FSW_OFF_B = RW_SLAB_B;                             // FSMN taps
 static_assert(RW_SLAB_B <= RW_LDS_B && (RW_P_FLOATS + 2 * RW_BM) * 4 <= RW_LDS_B, "epilogue LDS");
 static_assert(RW_FSW_OFF_B + RW_FS_KS * RW_BN * 4 <= RW_LDS_B, "FSMN taps do not fit behind the slabs");
 
-template <int MODE, bool LN, int NT, int AM, int I0>
-__device__ __forceinline__ void gemm2_row_epilogue(const GemmRowArgs& p, floatx16 (&accf)[AM][4], unsigned char* smem, int m0, int tid,
+template <int MODE, bool LN, int NT, int AM, int I0, typename AT, int AM_, int AN_>
+__device__ __forceinline__ void gemm2_row_epilogue(const GemmRowArgs& p, AT (&accf)[AM_][AN_], unsigned char* smem, int m0, int tid,
                                                    int wave, int wr, int wc, int lane, bool stage_taps) {
     constexpr int WM = 2, WN = 4;
+    constexpr bool S16 = AN_ == 8;           // accumulators of the 16x16x32 MFMA
+    static_assert((S16 && AM_ == 2 * AM && sizeof(AT) == 16) || (!S16 && AM_ == AM && AN_ == 4 && sizeof(AT) == 64), "accumulator tiles");
     const int hh = lane >> 5, idx = lane & 31;
-    floatx16 (&acc_)[AM][4] = accf;
+    int sw16 = 4 * (lane >> 4) * RW_ELD + (lane & 15);      // this lane's first slab word in the 16 x 16 layout
+    asm volatile("" : "+v"(sw16));                          // (one base register, constant offsets behind it)
+    AT (&acc_)[AM_][AN_] = accf;
     // measurement switches of the FSMN form (a_nt bits 4..6, measurement library only; profiles/r06ab): 16 no v-row loads, 32 no
     // residual loads, 64 no global stores -- the results are then wrong by construction
 #if defined(PF_MEASUREMENT_KERNELS)
@@ -68,11 +74,21 @@ __device__ __forceinline__ void gemm2_row_epilogue(const GemmRowArgs& p, floatx1
     float4 ov[WM][16];
 #pragma unroll
     for (int i = 0; i < WM; ++i) {
+        if constexpr (S16) {
 #pragma unroll
-        for (int jj = 0; jj < WN; ++jj)
+            for (int si = 0; si < 2; ++si)
 #pragma unroll
-            for (int r = 0; r < 16; ++r)
-                slab[((r & 3) + 8 * (r >> 2) + 4 * hh) * RW_ELD + jj * 32 + idx] = acc(i, jj)[r];
+                for (int jj = 0; jj < 8; ++jj)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        slab[sw16 + (si * 16 + r) * RW_ELD + jj * 16] = acc_[2 * (I0 + i) + si][jj][r];
+        } else {
+#pragma unroll
+            for (int jj = 0; jj < WN; ++jj)
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    slab[((r & 3) + 8 * (r >> 2) + 4 * hh) * RW_ELD + jj * 32 + idx] = acc(i, jj)[r];
+        }
         const int row0 = m0 + wr * 64 + i * 32 + rsub * 16;
         if constexpr (FSMN) {
             // this half-wave's 16 rows are one 16-row group of one sequence: valid v rows [lo, hi) (sequence start .. start +

@@ -1,13 +1,22 @@
 // The f16x2 tile GEMM (gemm_f16x2.hip: C = epilogue(A[M,K] * W[N,K]^T), both operands as two fp16 planes, three
-// v_mfma_f32_32x32x16_f16 products per operand pair into one fp32 accumulator) as a FOUR-wave 256 x 256 block: one wave per
-// SIMD, each with the SIMD's whole 512-entry register file -- a 128 x 128 output quadrant = 16 accumulator tiles = all 256
-// AGPRs, and TWO 16-deep k-steps' operand fragments (2 x 64 VGPRs) alive at a time. Same call sites as the other shapes
-// (funasr/models/transformer/positionwise_feed_forward.py:14-34, funasr/models/sanm/attention.py:256,306); the same products
-// in the same k order per output element and the shared epilogue (gemm_f16x2_epilogue.h), so results are BITWISE those of
-// every other shape (tested: tests/test_kernels_f16x2_gpu.py, tools/bench_w4.py parity). Two wave grids over the same K loop:
+// v_mfma_f32_16x16x32_f16 products per operand pair into one fp32 accumulator) as a FOUR-wave 256 x 256 block: one wave per
+// SIMD, each with the SIMD's whole 512-entry register file -- a 128 x 128 output quadrant = 64 accumulator tiles of 16 x 16 = all
+// 256 AGPRs, and ONE 32-deep stage's operand fragments (4 kinds x 8 tiles = 128 VGPRs) alive at a time. Same call sites as the
+// other shapes (funasr/models/transformer/positionwise_feed_forward.py:14-34, funasr/models/sanm/attention.py:256,306); the same
+// products in the same k order per output element and the shared epilogue (gemm_f16x2_epilogue.h), so results are BITWISE those
+// of every other shape (tested: tests/test_kernels_f16x2_gpu.py, tests/test_gemm_mfma_shape_gpu.py). Two wave grids over the same K loop:
 //   2 x 2: the 256 x 256 tile form (gemm_f16x2.hip's epilogue: fp32 / planes / QKV form), Gemm2Args.tile 7;
 //   1 x 4: the 128 x 512 full-row form (gemm_f16x2_row.hip's epilogue: residuals, FSMN memory block, LayerNorm, planes; run once
 //          per 64-row half of the block), GemmRowArgs.block_rows 130.
+//
+// The loop on the 16x16x32 MFMA. A stage is three PRODUCTS of 64 MFMAs, each over the stage's 32 k: lo*hi (A lo x W hi), hi*lo
+// (A hi x W lo), hi*hi (A hi x W hi) -- the order of every other shape. Fragment registers are reused as their kind dies: during
+// lo*hi the stage's A hi and W lo are read (one ds_read_b128 per four MFMAs); the barrier in front of hi*lo publishes the next stage
+// and frees this one's buffer; during hi*lo the NEXT stage's A lo is read (A lo is dead since lo*hi); hi*hi walks the accumulators
+// column by column so that W hi tile j is dead after eight MFMAs and the next stage's tile j lands in the same registers. One stage
+// per loop iteration and ONE register set: a form with W hi double buffered by stage parity needed two stages per iteration and two
+// tails, and the joins of that control flow made the allocator spill the 64 accumulator tuples (1.7 - 2.8 KB of scratch per lane).
+// The DMA pieces of the stage after next go out spread over the 64 MFMA gaps of hi*lo and are waited for behind the next lo*hi.
 //
 // Why another shape (round 5). The eight-wave shapes read ALL fragments of a 32-deep stage right behind the stage's barrier,
 // with both waves of every SIMD waiting for them at the same time: 192 ds_read_b128 (768 LDS cycles) per 3072 cycles of
@@ -18,7 +27,7 @@
 //     alone (no DMA, no epilogue; M = 32768, w_1) runs 92 us on zero operands = 0.90 of the 2.5 PFLOP/s peak, and 124-139 us
 //     on random operands = the power-limited rate of this instruction mix (tools/micro/mfma_peak.hip: 1647 TFLOP/s at
 //     1.78 GHz / 1240 W; profiles/r05a_w4_first_run.jsonl);
-//   * operand staging as in the eight-wave shapes: two 64-KB stages (32 deep, 64-B LDS rows, chunk swizzle c ^ ((r >> 2) & 3)),
+//   * operand staging as in the eight-wave shapes: two 64-KB stages (32 deep, 64-B LDS rows, chunk swizzle c ^ (-(r >> 2) & 3)),
 //     every wave issues 16 of a stage's 64 one-KB LDS-DMA pieces, one per three MFMA gaps, during the k-step in which the
 //     buffer falls free, and waits for them -- vmcnt(0): the only exact wait on LDS-DMA (DESIGN, round 4) -- a k-step later;
 //     ONE barrier per stage, in the middle of it (it publishes the next stage and frees the buffer just read);
@@ -50,26 +59,33 @@ template <int GM_, int GN_> struct W4Geo {
     static_assert(GM * GN == 4 && NPW == 2 * (TA + TW), "four waves");
 };
 
-struct W4Frags { f16x8 al[4], ah[4], bh[4], bl[4]; };      // A lo / hi tiles (rows), W hi / lo tiles (columns)
+// a 32-deep stage's fragments: 8 row tiles (A) / 8 column tiles (W) of 16 x 32, lo and hi planes. W hi is used by the first product
+// of a stage and by the last, so the next stage's copy needs registers of its own: two sets, by stage parity
+struct W4Frags { f16x8 al[8], ah[8], bl[8], bh[8]; };
 
-__device__ __forceinline__ void w4_mfma(floatx16& acc, const f16x8& a, const f16x8& b) {
-    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
+__device__ __forceinline__ void w4_mfma(floatx4& acc, const f16x8& a, const f16x8& b) {
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
 }
 template <int OFF> __device__ __forceinline__ void w4_read(f16x8& dst, unsigned addr) {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
 }
-// every fragment read of this wave has returned; the operands tie the wait to the registers it covers
+// every fragment read of this wave has returned; the operands tie the wait to the registers it covers (volatile asm statements keep
+// their source order, so the ties that do not fit one statement follow in empty ones)
+__device__ __forceinline__ void w4_tie8(f16x8 (&x)[8]) {
+    asm volatile("" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7]));
+}
 __device__ __forceinline__ void w4_reads_done(W4Frags& f) {
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(f.al[0]), "+v"(f.al[1]), "+v"(f.al[2]), "+v"(f.al[3]), "+v"(f.ah[0]), "+v"(f.ah[1]), "+v"(f.ah[2]), "+v"(f.ah[3]),
-                   "+v"(f.bh[0]), "+v"(f.bh[1]), "+v"(f.bh[2]), "+v"(f.bh[3]), "+v"(f.bl[0]), "+v"(f.bl[1]), "+v"(f.bl[2]), "+v"(f.bl[3]));
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    w4_tie8(f.al); w4_tie8(f.ah); w4_tie8(f.bl); w4_tie8(f.bh);
 }
 // the compiler does not see an MFMA in w4_mfma: the wait states between the last product (or the zero fill) and the next
-// reader of an accumulator are spent here (16 passes of a 32 x 32 x 16 product + the write-back)
-__device__ __forceinline__ void w4_settle(floatx16 (&acc)[4][4]) {
-    asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15"
-                 : "+a"(acc[0][0]), "+a"(acc[0][1]), "+a"(acc[0][2]), "+a"(acc[0][3]), "+a"(acc[1][0]), "+a"(acc[1][1]), "+a"(acc[1][2]), "+a"(acc[1][3]),
-                   "+a"(acc[2][0]), "+a"(acc[2][1]), "+a"(acc[2][2]), "+a"(acc[2][3]), "+a"(acc[3][0]), "+a"(acc[3][1]), "+a"(acc[3][2]), "+a"(acc[3][3]));
+// reader of an accumulator are spent here. Sized for the 16 passes of a 32 x 32 x 16 product + the write-back; the 16 x 16 x 32
+// product has 8 passes and needs less (11 wait states before a VALU read), so the old size is kept: it runs twice per kernel.
+__device__ __forceinline__ void w4_settle(floatx4 (&acc)[8][8]) {
+    asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+        asm volatile("" : "+a"(acc[i][0]), "+a"(acc[i][1]), "+a"(acc[i][2]), "+a"(acc[i][3]), "+a"(acc[i][4]), "+a"(acc[i][5]), "+a"(acc[i][6]), "+a"(acc[i][7]));
 }
 // one 1-KB LDS-DMA piece: uniform 64-bit base + 32-bit per-lane byte offset, destination lds_buf + LOFF. No branch, no compare:
 // a piece costs the issuing wave ~17 cycles of scalar work and ~19 of VMEM issue that one MFMA's shadow has to hold
@@ -87,15 +103,15 @@ template <int LOFF, bool NT> __device__ __forceinline__ void w4_piece(const char
 template <class G, int NODMA, bool A_NT>
 __device__ __forceinline__ void w4_kloop(const unsigned short* A, int lda, size_t a_plane, const unsigned short* W, int ldw, size_t w_plane,
                                          int M, int N, int K, int m0, int n0, unsigned char* smem, int wave, int wr, int wc, int lane,
-                                         floatx16 (&acc)[4][4]) {
-    const int hh = lane >> 5, idx = lane & 31;
+                                         floatx4 (&acc)[8][8]) {
+    const int q16 = lane >> 4, l16 = lane & 15;
     // ---- DMA sources. A stage is STAGE_B / 1024 pieces of 16 rows x 64 B of one plane (lane l -> row l / 4, physical chunk l % 4
     //      <- the logical chunk the read-side swizzle expects there), linear in LDS; wave w issues pieces w + 4 i: the A planes'
     //      row groups 16 (w + 4 t) .. first, then the W planes'
     unsigned va[G::TA], vw[G::TW];
     {
         const int prow = lane >> 2;
-        const unsigned chunkb = (unsigned)(((lane & 3) ^ ((prow >> 2) & 3)) * 16);
+        const unsigned chunkb = (unsigned)(((lane & 3) ^ ((0 - (prow >> 2)) & 3)) * 16);      // the swizzle of the 16x16x32 fragment read
 #pragma unroll
         for (int t = 0; t < G::TA; ++t) {
             int row = m0 + 16 * (wave + 4 * t) + prow;
@@ -126,73 +142,81 @@ __device__ __forceinline__ void w4_kloop(const unsigned short* A, int lda, size_
         else w4_piece<2 * G::A_PLANE_B + G::W_PLANE_B + 4096 * (i - 2 * G::TA - G::TW), false>(w_lo + ko, vw[i - 2 * G::TA - G::TW], buf);
     };
 
-    // ---- fragment addresses: lane (idx, hh) reads row idx of a 32-row tile, logical chunk 2 st + hh of k-step st
-    const unsigned fsw = (unsigned)((idx >> 2) & 3);
-    const unsigned fa0 = lds0 + (unsigned)((wr * 128 + idx) * 64);
-    const unsigned fb0 = lds0 + 2 * G::A_PLANE_B + (unsigned)((wc * 128 + idx) * 64);
-    // read R (0..15) of a k-step: A lo tiles, W hi tiles (the first product's operands), A hi tiles, W lo tiles
-    auto frag_read = [&](auto Rr, W4Frags& f, unsigned fa, unsigned fb) {
-        constexpr int r = decltype(Rr)::value;
-        if constexpr (r < 4) w4_read<G::A_PLANE_B + (r & 3) * 2048>(f.al[r & 3], fa);
-        else if constexpr (r < 8) w4_read<(r & 3) * 2048>(f.bh[r & 3], fb);
-        else if constexpr (r < 12) w4_read<(r & 3) * 2048>(f.ah[r & 3], fa);
-        else w4_read<G::W_PLANE_B + (r & 3) * 2048>(f.bl[r & 3], fb);
-    };
-    auto coff = [&](int st) { return (unsigned)(((2 * st + hh) ^ fsw) * 16); };
+    // ---- fragment addresses (operand lane map of the 16x16x32 MFMA): lane l reads row l & 15 of a 16-row tile, logical chunk l >> 4
+    //      (k = 8 (l >> 4) .. + 7) of the 64-B row, physical chunk c ^ (-(row >> 2) & 3) (gemm_f16x2.hip)
+    const unsigned coff16 = (unsigned)((q16 ^ ((0 - (l16 >> 2)) & 3)) * 16);
+    const unsigned fa0 = lds0 + (unsigned)((wr * 128 + l16) * 64) + coff16;
+    const unsigned fb0 = lds0 + 2 * G::A_PLANE_B + (unsigned)((wc * 128 + l16) * 64) + coff16;
 
     const int ns = K / 32;                        // stages (>= 2)
 
-    // ---- prologue: stage 0 lands and is published; its first k-step is read; stage 1 is on its way
+    // ---- prologue: stage 0 lands and is published; the operands of its first product are read; stage 1 is on its way
     [&]<int... I>(std::integer_sequence<int, I...>) { (piece(std::integral_constant<int, I>{}, 0, ldsw), ...); }(std::make_integer_sequence<int, G::NPW>{});
     if constexpr (NODMA == 0) glds_wait_all();
     __builtin_amdgcn_s_barrier();
-    W4Frags f0, f1;
-    [&]<int... I>(std::integer_sequence<int, I...>) { (frag_read(std::integral_constant<int, I>{}, f0, fa0 + coff(0), fb0 + coff(0)), ...); }(std::make_integer_sequence<int, 16>{});
+    W4Frags f;
+    [&]<int... T>(std::integer_sequence<int, T...>) { (w4_read<G::A_PLANE_B + T * 1024>(f.al[T], fa0), ...); }(std::make_integer_sequence<int, 8>{});
+    [&]<int... T>(std::integer_sequence<int, T...>) { (w4_read<T * 1024>(f.bh[T], fb0), ...); }(std::make_integer_sequence<int, 8>{});
     [&]<int... I>(std::integer_sequence<int, I...>) { (piece(std::integral_constant<int, I>{}, 1, ldsw + G::STAGE_B), ...); }(std::make_integer_sequence<int, G::NPW>{});
-    w4_reads_done(f0);
+    w4_reads_done(f);
 
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < 8; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+        for (int j = 0; j < 8; ++j)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+            for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
     w4_settle(acc);
 
-    // ---- one 16-deep k-step: 48 MFMAs on `x`; the next k-step's fragments are read into `y` from (fa, fb), one read per two
-    //      MFMAs; ISSUE: this wave's pieces of stage `js` go out, spread evenly over the 48 MFMA gaps
-    auto kstep = [&](auto Issue, W4Frags& x, W4Frags& y, unsigned fa, unsigned fb, int js, unsigned buf) {
+    // ---- one product of a stage (parity P): 64 MFMAs over the stage's 32 k, consecutive ones on different accumulators.
+    //      PH 0: lo * hi (A lo x W hi[P]) while A hi and W lo of the SAME stage are read from (fa, fb), one read per four MFMAs;
+    //      PH 1: hi * lo (A hi x W lo) while the NEXT stage's A lo is read from (fa, fb) -- A lo is dead since PH 0;
+    //      PH 2: hi * hi (A hi x W hi[P]) while the NEXT stage's W hi is read into the other set, one read per eight MFMAs.
+    //      ISSUE: this wave's pieces of stage `js` go out, spread evenly over the 64 MFMA gaps of PH 1, so that each has PH 2 and the
+    //      next stage's PH 0 (128 MFMAs, as long as the 48 of a 16-deep step of the 32x32 form) to land before it is waited for
+    auto product = [&](auto Ph, auto Issue, unsigned fa, unsigned fb, int js, unsigned buf) {
+        constexpr int PH = decltype(Ph)::value;
         constexpr bool ISSUE = decltype(Issue)::value;
         [&]<int... Gp>(std::integer_sequence<int, Gp...>) {
             ([&] {
-                constexpr int g = Gp, P = g >> 4, t = g & 15, i = t >> 2, j = t & 3;
-                // the two small products first, hi * hi last -- the order of every other shape
-                if constexpr (P == 0) w4_mfma(acc[i][j], x.al[i], x.bh[j]);
-                else if constexpr (P == 1) w4_mfma(acc[i][j], x.ah[i], x.bl[j]);
-                else w4_mfma(acc[i][j], x.ah[i], x.bh[j]);
-                if constexpr ((g & 1) == 0 && g < 32) frag_read(std::integral_constant<int, (g >> 1)>{}, y, fa, fb);
-                // piece q goes behind MFMA (48 q) / NPW + 1: g carries piece q iff that holds for q = ((g - 1) NPW + 47) / 48
-                if constexpr (ISSUE && g >= 1) {
-                    constexpr int q = ((g - 1) * G::NPW + 47) / 48;
-                    if constexpr (q < G::NPW && (48 * q) / G::NPW + 1 == g) piece(std::integral_constant<int, q>{}, js, buf);
+                // PH 0 / 1 walk the accumulators row by row; PH 2 column by column, so that W hi tile j is dead after eight MFMAs
+                // and the next stage's tile j can land in the same registers (read one MFMA into the next column)
+                constexpr int g = Gp, i = PH == 2 ? (g & 7) : (g >> 3), j = PH == 2 ? (g >> 3) : (g & 7);
+                if constexpr (PH == 0) w4_mfma(acc[i][j], f.al[i], f.bh[j]);
+                else if constexpr (PH == 1) w4_mfma(acc[i][j], f.ah[i], f.bl[j]);
+                else w4_mfma(acc[i][j], f.ah[i], f.bh[j]);
+                if constexpr (PH == 0 && (g & 3) == 0) {
+                    constexpr int r = g >> 2;
+                    if constexpr (r < 8) w4_read<r * 1024>(f.ah[r], fa);
+                    else w4_read<G::W_PLANE_B + (r - 8) * 1024>(f.bl[r - 8], fb);
+                }
+                if constexpr (PH == 1 && (g & 7) == 0) w4_read<G::A_PLANE_B + (g >> 3) * 1024>(f.al[g >> 3], fa);
+                if constexpr (PH == 2 && (g & 7) == 0 && g >= 8) w4_read<((g >> 3) - 1) * 1024>(f.bh[(g >> 3) - 1], fb);
+                // piece q goes behind MFMA (64 q) / NPW + 1 of hi*lo: g carries piece q iff that holds for q = ((g - 1) NPW + 63) / 64
+                if constexpr (ISSUE && PH == 1 && g >= 1) {
+                    constexpr int q = ((g - 1) * G::NPW + 63) / 64;
+                    if constexpr (q < G::NPW && (64 * q) / G::NPW + 1 == g) piece(std::integral_constant<int, q>{}, js, buf);
                 }
             }(), ...);
-        }(std::make_integer_sequence<int, 48>{});
-        w4_reads_done(y);
+        }(std::make_integer_sequence<int, 64>{});
+        if constexpr (PH == 2) w4_read<7 * 1024>(f.bh[7], fb);
     };
-    // stage j (buffer j & 1): first k-step from f0 while its second k-step is read into f1; everything in flight (stage j + 1)
-    // lands; the barrier publishes stage j + 1 and frees buffer j & 1 (its last reads have returned); second k-step from f1
-    // while stage j + 1's first k-step is read into f0 and stage j + 2 goes into the freed buffer
+    typedef std::integral_constant<int, 0> I0;
+    typedef std::integral_constant<int, 1> I1;
+    typedef std::integral_constant<int, 2> I2;
     auto stage = [&](auto Issue, int j) {
         const unsigned cur = (unsigned)(j & 1) * G::STAGE_B, nxt = G::STAGE_B - cur;
-        kstep(std::false_type{}, f0, f1, fa0 + cur + coff(1), fb0 + cur + coff(1), 0, 0u);
+        product(I0{}, std::false_type{}, fa0 + cur, fb0 + cur, 0, 0u);
+        w4_reads_done(f);
         if constexpr (NODMA == 0) glds_wait_all();
         __builtin_amdgcn_s_barrier();
-        kstep(Issue, f1, f0, fa0 + nxt + coff(0), fb0 + nxt + coff(0), j + 2, ldsw + cur);
+        product(I1{}, Issue, fa0 + nxt, fb0 + nxt, j + 2, ldsw + cur);
+        product(I2{}, Issue, fa0 + nxt, fb0 + nxt, j + 2, ldsw + cur);
+        w4_reads_done(f);
     };
     for (int j = 0; j < ns - 2; ++j) stage(std::true_type{}, j);
     stage(std::false_type{}, ns - 2);
-    stage(std::false_type{}, ns - 1);             // (its second k-step reads one k-step past the end into f0: never multiplied)
+    stage(std::false_type{}, ns - 1);             // (reads one stage past the end into A lo / W hi: never multiplied)
     w4_settle(acc);
 }
 
@@ -209,7 +233,7 @@ __global__ __launch_bounds__(256, 1) void gemm_f16x2_w4_kernel(Gemm2Args p, int 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wr = wave >> 1, wc = wave & 1;
-    floatx16 acc[4][4];
+    floatx4 acc[8][8];
     w4_kloop<G, NODMA, false>(p.A, p.lda, p.a_plane, p.W, p.ldw, p.w_plane, p.M, p.N, p.K, m0, n0, smem, wave, wr, wc, lane, acc);
     gemm2_epilogue<4, 4, 4, MODE, OUT, EABL>(p, acc, smem, m0, n0, nblk, wave, wr, wc, lane);
 }
@@ -225,7 +249,7 @@ __global__ __launch_bounds__(256, 1) void gemm_f16x2_w4_row_kernel(GemmRowArgs p
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    floatx16 acc[4][4];
+    floatx4 acc[8][8];
     w4_kloop<G, 0, A_NT>(p.A, p.lda, p.a_plane, p.W, p.ldw, p.w_plane, p.M, G::BN, p.K, m0, 0, smem, wave, 0, wave, lane, acc);
     gemm2_row_epilogue<MODE, LN, 256, 4, 0>(p, acc, smem, m0, tid, wave, 0, wave, lane, true);
     gemm2_row_epilogue<MODE, LN, 256, 4, 2>(p, acc, smem, m0, tid, wave, 1, wave, lane, false);
@@ -274,7 +298,9 @@ int launch_w4_row_m(const GemmRowArgs& a, hipStream_t stream) {
 
 bool gemm_f16x2_w4_ok(const Gemm2Args& a) {
     // rows / columns are clamped in the DMA sources and masked in the epilogue like the other shapes; 32-bit per-lane byte offsets
-    return a.K % 32 == 0 && a.K >= 64 && a.N % 256 == 0 && a.kslices <= 1 && a.ksplit <= 1 && !a.amax_val && a.a_kstep <= 0 && a.w_kstep <= 0 &&
+    // (not the QKV / KV form: its epilogue on top of 256 accumulator registers spills -- 326 us against the eight-wave shape's 177 at
+    // the headline shape before the 16x16x32 loop, more behind it; that form is chosen by shape)
+    return a.qkv_D <= 0 && a.K % 32 == 0 && a.K >= 64 && a.N % 256 == 0 && a.kslices <= 1 && a.ksplit <= 1 && !a.amax_val && a.a_kstep <= 0 && a.w_kstep <= 0 &&
            (size_t)a.M * (size_t)a.lda * 2 < (1ull << 32) && (size_t)a.N * (size_t)a.ldw * 2 < (1ull << 32);
 }
 
@@ -282,7 +308,6 @@ bool gemm_f16x2_w4_ok(const Gemm2Args& a) {
 int launch_gemm_f16x2_w4(const Gemm2Args& a, int abl, hipStream_t stream) {
     PF_REQUIRE(gemm_f16x2_w4_ok(a), "gemm_f16x2 (four-wave shape): needs K % 32 == 0, K >= 64, N % 256 == 0 and operands below 4 GB");
     const int mode = (a.R1 ? 1 : 0) | (a.R2 ? 2 : 0);
-    if (a.qkv_D > 0) return launch_w4<0, 2>(a, stream);
     if (a.C2) {
         PF_REQUIRE(mode == 0, "gemm_f16x2: the plane output has no residual form");
 #if defined(PF_MEASUREMENT_KERNELS)

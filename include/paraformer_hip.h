@@ -163,7 +163,8 @@ int pf_encoder_set_tensor(pf_encoder* e, const char* name, const float* data, in
 int pf_encoder_missing(const pf_encoder* e);
 /* Arithmetic mode. 3 = "f16x2", THE DEFAULT wherever its kernels exist (d_model / n_heads == 128, d_model % 256 == 0,
  * ffn_dim % 256 == 0; mode 0 otherwise): fp32-class results on the fp16 matrix cores -- every GEMM / attention operand is two
- * fp16 planes of the tensor times a power of two (x 2^e = hi + lo), three MFMA products per operand pair, fp32 accumulate,
+ * fp16 planes of the tensor times a power of two (x 2^e = hi + lo), three MFMA products per operand pair (the GEMMs on
+ * v_mfma_f32_16x16x32_f16 over 32-deep K stages, the attention on v_mfma_f32_32x32x16_f16), fp32 accumulate,
  * fp32 residual stream / LayerNorm statistics / softmax / FSMN (gemm_f16x2.hip, gemm_f16x2_row.hip, attention_f16x2.hip).
  * Meets every parity bar of mode 0 (activations <= 1e-3, CIF indices equal to the CPU reference; tests/test_parity_gpu.py,
  * fixture f32_mode) and is the measured mode of bench.py. 0 = every product on the exact fp32 MFMA (the opt-out, 2.4x

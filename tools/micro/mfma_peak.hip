@@ -3,6 +3,10 @@
 // tiles, per 16-deep step lo*hi, hi*lo, hi*hi over 4 x 4 operand fragments -- with NO LDS and NO memory traffic in the loop:
 // what the part sustains on random operand planes under its power / clock management is the ceiling any f16x2 kernel can
 // approach, and the number `roofline.power_limited_peak` quotes (tools/bench_w4.py drives this and samples MHz / W).
+// Modes 2 / 3 run the same chain on v_mfma_f32_16x16x32_f16 (_bf16): the same 128 x 128 outputs per wave in 64 tiles of 16 x 16
+// (256 accumulator registers either way), one 32-deep step per iteration instead of a 16-deep one, so an iteration carries
+// twice the FLOP of modes 0 / 1. The clock the part holds under load can depend on the MFMA shape; tools/bench_mfma_shape.py
+// alternates the modes and also checks the bits of one 16x16x32 against two chained 32x32x16 (mfma_shape_bits).
 //   hipcc --offload-arch=gfx950 -O3 -shared -fPIC tools/micro/mfma_peak.hip -o tools/micro/mfma_peak.so
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -10,6 +14,7 @@
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef float floatx16 __attribute__((ext_vector_type(16)));
+typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 template <int BF16> __device__ __forceinline__ void mf(floatx16& acc, const f16x8& a, const f16x8& b) {
     if constexpr (BF16) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
@@ -59,6 +64,92 @@ __global__ __launch_bounds__(256, 1) void mfma_peak_kernel(const uint4* __restri
 #pragma unroll
             for (int r = 0; r < 16; ++r) t += acc[i][j][r];
     if (t == 123.456f) out[0] = t;
+}
+
+template <int BF16> __device__ __forceinline__ void mf16(floatx4& acc, const f16x8& a, const f16x8& b) {
+    if constexpr (BF16) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
+    else asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
+}
+
+// the 16x16x32 form. planes: [4 kinds (A hi, A lo, W hi, W lo)][8 tiles][64 lanes] x 16 B (twice the tiles of the 32x32 form:
+// a 16-row fragment of 32 k is as many bytes as a 32-row fragment of 16 k, and there are eight of them per side)
+template <int BF16>
+__global__ __launch_bounds__(256, 1) void mfma_peak16_kernel(const uint4* __restrict__ planes, int iters, float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    f16x8 ah[8], al[8], bh[8], bl[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        ah[i] = __builtin_bit_cast(f16x8, planes[(0 * 8 + i) * 64 + lane]);
+        al[i] = __builtin_bit_cast(f16x8, planes[(1 * 8 + i) * 64 + lane]);
+        bh[i] = __builtin_bit_cast(f16x8, planes[(2 * 8 + i) * 64 + lane]);
+        bl[i] = __builtin_bit_cast(f16x8, planes[(3 * 8 + i) * 64 + lane]);
+    }
+    floatx4 acc[8][8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
+    for (int it = 0; it < iters; ++it) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) mf16<BF16>(acc[i][j], al[i], bh[j]);
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) mf16<BF16>(acc[i][j], ah[i], bl[j]);
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) mf16<BF16>(acc[i][j], ah[i], bh[j]);
+    }
+    asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
+    float t = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) t += acc[i][j][r];
+    if (t == 123.456f) out[0] = t;
+}
+
+// ---- bits of the two shapes on one problem: D = C + A W^T with A [32][32] (m, k), W [32][32] (n, k) fp16 and C [32][32] fp32, all
+// row-major. One wave. d32 takes two chained 32x32x16 (k 0..15, then 16..31); d16 takes one 16x16x32 per 16 x 16 quadrant.
+// Operand lane maps: 32x32x16 -- lane l holds row l & 31, k = 8 (l >> 5) .. + 7; 16x16x32 -- row l & 15, k = 8 (l >> 4) .. + 7.
+// C/D lane maps: 32x32 -- col l & 31, register r is row 8 (r >> 2) + 4 (l >> 5) + (r & 3); 16x16 -- col l & 15, row 4 (l >> 4) + r.
+__global__ __launch_bounds__(64) void mfma_shape_bits_kernel(const _Float16* __restrict__ A, const _Float16* __restrict__ W,
+                                                             const float* __restrict__ C, float* __restrict__ d32, float* __restrict__ d16) {
+    const int l = threadIdx.x & 63;
+    {
+        floatx16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = C[(8 * (r >> 2) + 4 * (l >> 5) + (r & 3)) * 32 + (l & 31)];
+#pragma unroll
+        for (int kk = 0; kk < 32; kk += 16) {
+            const f16x8 a = *(const f16x8*)(A + (l & 31) * 32 + kk + 8 * (l >> 5));
+            const f16x8 b = *(const f16x8*)(W + (l & 31) * 32 + kk + 8 * (l >> 5));
+            mf<0>(acc, a, b);
+        }
+        asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+#pragma unroll
+        for (int r = 0; r < 16; ++r) d32[(8 * (r >> 2) + 4 * (l >> 5) + (r & 3)) * 32 + (l & 31)] = acc[r];
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int m0 = 16 * (q >> 1), n0 = 16 * (q & 1);
+        floatx4 acc;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[r] = C[(m0 + 4 * (l >> 4) + r) * 32 + n0 + (l & 15)];
+        const f16x8 a = *(const f16x8*)(A + (m0 + (l & 15)) * 32 + 8 * (l >> 4));
+        const f16x8 b = *(const f16x8*)(W + (n0 + (l & 15)) * 32 + 8 * (l >> 4));
+        mf16<0>(acc, a, b);
+        asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+#pragma unroll
+        for (int r = 0; r < 4; ++r) d16[(m0 + 4 * (l >> 4) + r) * 32 + n0 + (l & 15)] = acc[r];
+    }
 }
 
 // ---- memory-path probes (bench.py "mem_probe"): what a box's memory system delivers to plain kernels, outside the bench clock.
@@ -114,13 +205,22 @@ float mem_probe_run(const void* src, void* dst, size_t n16, int mode, int blocks
     return best;
 }
 
+// fills d32 / d16 ([32][32] fp32 each, device) from A, W (fp16) and C (fp32); 0 on success
+int mfma_shape_bits(const void* A, const void* W, const void* C, void* d32, void* d16) {
+    hipLaunchKernelGGL(mfma_shape_bits_kernel, dim3(1), dim3(64), 0, 0, (const _Float16*)A, (const _Float16*)W, (const float*)C, (float*)d32, (float*)d16);
+    return hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
 // runs `launches` launches of `iters` steps on `blocks` workgroups of 4 waves; returns the mean ms per launch (< 0: HIP error).
-// flops per launch = blocks * 4 * iters * 48 * 32768
-float mfma_peak_run(const void* planes_dev, int bf16, int blocks, int iters, int launches, float* scratch_dev) {
+// mode 0: f16 32x32x16, 1: bf16 32x32x16 -- flops per launch = blocks * 4 * iters * 48 * 32768;
+// mode 2: f16 16x16x32, 3: bf16 16x16x32 (planes hold 8 tiles per kind) -- flops per launch = blocks * 4 * iters * 192 * 16384
+float mfma_peak_run(const void* planes_dev, int mode, int blocks, int iters, int launches, float* scratch_dev) {
     hipEvent_t a, b;
     if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return -1.f;
     auto go = [&] {
-        if (bf16) hipLaunchKernelGGL(mfma_peak_kernel<1>, dim3(blocks), dim3(256), 0, 0, (const uint4*)planes_dev, iters, scratch_dev);
+        if (mode == 2) hipLaunchKernelGGL(mfma_peak16_kernel<0>, dim3(blocks), dim3(256), 0, 0, (const uint4*)planes_dev, iters, scratch_dev);
+        else if (mode == 3) hipLaunchKernelGGL(mfma_peak16_kernel<1>, dim3(blocks), dim3(256), 0, 0, (const uint4*)planes_dev, iters, scratch_dev);
+        else if (mode == 1) hipLaunchKernelGGL(mfma_peak_kernel<1>, dim3(blocks), dim3(256), 0, 0, (const uint4*)planes_dev, iters, scratch_dev);
         else hipLaunchKernelGGL(mfma_peak_kernel<0>, dim3(blocks), dim3(256), 0, 0, (const uint4*)planes_dev, iters, scratch_dev);
     };
     go();
