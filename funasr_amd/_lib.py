@@ -99,6 +99,11 @@ class pf_tfencoder_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("input_dim", "d_model", "n_heads", "ffn_dim", "n_blocks", "precision")] + [("ln_eps", C.c_float)]
 
 
+class pf_ebranchformer_config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("input_dim", "d_model", "n_heads", "ffn_dim", "n_blocks", "cgmlp_units", "cgmlp_kernel",
+                                          "merge_kernel", "use_ffn", "macaron", "legacy", "precision")] + [("ln_eps", C.c_float)]
+
+
 class pf_textencoder_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("vocab_size", "d_model", "n_heads", "ffn_dim", "n_blocks")] + [("ln_eps", C.c_float)]
 
@@ -238,6 +243,16 @@ SIGNATURES = {
     "pf_tfencoder_forward": (C.c_int, [_vp, _vp, _pi32, _i32, _i32, _vp, _pi32, _vp]),
     "pf_k_tf_attention": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "pf_k_tf_embed_rows": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _f32, _vp, _vp]),
+    "pf_ebranchformer_create": (_vp, [C.POINTER(pf_ebranchformer_config)]),
+    "pf_ebranchformer_destroy": (None, [_vp]),
+    "pf_ebranchformer_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),
+    "pf_ebranchformer_missing": (C.c_int, [_vp]),
+    "pf_ebranchformer_set_precision": (C.c_int, [_vp, _i32]),
+    "pf_ebranchformer_num_frames": (_i32, [_vp, _i32, _i32]),
+    "pf_ebranchformer_forward": (C.c_int, [_vp, _vp, _pi32, _i32, _i32, _vp, _pi32, _vp]),
+    "pf_k_eb_gelu": (C.c_int, [_vp, _i64, _vp]),
+    "pf_k_eb_csgu": (C.c_int, [_vp, _vp, _vp, _f32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "pf_k_eb_merge": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "pf_textencoder_create": (_vp, [C.POINTER(pf_textencoder_config)]),
     "pf_textencoder_destroy": (None, [_vp]),
     "pf_textencoder_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),

@@ -9,7 +9,8 @@
 // begin_common, step_common_checks and reorder_common are the argument checks of both. Cf, Tf, Td and Fd add what is their own: the
 // block loops, the K / V cache with its device reorder, the FSMN windows with their position rule. The LCB-Net handles (pf_textencoder_*,
 // pf_fusion_*; kernels in lcbnet.hip) sit on the same base: the text encoder is the Transformer encoder's block loop (SubEnc::tf_blocks)
-// behind token rows instead of the subsampling, the fusion layer that block with a cross-attention between its two halves.
+// behind token rows instead of the subsampling, the fusion layer that block with a cross-attention between its two halves. The
+// E-Branchformer encoder (pf_ebranchformer_*, struct Eb; kernels in ebranchformer.hip) is a third block loop behind the same front.
 //
 // Encoder forward over the zero-padded batch [B, Tin, F] (the reference runs Conv2dSubsampling and the convolution module over
 // the padded tensor without masking, so every row of the batch is computed and a clip's frames depend on the batch's length):
@@ -39,6 +40,7 @@
 #include "conformer.h"
 #include "uniasr.h"
 #include "lcbnet.h"
+#include "ebranchformer.h"
 
 using namespace pf;
 
@@ -376,6 +378,143 @@ int Tf::forward(const float* feats, const int32_t* lens, int B, int Tin, float* 
     return tf_blocks(bx, B, out);
 }
 
+// ================================================================================================ E-Branchformer encoder
+// funasr/models/e_branchformer/encoder.py EBranchformerEncoder (input_layer conv2d, rel_selfattn): the shared subsampling -> x sqrt(D)
+// -> blocks `encoders.i.`:
+//   [x += 0.5 ffm(norm_ff_macaron x)]                                        (use_ffn and macaron; Swish, 0.5 folded into w_2#half)
+//   x1 = attn(norm_mha x)                                                    (the Conformer's relative-position attention + linear_out)
+//   x2 = channel_proj2(csgu(GELU(channel_proj1(norm_mlp x))))                (cgMLP; launch_eb_gelu, launch_eb_csgu)
+//   x += merge_proj([x1 | x2] + depthwise_conv_fusion([x1 | x2]))            (launch_eb_merge reads x1 and x2 from their own buffers)
+//   [x += ff_scale ff(norm_ff x)]                                            (use_ffn)
+//   x = norm_final x
+// -> after_norm. Neither depthwise conv is masked: every row of the padded batch is computed in every block.
+// Launches per block in fp32: 16 without feed-forwards (8 GEMMs: q, k, v, linear_pos, linear_out, channel_proj1, channel_proj2,
+// merge_proj; 5 row kernels: norm_mha, norm_mlp, GELU, merge, norm_final; 2 for the gating unit: row statistics, then normalise +
+// conv + gate; 1 attention), + 4 per feed-forward (LayerNorm, w_1, Swish, w_2): 24 at the template's macaron pair.
+// precision 3: the block GEMMs from two-plane fp16 operands, exponents from a-priori bounds of the weights: the LayerNorm bounds for
+// q / k / v, channel_proj1 and w_1; the row-L1 bound of linear_v for linear_out's operand and of w_1 for w_2's; for channel_proj2's
+// operand x_r * g the product of the row-L1 bound of channel_proj1's first U / 2 rows (|GELU(v)| <= |v|) and of the gate's bound
+// (csgu.norm's LayerNorm bound times the tap L1, plus |bias|). merge_proj STAYS EXACT FP32 in this mode: the bound of its operand
+// ((1 + tap L1) times the row-L1 bounds of linear_out and of channel_proj2 over the product bound above, plus |bias|) compounds to
+// 2^20 times the rows' size at the test fixture's weights and further at the template's widths, past the 2^17 within which a two-plane
+// operand keeps its 22 bits, and with it the template-size encoder was 18 x the reference's fp32 - fp64 gap from the float64 oracle
+// (DESIGN 3.16). linear_pos and the subsampling stay exact fp32 too.
+struct EbBlockX { int e_ffm_in = 0, e_ffm_h = 0, e_mha_in = 0, e_att = 0, e_mlp_in = 0, e_gate = 0, e_ff_in = 0, e_ff_h = 0; };
+
+struct Eb : SubEnc<pf_ebranchformer_config> {
+    std::vector<EbBlockX> bx;
+    DevBuf P, b1, b2, gate, cat, stats;
+    int pos_rows() const { return cfg.legacy ? 5000 : 9999; }
+    bool ffn() const { return cfg.use_ffn != 0; }
+    bool macaron() const { return cfg.use_ffn != 0 && cfg.macaron != 0; }
+    int prepare(hipStream_t s);
+    int forward(const float* feats, const int32_t* lens, int B, int Tin, float* out, int32_t* olens, hipStream_t s);
+};
+
+// max over the C channels of a depthwise conv (w [C][K], bias [C]) of in_bound * sum_k |w[c][k]| + |bias[c]|: an a-priori bound on
+// |conv(x) + bias| for |x| <= in_bound
+float dw_bound(const std::vector<float>& w, const std::vector<float>& bias, int K, int C, float in_bound) {
+    float m = 0.f;
+    for (int c = 0; c < C; ++c) {
+        float l1 = 0.f;
+        for (int k = 0; k < K; ++k) l1 += fabsf(w[(size_t)c * K + k]);
+        m = fmaxf(m, in_bound * l1 + fabsf(bias[c]));
+    }
+    return m;
+}
+
+int Eb::prepare(hipStream_t s) {
+    const int D = cfg.d_model, NB = cfg.n_blocks, FF = cfg.ffn_dim, U = cfg.cgmlp_units, C = U / 2;
+    if (CfSub::prepare(tt, D, D, CfSub::F2(cfg.input_dim), "ebranchformer")) return -2;
+    bx.assign(NB, EbBlockX());
+    if (cfg.precision == 3) tt.drop_bf16();
+    for (int i = 0; i < NB; ++i) {
+        const std::string p = blk(i);
+        for (const char* ff : {"feed_forward.", "feed_forward_macaron."}) {
+            if (!macaron()) break;
+            std::vector<float> w = tt.host(p + ff + "w_2.weight"), bb = tt.host(p + ff + "w_2.bias");
+            if (w.empty() || bb.empty()) { set_error("ebranchformer: weight copy failed"); return -2; }
+            for (float& v : w) v *= 0.5f;
+            for (float& v : bb) v *= 0.5f;
+            if (tt.put_derived(p + ff + "w_2.weight#half", w) || tt.put_derived(p + ff + "w_2.bias#half", bb)) return -2;
+        }
+        if (cfg.precision != 3) continue;
+        EbBlockX& x = bx[i];
+        if (macaron() && ln_lin_exps(p + "norm_ff_macaron.", p + "feed_forward_macaron.w_1.", FF, &x.e_ffm_in, &x.e_ffm_h, s)) return -2;
+        if (ffn() && ln_lin_exps(p + "norm_ff.", p + "feed_forward.w_1.", FF, &x.e_ff_in, &x.e_ff_h, s)) return -2;
+        float rb, nb;
+        if (ln_lin_exps(p + "norm_mha.", p + "attn.linear_v.", D, &x.e_mha_in, &x.e_att, s)) return -2;
+        int e_r;                            // (x_r alone reaches no GEMM: its bound goes into the gated product's)
+        if (ln_lin_exps(p + "norm_mlp.", p + "cgmlp.channel_proj1.0.", C, &x.e_mlp_in, &e_r, s, &rb)) return -2;
+        if (TensorTable::dev_ln_bound(tt.get(p + "cgmlp.csgu.norm.weight"), tt.get(p + "cgmlp.csgu.norm.bias"), C, &nb, s)) return -2;
+        std::vector<float> gw = tt.host(p + "cgmlp.csgu.conv.weight"), gb = tt.host(p + "cgmlp.csgu.conv.bias");
+        if (gw.empty() || gb.empty()) { set_error("ebranchformer: weight copy failed"); return -2; }
+        x.e_gate = exp_for_bound(rb * dw_bound(gw, gb, cfg.cgmlp_kernel, C, nb));
+    }
+    prepared = tt.version;
+    return 0;
+}
+
+int Eb::forward(const float* feats, const int32_t* lens, int B, int Tin, float* out, int32_t* olens, hipStream_t s) {
+    const pf_ebranchformer_config& c = cfg;
+    const int D = c.d_model, FF = c.ffn_dim, U = c.cgmlp_units, C = U / 2;
+    int rc;
+    if ((rc = front(feats, lens, B, Tin, std::max(ffn() ? FF : 0, U), nullptr, olens, s))) return rc;
+    const int nP = c.legacy ? T : 2 * T - 1;
+    const size_t M = (size_t)Mi;
+    if (P.ensure(sizeof(float) * (size_t)nP * D) || b1.ensure(sizeof(float) * M * D) || b2.ensure(sizeof(float) * M * D) ||
+        gate.ensure(sizeof(float) * M * C) || cat.ensure(sizeof(float) * M * 2 * D) || stats.ensure(sizeof(float) * M * 2))
+        return -2;
+    const float* pos = tt.get("pos_table") + (c.legacy ? (size_t)0 : (size_t)(5000 - T) * D);
+    float *x = xa.as<float>(), *y = xb.as<float>(), *xn = this->xn.as<float>(), *qkv = this->qkv.as<float>(), *Pm = P.as<float>(),
+          *att = this->att.as<float>(), *hid = this->hid.as<float>(), *x1 = b1.as<float>(), *x2 = b2.as<float>(), *g = gate.as<float>(),
+          *cc = cat.as<float>();
+    for (int i = 0; i < c.n_blocks; ++i) {
+        const std::string p = blk(i);
+        const EbBlockX& e = bx[i];
+        const char* half = macaron() ? "#half" : "";
+        auto ff = [&](const std::string& f, const std::string& norm, int e_in, int e_h) {
+            int r;
+            if ((r = ln(p + norm, x, xn))) return r;
+            if ((r = lin(xn, D, p + f + "w_1.", FF, nullptr, hid, FF, e_in))) return r;
+            if ((r = launch_cf_act(hid, M * FF, 1, s))) return r;
+            if ((r = lin(hid, FF, p + f + "w_2.", D, x, y, D, e_h, half))) return r;
+            std::swap(x, y);
+            return 0;
+        };
+        if (macaron() && (rc = ff("feed_forward_macaron.", "norm_ff_macaron.", e.e_ffm_in, e.e_ffm_h))) return rc;
+        // branch 1: relative-position self-attention -> x1
+        if ((rc = ln(p + "norm_mha.", x, xn))) return rc;
+        const char* names[3] = {"attn.linear_q.", "attn.linear_k.", "attn.linear_v."};
+        for (int j = 0; j < 3; ++j)
+            if ((rc = lin(xn, D, p + names[j], D, nullptr, qkv + (size_t)j * D, 3 * D, e.e_mha_in))) return rc;
+        if ((rc = gm(false, pos, nP, D, p + "attn.linear_pos.weight", nullptr, D, nullptr, Pm, D, 0))) return rc;
+        if ((rc = launch_cf_relpos_attention(qkv, Pm, tt.get(p + "attn.pos_bias_u"), tt.get(p + "attn.pos_bias_v"), klens.as<int>(), B, T,
+                                             c.n_heads, c.legacy, att, s)))
+            return rc;
+        if ((rc = lin(att, D, p + "attn.linear_out.", D, nullptr, x1, D, e.e_att))) return rc;
+        // branch 2: cgMLP -> x2
+        if ((rc = ln(p + "norm_mlp.", x, xn))) return rc;
+        if ((rc = lin(xn, D, p + "cgmlp.channel_proj1.0.", U, nullptr, hid, U, e.e_mlp_in))) return rc;
+        if ((rc = launch_eb_gelu(hid, M * U, s))) return rc;
+        if ((rc = launch_eb_csgu(hid, tt.get(p + "cgmlp.csgu.norm.weight"), tt.get(p + "cgmlp.csgu.norm.bias"), c.ln_eps,
+                                 tt.get(p + "cgmlp.csgu.conv.weight"), tt.get(p + "cgmlp.csgu.conv.bias"), B, T, C, c.cgmlp_kernel,
+                                 stats.as<float>(), g, s)))
+            return rc;
+        if ((rc = lin(g, C, p + "cgmlp.channel_proj2.", D, nullptr, x2, D, e.e_gate))) return rc;
+        // merge
+        if ((rc = launch_eb_merge(x1, x2, tt.get(p + "depthwise_conv_fusion.weight"), tt.get(p + "depthwise_conv_fusion.bias"), B, T, D,
+                                  c.merge_kernel, cc, s)))
+            return rc;
+        if ((rc = gm(false, cc, Mi, 2 * D, p + "merge_proj.weight", tt.get(p + "merge_proj.bias"), D, x, y, D, 0))) return rc;   // fp32 in both modes
+        std::swap(x, y);
+        if (ffn() && (rc = ff("feed_forward.", "norm_ff.", e.e_ff_in, e.e_ff_h))) return rc;
+        if ((rc = ln(p + "norm_final.", x, y))) return rc;
+        std::swap(x, y);
+    }
+    return ln("after_norm.", x, out);
+}
+
 // ================================================================================================ LCB-Net: text encoder, fusion layer
 // funasr/models/lcbnet/encoder.py. TransformerTextEncoder: Embedding x sqrt(D) + pe -> the block loop of the Transformer encoder ->
 // after_norm; its front is the token rows instead of the subsampling. FusionSANEncoder (SelfSrcAttention), ONE layer over the audio
@@ -624,6 +763,74 @@ int32_t pf_tfencoder_num_frames(const pf_tfencoder* h, int32_t n_frames, int32_t
 int pf_tfencoder_forward(pf_tfencoder* h, const float* feats, const int32_t* lens_host, int32_t B, int32_t Tin, float* out,
                          int32_t* out_lens_host, void* stream) {
     return enc_forward(reinterpret_cast<Tf*>(h), "tfencoder", "table holds", feats, lens_host, B, Tin, out, out_lens_host, stream);
+}
+
+pf_ebranchformer* pf_ebranchformer_create(const pf_ebranchformer_config* cfg) {
+    if (!cfg) { set_error("ebranchformer: null config"); return nullptr; }
+    if (check_device()) return nullptr;
+    const pf_ebranchformer_config& c = *cfg;
+    auto odd31 = [](int k) { return k % 2 == 1 && k >= 1 && k <= 31; };
+    auto flag = [](int v) { return v == 0 || v == 1; };
+    const bool ok = c.input_dim >= 7 && c.input_dim <= 256 && c.d_model > 0 && c.d_model % 64 == 0 && c.d_model <= 2048 && c.n_heads > 0 &&
+                    c.d_model == 64 * c.n_heads && c.n_blocks >= 0 && c.cgmlp_units > 0 && c.cgmlp_units % 64 == 0 && c.cgmlp_units <= 16384 &&
+                    odd31(c.cgmlp_kernel) && odd31(c.merge_kernel) && flag(c.use_ffn) && flag(c.macaron) && flag(c.legacy) &&
+                    (!c.use_ffn || (c.ffn_dim > 0 && c.ffn_dim % 32 == 0)) && (c.precision == 0 || c.precision == 3) && c.ln_eps > 0.f;
+    if (!ok) {
+        set_error("ebranchformer: unsupported config (7 .. 256 input features, head dim 64, d_model % 64, cgmlp_units % 64 (gate channels "
+                  "% 32), ffn_dim % 32, odd conv kernels <= 31, precision 0 or 3)");
+        return nullptr;
+    }
+    std::unique_ptr<Eb> h(new Eb());
+    h->cfg = c;
+    TensorTable& tt = h->tt;
+    const int D = c.d_model, FF = c.ffn_dim, U = c.cgmlp_units;
+    int rc = 0;
+    rc |= tt.add_linear("embed.conv.0.", D, 9);
+    rc |= tt.add_linear("embed.conv.2.", D, (int64_t)D * 9);
+    rc |= tt.add_linear("embed.out.0.", D, (int64_t)D * CfSub::F2(c.input_dim));
+    rc |= tt.add("pos_table", (int64_t)h->pos_rows() * D);
+    for (int i = 0; i < c.n_blocks; ++i) {
+        const std::string p = blk(i);
+        for (const char* n : {"linear_q.", "linear_k.", "linear_v.", "linear_out."}) rc |= tt.add_linear(p + "attn." + n, D, D);
+        rc |= tt.add_linear(p + "attn.linear_pos.", D, D, false);
+        rc |= tt.add(p + "attn.pos_bias_u", D);
+        rc |= tt.add(p + "attn.pos_bias_v", D);
+        rc |= tt.add_linear(p + "cgmlp.channel_proj1.0.", U, D);
+        rc |= tt.add_linear(p + "cgmlp.csgu.norm.", U / 2, 1);
+        rc |= tt.add_linear(p + "cgmlp.csgu.conv.", U / 2, c.cgmlp_kernel);
+        rc |= tt.add_linear(p + "cgmlp.channel_proj2.", D, U / 2);
+        rc |= tt.add_linear(p + "depthwise_conv_fusion.", 2 * D, c.merge_kernel);
+        rc |= tt.add_linear(p + "merge_proj.", D, 2 * D);
+        if (h->ffn()) {
+            rc |= tt.add_linear(p + "feed_forward.w_1.", FF, D);
+            rc |= tt.add_linear(p + "feed_forward.w_2.", D, FF);
+            rc |= tt.add_linear(p + "norm_ff.", D, 1);
+        }
+        if (h->macaron()) {
+            rc |= tt.add_linear(p + "feed_forward_macaron.w_1.", FF, D);
+            rc |= tt.add_linear(p + "feed_forward_macaron.w_2.", D, FF);
+            rc |= tt.add_linear(p + "norm_ff_macaron.", D, 1);
+        }
+        for (const char* n : {"norm_mha.", "norm_mlp.", "norm_final."}) rc |= tt.add_linear(p + n, D, 1);
+    }
+    rc |= tt.add_linear("after_norm.", D, 1);
+    if (rc) return nullptr;
+    return reinterpret_cast<pf_ebranchformer*>(h.release());
+}
+void pf_ebranchformer_destroy(pf_ebranchformer* h) { delete reinterpret_cast<Eb*>(h); }
+int pf_ebranchformer_set_tensor(pf_ebranchformer* h, const char* name, const float* data, int64_t numel) {
+    return table_set(reinterpret_cast<Eb*>(h), "ebranchformer_set_tensor: null", name, data, numel);
+}
+int pf_ebranchformer_missing(const pf_ebranchformer* h) { return table_missing(reinterpret_cast<const Eb*>(h)); }
+int pf_ebranchformer_set_precision(pf_ebranchformer* h, int32_t precision) {
+    return enc_set_precision(reinterpret_cast<Eb*>(h), "ebranchformer", precision);
+}
+int32_t pf_ebranchformer_num_frames(const pf_ebranchformer* h, int32_t n_frames, int32_t padded_frames) {
+    return enc_num_frames(h, n_frames, padded_frames);
+}
+int pf_ebranchformer_forward(pf_ebranchformer* h, const float* feats, const int32_t* lens_host, int32_t B, int32_t Tin, float* out,
+                             int32_t* out_lens_host, void* stream) {
+    return enc_forward(reinterpret_cast<Eb*>(h), "ebranchformer", "tables hold", feats, lens_host, B, Tin, out, out_lens_host, stream);
 }
 
 pf_tdecoder* pf_tdecoder_create(const pf_tdecoder_config* cfg) {
@@ -1039,6 +1246,18 @@ int pf_k_text_embed_rows(const float* table, const int32_t* ids_dev, const float
 int pf_k_conformer_glu_dw(const float* g,const float* dw, const float* dw_bias, const float* bn_scale, const float* bn_shift, int32_t B,
                           int32_t T, int32_t D, int32_t taps, float* y, void* stream) {
     return launch_cf_glu_dw(g, dw, dw_bias, bn_scale, bn_shift, B, T, D, taps, y, reinterpret_cast<hipStream_t>(stream));
+}
+int pf_k_eb_gelu(float* x, int64_t n, void* stream) {
+    PF_REQUIRE(n > 0, "eb_gelu: n > 0");
+    return launch_eb_gelu(x, (size_t)n, reinterpret_cast<hipStream_t>(stream));
+}
+int pf_k_eb_csgu(const float* h, const float* gamma, const float* beta, float eps, const float* dw, const float* dw_bias, int32_t B, int32_t T,
+                 int32_t C, int32_t taps, float* stats, float* y, void* stream) {
+    return launch_eb_csgu(h, gamma, beta, eps, dw, dw_bias, B, T, C, taps, stats, y, reinterpret_cast<hipStream_t>(stream));
+}
+int pf_k_eb_merge(const float* x1, const float* x2, const float* dw, const float* dw_bias, int32_t B, int32_t T, int32_t D, int32_t taps,
+                  float* y, void* stream) {
+    return launch_eb_merge(x1, x2, dw, dw_bias, B, T, D, taps, y, reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -407,6 +407,35 @@ def transformer_state_dict(seed: int, model) -> Dict[str, torch.Tensor]:
     return conformer_state_dict(seed, model)
 
 
+def ebranchformer_conf(output_size: int = 128, attention_heads: int = 2, linear_units: int = 256, cgmlp_linear_units: int = 256,
+                       enc_blocks: int = 2, dec_blocks: int = 2, cgmlp_kernel: int = 31, merge_kernel: int = 31, use_ffn: bool = True,
+                       macaron: bool = True, rel_pos_type: str = "latest", vocab: int = 40, input_size: int = 80,
+                       dec_linear_units: int = None, attention_dropout_rate: float = 0.1) -> dict:
+    """constructor arguments of an E-Branchformer model (the layout of funasr/models/e_branchformer/template.yaml) at a chosen size"""
+    enc = {"output_size": output_size, "attention_heads": attention_heads, "attention_layer_type": "rel_selfattn",
+           "pos_enc_layer_type": "rel_pos", "rel_pos_type": rel_pos_type, "cgmlp_linear_units": cgmlp_linear_units,
+           "cgmlp_conv_kernel": cgmlp_kernel, "use_linear_after_conv": False, "gate_activation": "identity", "num_blocks": enc_blocks,
+           "dropout_rate": 0.1, "positional_dropout_rate": 0.1, "attention_dropout_rate": attention_dropout_rate, "input_layer": "conv2d",
+           "layer_drop_rate": 0.0, "linear_units": linear_units, "positionwise_layer_type": "linear", "use_ffn": use_ffn,
+           "macaron_ffn": macaron, "merge_conv_kernel": merge_kernel}
+    dec = {"attention_heads": attention_heads, "linear_units": dec_linear_units or linear_units, "num_blocks": dec_blocks, "dropout_rate": 0.1,
+           "positional_dropout_rate": 0.1, "self_attention_dropout_rate": 0.0, "src_attention_dropout_rate": 0.0}
+    return {"encoder": "EBranchformerEncoder", "encoder_conf": enc, "decoder": "TransformerDecoder", "decoder_conf": dec,
+            "ctc_weight": 0.3, "lsm_weight": 0.1, "length_normalized_loss": False, "input_size": input_size, "vocab_size": vocab}
+
+
+# funasr/models/e_branchformer/template.yaml (the ESPnet AISHELL recipe)
+EBRANCHFORMER_TEMPLATE = dict(output_size=256, attention_heads=4, linear_units=1024, cgmlp_linear_units=1024, enc_blocks=12, dec_blocks=6,
+                              cgmlp_kernel=31, merge_kernel=31, use_ffn=True, macaron=True, rel_pos_type="latest", vocab=4234,
+                              dec_linear_units=2048)
+
+
+def ebranchformer_state_dict(seed: int, model) -> Dict[str, torch.Tensor]:
+    """synthetic weights in the layout of `model` (an EBranchformer module or the reference's), drawn as conformer_state_dict draws
+    them (the two depthwise convs fan-in scaled with a bias of order 0.1: neither near the identity nor negligible beside it)"""
+    return conformer_state_dict(seed, model)
+
+
 def lcbnet_conf(output_size: int = 128, attention_heads: int = 2, linear_units: int = 256, enc_blocks: int = 2, dec_blocks: int = 2,
                 text_blocks: int = 2, vocab: int = 300, input_size: int = 80) -> dict:
     """constructor arguments of an LCBNet model at a chosen size: transformer_conf plus the text encoder, the one fusion layer and the

@@ -551,6 +551,47 @@ int32_t pf_tfencoder_num_frames(const pf_tfencoder* h, int32_t n_frames, int32_t
 int pf_tfencoder_forward(pf_tfencoder* h, const float* feats_dev, const int32_t* lens_host, int32_t B, int32_t Tin, float* out_dev,
                          int32_t* out_lens_host, void* stream);
 
+/* ---- E-Branchformer encoder (funasr/models/e_branchformer/encoder.py EBranchformerEncoder: Conv2dSubsampling, then blocks of two
+ * parallel branches -- relative-position self-attention ("latest" or "legacy", head dim 64) and the convolutional gating MLP
+ * (branchformer/cgmlp.py: Linear + exact GELU, LayerNorm + depthwise conv gate, Linear) -- merged by a depthwise conv over their
+ * concatenation and a Linear, with optional (macaron) Swish feed-forwards around them). Tensor names are the reference's keys below
+ * `encoder.`: "embed.conv.0.weight", "encoders.0.attn.linear_pos.weight", "encoders.0.attn.pos_bias_u",
+ * "encoders.0.cgmlp.channel_proj1.0.weight", "encoders.0.cgmlp.csgu.norm.weight", "encoders.0.cgmlp.csgu.conv.weight",
+ * "encoders.0.cgmlp.channel_proj2.bias", "encoders.0.depthwise_conv_fusion.weight", "encoders.0.merge_proj.weight",
+ * "encoders.0.norm_mlp.weight", "after_norm.bias", ... plus "pos_table" as for pf_conformer.
+ * Shapes, lengths and precisions are pf_conformer's: the ZERO-PADDED batch in, every row computed, lengths by the mask rule. Neither
+ * depthwise conv is masked (the reference's are not): a clip's frames depend on the rows behind its end, i.e. on its batch.
+ * precision 3 runs the block GEMMs on the fp16 MFMA with two-plane operands except merge_proj, which stays exact fp32 (its operand's
+ * a-priori bound is too loose); the subsampling GEMMs, linear_pos, attention, convs and LayerNorms are fp32 in both.
+ * cgmlp_units % 64 == 0 (the gate has cgmlp_units / 2 channels), conv kernels odd <= 31; ffn_dim is read only with use_ffn. */
+typedef struct pf_ebranchformer pf_ebranchformer;
+typedef struct pf_ebranchformer_config {
+    int32_t input_dim, d_model, n_heads, ffn_dim, n_blocks;
+    int32_t cgmlp_units, cgmlp_kernel, merge_kernel;
+    int32_t use_ffn;              /* 1: a Swish feed-forward behind the merge */
+    int32_t macaron;              /* 1 (with use_ffn): a second feed-forward in front of the branches, both scaled by 0.5 */
+    int32_t legacy;               /* 1: rel_pos_type "legacy" */
+    int32_t precision;            /* 0 fp32, 3 f16x2 */
+    float ln_eps;
+} pf_ebranchformer_config;
+pf_ebranchformer* pf_ebranchformer_create(const pf_ebranchformer_config* cfg);
+void pf_ebranchformer_destroy(pf_ebranchformer* h);
+int pf_ebranchformer_set_tensor(pf_ebranchformer* h, const char* name, const float* data, int64_t numel);
+int pf_ebranchformer_missing(const pf_ebranchformer* h);
+int pf_ebranchformer_set_precision(pf_ebranchformer* h, int32_t precision);
+int32_t pf_ebranchformer_num_frames(const pf_ebranchformer* h, int32_t n_frames, int32_t padded_frames);
+/* as pf_conformer_forward. Fails when Tin < 7 or T > 5000. No sync. */
+int pf_ebranchformer_forward(pf_ebranchformer* h, const float* feats_dev, const int32_t* lens_host, int32_t B, int32_t Tin, float* out_dev,
+                             int32_t* out_lens_host, void* stream);
+/* single-kernel hooks (tests) of the block: the exact GELU in place (n % 4 == 0); the gating unit h_dev [B T, 2 C] -> y_dev [B T, C] =
+ * x_r * (dwconv(LayerNorm(x_g)) + bias) with stats_dev [B T, 2] as workspace; the merge x1_dev, x2_dev [B T, D] (separate buffers) ->
+ * y_dev [B T, 2 D] = c + dwconv(c) + bias over c = [x1 | x2]. Convs over time within a sequence's T rows, zeros outside. */
+int pf_k_eb_gelu(float* x_dev, int64_t n, void* stream);
+int pf_k_eb_csgu(const float* h_dev, const float* gamma_dev, const float* beta_dev, float eps, const float* dw_dev, const float* dw_bias_dev,
+                 int32_t B, int32_t T, int32_t C, int32_t taps, float* stats_dev, float* y_dev, void* stream);
+int pf_k_eb_merge(const float* x1_dev, const float* x2_dev, const float* dw_dev, const float* dw_bias_dev, int32_t B, int32_t T, int32_t D,
+                  int32_t taps, float* y_dev, void* stream);
+
 /* ---- Transformer decoder, one autoregressive step for all running hypotheses of a beam (funasr/models/transformer/decoder.py
  * TransformerDecoder.forward_one_step / batch_score: embed x sqrt(D) + sinusoid, pre-LN self-attention over the hypothesis' own
  * prefix, cross-attention over the utterance's encoder memory, ReLU feed-forward, after_norm, output layer, log-softmax; head dim 64).
