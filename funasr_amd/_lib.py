@@ -104,6 +104,15 @@ class pf_ebranchformer_config(C.Structure):
                                           "merge_kernel", "use_ffn", "macaron", "legacy", "precision")] + [("ln_eps", C.c_float)]
 
 
+class pf_pif_config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("d_model", "l_order", "r_order", "sigma_heads")] + \
+               [(n, C.c_float) for n in ("threshold", "smooth_factor", "noise_threshold")]
+
+
+class pf_sandecoder_config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("d_model", "n_heads", "ffn_dim", "n_blocks", "vocab_size", "precision")] + [("ln_eps", C.c_float)]
+
+
 class pf_textencoder_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("vocab_size", "d_model", "n_heads", "ffn_dim", "n_blocks")] + [("ln_eps", C.c_float)]
 
@@ -253,6 +262,21 @@ SIGNATURES = {
     "pf_k_eb_gelu": (C.c_int, [_vp, _i64, _vp]),
     "pf_k_eb_csgu": (C.c_int, [_vp, _vp, _vp, _f32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "pf_k_eb_merge": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "pf_pif_create": (_vp, [C.POINTER(pf_pif_config)]),
+    "pf_pif_destroy": (None, [_vp]),
+    "pf_pif_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),
+    "pf_pif_missing": (C.c_int, [_vp]),
+    "pf_pif_alphas": (C.c_int, [_vp, _vp, _pi32, _i32, _i32, _vp, _vp, _vp]),
+    "pf_pif_embeds": (C.c_int, [_vp, _vp, _vp, _vp, _pi32, _pi32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "pf_sandecoder_create": (_vp, [C.POINTER(pf_sandecoder_config)]),
+    "pf_sandecoder_destroy": (None, [_vp]),
+    "pf_sandecoder_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),
+    "pf_sandecoder_missing": (C.c_int, [_vp]),
+    "pf_sandecoder_set_precision": (C.c_int, [_vp, _i32]),
+    "pf_sandecoder_forward": (C.c_int, [_vp, _vp, _pi32, _vp, _pi32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "pf_k_pif_alphas": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp]),
+    "pf_k_pif_align": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "pf_k_pif_embed": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "pf_textencoder_create": (_vp, [C.POINTER(pf_textencoder_config)]),
     "pf_textencoder_destroy": (None, [_vp]),
     "pf_textencoder_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),

@@ -45,6 +45,7 @@ from . import bicif_paraformer as _bicif_paraformer  # noqa: F401  (registers Bi
 from . import conformer as _conformer  # noqa: F401  (registers Conformer / ConformerEncoder / TransformerDecoder)
 from . import transformer as _transformer  # noqa: F401  (registers Transformer / TransformerEncoder)
 from . import ebranchformer as _ebranchformer  # noqa: F401  (registers EBranchformer / Branchformer / EBranchformerEncoder)
+from . import e_paraformer as _e_paraformer  # noqa: F401  (registers EParaformer / PifPredictor / ParaformerSANDecoder)
 from . import sanm as _sanm  # noqa: F401  (registers SANM / FsmnDecoder)
 from . import uniasr as _uniasr  # noqa: F401  (registers UniASR / FsmnDecoderSCAMAOpt)
 from . import lcbnet as _lcbnet  # noqa: F401  (registers LCBNet / TransformerTextEncoder / FusionSANEncoder / ConvBiasPredictor)

@@ -11,6 +11,8 @@
 // pf_fusion_*; kernels in lcbnet.hip) sit on the same base: the text encoder is the Transformer encoder's block loop (SubEnc::tf_blocks)
 // behind token rows instead of the subsampling, the fusion layer that block with a cross-attention between its two halves. The
 // E-Branchformer encoder (pf_ebranchformer_*, struct Eb; kernels in ebranchformer.hip) is a third block loop behind the same front.
+// E-Paraformer's one-pass decoder (pf_sandecoder_*, struct Sd) is the fusion layer's block n_blocks times on that base, and its
+// predictor (pf_pif_*, struct Pif; kernels in pif.hip) a handle of two calls.
 //
 // Encoder forward over the zero-padded batch [B, Tin, F] (the reference runs Conv2dSubsampling and the convolution module over
 // the padded tensor without masking, so every row of the batch is computed and a clip's frames depend on the batch's length):
@@ -41,6 +43,8 @@
 #include "uniasr.h"
 #include "lcbnet.h"
 #include "ebranchformer.h"
+#include "cif.h"
+#include "pif.h"
 
 using namespace pf;
 
@@ -634,6 +638,50 @@ struct Td : Stepper<pf_tdecoder_config> {
 
 std::string dl(int i) { return "decoders." + std::to_string(i) + "."; }
 
+// ================================================================================================ E-Paraformer: PIF predictor, SAN decoder
+// funasr/models/e_paraformer. The predictor (pf_pif_*, kernels in pif.hip) is two calls around ONE host read of the B token sums, as
+// the CIF predictor's: alphas() -> the caller rounds the sums (half to even) -> embeds() with the counts. Exact fp32 in every mode.
+struct Pif {
+    pf_pif_config cfg;
+    TensorTable tt;
+    DevBuf lens, counts;
+};
+
+// The decoder (pf_sandecoder_*; ParaformerSANDecoder.forward, decoder.py:1201-1251) runs ONCE over all B x L token rows: the rows are
+// the predictor's embeddings (no lookup, no positional row), per layer `decoders.i.`
+//   x += linear_out(attention(norm1 x))                  keys at or past the clip's token count masked, NOT causal (launch_tf_attention)
+//   x += linear_out(attention(norm2 x, memory))          keys at or past the clip's encoder length masked (launch_tf_cross_attention)
+//   x += w_2(relu(w_1(norm3 x)))
+// then after_norm, output_layer, log-softmax, row arg-max. It is the LCB-Net fusion layer's block n_blocks times on the same base.
+// Launches per forward: 18 per layer (3 LayerNorms, 10 GEMMs, 2 attentions, ReLU; K and V of the memory are two GEMMs into one
+// [B T, 2 D] buffer) + 5 (after_norm, output_layer, log-softmax, arg-max, its log-probability).
+// precision 3: from two-plane fp16 operands run the GEMMs whose operand has an a-priori bound -- self_attn q / k / v (norm1's
+// LayerNorm bound), self_attn.linear_out (the row-L1 bound of linear_v: the attention output is a convex combination of value rows,
+// or zero), src_attn.linear_q (norm2's bound), w_1 (norm3's bound) and w_2 (the row-L1 bound of w_1; ReLU does not enlarge it).
+// Exact fp32 in both modes: src_attn.linear_k / linear_v (their operand is the CALLER's memory, for which no bound exists inside this
+// handle), src_attn.linear_out (its operand is bounded only through that memory) and output_layer (V = 4234 is no multiple of 4, and
+// the arg-max of its rows is the result).
+struct SdBlockX { int e_sa_in = 0, e_sa = 0, e_ca_in = 0, e_ff_in = 0, e_ff_h = 0; };
+
+struct Sd : SubEnc<LcbCfg> {
+    std::vector<SdBlockX> bx;
+    DevBuf kv, mlens, logits;
+    int prepare(hipStream_t ps) {
+        const int D = cfg.d_model;
+        bx.assign(cfg.n_blocks, SdBlockX());
+        for (int i = 0; i < cfg.n_blocks && cfg.precision == 3; ++i) {
+            const std::string p = dl(i);
+            SdBlockX& x = bx[i];
+            int unused;
+            if (ln_lin_exps(p + "norm1.", p + "self_attn.linear_v.", D, &x.e_sa_in, &x.e_sa, ps)) return -2;
+            if (ln_lin_exps(p + "norm2.", p + "src_attn.linear_q.", D, &x.e_ca_in, &unused, ps)) return -2;
+            if (ln_lin_exps(p + "norm3.", p + "feed_forward.w_1.", cfg.ffn_dim, &x.e_ff_in, &x.e_ff_h, ps)) return -2;
+        }
+        prepared = tt.version;
+        return 0;
+    }
+};
+
 // ================================================================================================ SAN-M (FsmnDecoder) step
 // One layer table for the three groups of the reference's module: `decoders` (FFN, FSMN memory, cross-attention), `decoders2` (FFN,
 // FSMN memory) and the one FFN-only layer of `decoders3`.
@@ -1214,7 +1262,158 @@ int pf_fusion_forward(pf_fusion* hh, const float* x_in, const int32_t* x_lens_ho
     return launch_gemm_f32(g, s);
 }
 
+// ---- E-Paraformer (funasr/models/e_paraformer): the PIF predictor's two calls and the one-pass SAN decoder
+pf_pif* pf_pif_create(const pf_pif_config* cfg) {
+    if (!cfg) { set_error("pif: null config"); return nullptr; }
+    const pf_pif_config& c = *cfg;
+    if (!(c.d_model > 0 && c.d_model <= PIF_MAX_D && c.sigma_heads >= 1 && c.sigma_heads <= PIF_MAX_HEADS && c.d_model % c.sigma_heads == 0 &&
+          (c.d_model / c.sigma_heads) % 32 == 0 && c.l_order >= 0 && c.l_order <= PIF_MAX_ORDER && c.r_order >= 0 && c.r_order <= PIF_MAX_ORDER)) {
+        set_error("pif: unsupported config (d_model <= 1024, 1 .. 8 sigma heads of a multiple of 32 channels, l_order / r_order 0 .. 15)");
+        return nullptr;
+    }
+    if (check_device()) return nullptr;
+    std::unique_ptr<Pif> h(new Pif());
+    h->cfg = c;
+    TensorTable& tt = h->tt;
+    int rc = 0;
+    rc |= tt.add_linear("cif_conv1d.", c.d_model, c.l_order + c.r_order + 1);
+    rc |= tt.add_linear("cif_output.", 1, c.d_model);
+    rc |= tt.add("sigma", c.sigma_heads);
+    rc |= tt.add("bias", c.sigma_heads);                 // constant over the frames: it cancels in the softmax and is never read
+    if (rc) return nullptr;
+    return reinterpret_cast<pf_pif*>(h.release());
+}
+void pf_pif_destroy(pf_pif* h) { delete reinterpret_cast<Pif*>(h); }
+int pf_pif_set_tensor(pf_pif* h, const char* name, const float* data, int64_t numel) {
+    return table_set(reinterpret_cast<Pif*>(h), "pif_set_tensor: null", name, data, numel);
+}
+int pf_pif_missing(const pf_pif* h) { return table_missing(reinterpret_cast<const Pif*>(h)); }
+static int pif_lens(Pif* h, const char* who, const int32_t* lens_host, int B, int T, hipStream_t s) {
+    PF_REQUIRE(B > 0 && B <= 65535 && T > 0 && T <= PIF_MAX_T, std::string(who) + ": 1 .. 65535 clips of 1 .. 5000 frames");
+    for (int b = 0; b < B; ++b) PF_REQUIRE(lens_host[b] >= 0 && lens_host[b] <= T, std::string(who) + ": a length exceeds the padded length");
+    if (h->tt.require_all("pif")) return -3;
+    return upload_lens(h->lens, lens_host, B, s) ? -2 : 0;
+}
+int pf_pif_alphas(pf_pif* hh, const float* x, const int32_t* lens_host, int32_t B, int32_t T, float* alphas, float* token_num, void* stream) {
+    Pif* h = reinterpret_cast<Pif*>(hh);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    PF_REQUIRE(h && x && lens_host && alphas && token_num, "pif_alphas: null argument");
+    if (int rc = pif_lens(h, "pif_alphas", lens_host, B, T, s)) return rc;
+    const pf_pif_config& c = h->cfg;
+    return launch_pif_alphas(x, h->tt.get("cif_conv1d.weight"), h->tt.get("cif_conv1d.bias"), h->tt.get("cif_output.weight"),
+                             h->tt.get("cif_output.bias"), h->lens.as<int>(), B, T, c.d_model, c.l_order, c.r_order, c.smooth_factor,
+                             c.noise_threshold, alphas, token_num, s);
+}
+int pf_pif_embeds(pf_pif* hh, const float* x, float* alphas, const float* token_num, const int32_t* counts_host, const int32_t* lens_host,
+                  int32_t B, int32_t T, int32_t Lmax, float* align, float* embeds, void* stream) {
+    Pif* h = reinterpret_cast<Pif*>(hh);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    PF_REQUIRE(h && x && alphas && token_num && counts_host && lens_host && align && embeds, "pif_embeds: null argument");
+    PF_REQUIRE(Lmax >= 1 && Lmax <= PIF_MAX_L, "pif_embeds: 1 .. 2048 fire positions");
+    if (int rc = pif_lens(h, "pif_embeds", lens_host, B, T, s)) return rc;
+    for (int b = 0; b < B; ++b) PF_REQUIRE(counts_host[b] >= 0 && counts_host[b] <= Lmax, "pif_embeds: a token count outside 0 .. Lmax");
+    if (upload_lens(h->counts, counts_host, B, s)) return -2;
+    int rc;
+    if ((rc = launch_pif_align(alphas, token_num, h->counts.as<int>(), B, T, alphas, align, s))) return rc;
+    return launch_pif_embed(align, x, h->tt.get("sigma"), h->lens.as<int>(), B, T, Lmax, h->cfg.d_model, h->cfg.sigma_heads, embeds, s);
+}
+
+pf_sandecoder* pf_sandecoder_create(const pf_sandecoder_config* cfg) {
+    if (!cfg) { set_error("sandecoder: null config"); return nullptr; }
+    if (!(cfg->vocab_size > 0 && cfg->n_blocks >= 1 && (cfg->precision == 0 || cfg->precision == 3) &&
+          lcb_shape_ok(cfg->d_model, cfg->n_heads, cfg->ffn_dim, cfg->ln_eps))) {
+        set_error("sandecoder: unsupported config (vocab_size > 0, head dim 64, d_model <= 2048, ffn_dim % 32, precision 0 or 3)");
+        return nullptr;
+    }
+    if (check_device()) return nullptr;
+    std::unique_ptr<Sd> h(new Sd());
+    LcbCfg& c = h->cfg;
+    c.vocab_size = cfg->vocab_size; c.d_model = cfg->d_model; c.n_heads = cfg->n_heads; c.ffn_dim = cfg->ffn_dim; c.n_blocks = cfg->n_blocks;
+    c.precision = cfg->precision; c.ln_eps = cfg->ln_eps;
+    TensorTable& tt = h->tt;
+    int rc = 0;
+    for (int i = 0; i < c.n_blocks; ++i) rc |= add_tf_block(tt, dl(i), {"self_attn.", "src_attn."}, {"norm1.", "norm2.", "norm3."}, c.d_model, c.ffn_dim);
+    rc |= tt.add_linear("after_norm.", c.d_model, 1);
+    rc |= tt.add_linear("output_layer.", c.vocab_size, c.d_model);
+    if (rc) return nullptr;
+    return reinterpret_cast<pf_sandecoder*>(h.release());
+}
+void pf_sandecoder_destroy(pf_sandecoder* h) { delete reinterpret_cast<Sd*>(h); }
+int pf_sandecoder_set_tensor(pf_sandecoder* h, const char* name, const float* data, int64_t numel) {
+    return table_set(reinterpret_cast<Sd*>(h), "sandecoder_set_tensor: null", name, data, numel);
+}
+int pf_sandecoder_missing(const pf_sandecoder* h) { return table_missing(reinterpret_cast<const Sd*>(h)); }
+int pf_sandecoder_set_precision(pf_sandecoder* h, int32_t precision) { return enc_set_precision(reinterpret_cast<Sd*>(h), "sandecoder", precision); }
+int pf_sandecoder_forward(pf_sandecoder* hh, const float* memory, const int32_t* mem_lens_host, const float* embeds, const int32_t* tok_lens_host,
+                          int32_t B, int32_t T, int32_t L, float* logp, int32_t* ids, float* best, void* stream) {
+    Sd* h = reinterpret_cast<Sd*>(hh);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    PF_REQUIRE(h && memory && mem_lens_host && embeds && tok_lens_host && ids && best && B > 0 && B <= 65535,
+               "sandecoder_forward: null/empty argument");
+    PF_REQUIRE(T >= 1 && T <= 12000 && L >= 1 && L <= PIF_MAX_L, "sandecoder_forward: 1 .. 12000 memory rows, 1 .. 2048 token rows");
+    PF_REQUIRE(((uintptr_t)memory & 15) == 0 && ((uintptr_t)embeds & 15) == 0, "sandecoder_forward: 16-B alignment");
+    for (int b = 0; b < B; ++b)
+        PF_REQUIRE(mem_lens_host[b] >= 0 && mem_lens_host[b] <= T && tok_lens_host[b] >= 0 && tok_lens_host[b] <= L,
+                   "sandecoder_forward: a length exceeds the padded length");
+    const LcbCfg& c = h->cfg;
+    const int D = c.d_model, FF = c.ffn_dim, V = c.vocab_size;
+    int rc;
+    if ((rc = h->tt.require_all("sandecoder"))) return rc;
+    if (h->prepared != h->tt.version && (rc = h->prepare(s))) return rc;
+    if ((rc = h->rows(B, L, FF, tok_lens_host, s))) return rc;
+    const size_t M = (size_t)h->Mi;
+    if (h->kv.ensure(sizeof(float) * (size_t)B * T * 2 * D) || h->logits.ensure(sizeof(float) * M * V) || upload_lens(h->mlens, mem_lens_host, B, s))
+        return -2;
+    float *bufs[2] = {h->xa.as<float>(), h->xb.as<float>()}, *xn = h->xn.as<float>(), *q = h->qkv.as<float>(), *att = h->att.as<float>(),
+          *hid = h->hid.as<float>(), *kv = h->kv.as<float>();
+    const float* x = embeds;                       // the rows of the block in flight: the caller's, then the two buffers in turn
+    int cur = 0;
+    for (int i = 0; i < c.n_blocks; ++i) {
+        const std::string p = dl(i);
+        const SdBlockX& e = h->bx[i];
+        if ((rc = h->ln(p + "norm1.", x, xn))) return rc;
+        const char* names[3] = {"self_attn.linear_q.", "self_attn.linear_k.", "self_attn.linear_v."};
+        for (int j = 0; j < 3; ++j)
+            if ((rc = h->lin(xn, D, p + names[j], D, nullptr, q + (size_t)j * D, 3 * D, e.e_sa_in))) return rc;
+        if ((rc = launch_tf_attention(q, h->klens.as<int>(), B, L, c.n_heads, att, s))) return rc;     // no key of a clip without tokens: zeros
+        if ((rc = h->lin(att, D, p + "self_attn.linear_out.", D, x, bufs[cur], D, e.e_sa))) return rc;
+        x = bufs[cur]; cur ^= 1;
+        if ((rc = h->ln(p + "norm2.", x, xn))) return rc;
+        if ((rc = h->lin(xn, D, p + "src_attn.linear_q.", D, nullptr, q, D, e.e_ca_in))) return rc;
+        if ((rc = h->gm(false, memory, B * T, D, p + "src_attn.linear_k.weight", h->tt.get(p + "src_attn.linear_k.bias"), D, nullptr, kv, 2 * D, 0))) return rc;
+        if ((rc = h->gm(false, memory, B * T, D, p + "src_attn.linear_v.weight", h->tt.get(p + "src_attn.linear_v.bias"), D, nullptr, kv + D, 2 * D, 0))) return rc;
+        if ((rc = launch_tf_cross_attention(q, D, kv, h->mlens.as<int>(), B, L, T, c.n_heads, att, s))) return rc;
+        if ((rc = h->gm(false, att, h->Mi, D, p + "src_attn.linear_out.weight", h->tt.get(p + "src_attn.linear_out.bias"), D, x, bufs[cur], D, 0))) return rc;
+        x = bufs[cur]; cur ^= 1;
+        if ((rc = h->ln(p + "norm3.", x, xn))) return rc;
+        if ((rc = h->lin(xn, D, p + "feed_forward.w_1.", FF, nullptr, hid, FF, e.e_ff_in))) return rc;
+        if ((rc = launch_cf_act(hid, M * FF, 0, s))) return rc;
+        if ((rc = h->lin(hid, FF, p + "feed_forward.w_2.", D, x, bufs[cur], D, e.e_ff_h))) return rc;
+        x = bufs[cur]; cur ^= 1;
+    }
+    if ((rc = h->ln("after_norm.", x, xn))) return rc;
+    float* logits = h->logits.as<float>();
+    if ((rc = h->gm(false, xn, h->Mi, D, "output_layer.weight", h->tt.get("output_layer.bias"), V, nullptr, logits, V, 0))) return rc;
+    float* lp = logp ? logp : logits;
+    if ((rc = launch_log_softmax(logits, V, lp, V, h->Mi, V, s))) return rc;
+    if ((rc = launch_argmax_rows(lp, V, h->Mi, V, ids, s))) return rc;
+    return launch_pif_gather_best(lp, V, ids, h->Mi, best, s);
+}
+
 // single-kernel hooks (tests)
+int pf_k_pif_alphas(const float* h, const float* conv_w, const float* conv_b, const float* out_w, const float* out_b, const int32_t* lens_dev,
+                    int32_t B, int32_t T, int32_t D, int32_t l_order, int32_t r_order, float smooth, float noise, float* a, float* token_num,
+                    void* stream) {
+    return launch_pif_alphas(h, conv_w, conv_b, out_w, out_b, lens_dev, B, T, D, l_order, r_order, smooth, noise, a, token_num,
+                             reinterpret_cast<hipStream_t>(stream));
+}
+int pf_k_pif_align(const float* a, const float* token_num, const int32_t* n_dev, int32_t B, int32_t T, float* an, float* align, void* stream) {
+    return launch_pif_align(a, token_num, n_dev, B, T, an, align, reinterpret_cast<hipStream_t>(stream));
+}
+int pf_k_pif_embed(const float* align, const float* h, const float* sigma, const int32_t* lens_dev, int32_t B, int32_t T, int32_t L, int32_t D,
+                   int32_t H, float* embeds, void* stream) {
+    return launch_pif_embed(align, h, sigma, lens_dev, B, T, L, D, H, embeds, reinterpret_cast<hipStream_t>(stream));
+}
 int pf_k_fsmn_step(const float* t, const float* x, const float* g2, const float* b2, const float* w, const float* win_in, float* win_out,
                    const int32_t* parents_dev, int32_t pos, int32_t n, int32_t D, int32_t K, int32_t left_pad, const float* g3, const float* b3,
                    float eps, float* x_out, float* xn_out, void* stream) {

@@ -436,6 +436,43 @@ def ebranchformer_state_dict(seed: int, model) -> Dict[str, torch.Tensor]:
     return conformer_state_dict(seed, model)
 
 
+def eparaformer_conf(output_size: int = 128, attention_heads: int = 2, linear_units: int = 256, enc_blocks: int = 2, dec_blocks: int = 2,
+                     kernel: int = 15, l_order: int = 1, r_order: int = 1, sigma_heads: int = 4, vocab: int = 40, input_size: int = 80,
+                     ctc_weight: float = 0.0) -> dict:
+    """constructor arguments of an E-Paraformer model (the layout of examples/aishell/e_paraformer/conf/
+    e_paraformer_conformer_12e_6d_2048_256.yaml) at a chosen size"""
+    c = conformer_conf(output_size=output_size, attention_heads=attention_heads, linear_units=linear_units, enc_blocks=enc_blocks,
+                       dec_blocks=dec_blocks, kernel=kernel, macaron=True, vocab=vocab, input_size=input_size)
+    pred = {"idim": output_size, "threshold": 1.0, "l_order": l_order, "r_order": r_order, "sigma": 0.5, "bias": 0.0, "sigma_heads": sigma_heads}
+    return {"encoder": "ConformerEncoder", "encoder_conf": c["encoder_conf"], "decoder": "ParaformerSANDecoder", "decoder_conf": c["decoder_conf"],
+            "predictor": "PifPredictor", "predictor_conf": pred, "ctc_weight": ctc_weight, "lsm_weight": 0.1, "length_normalized_loss": False,
+            "predictor_weight": 1.0, "predictor_bias": 2, "sampling_ratio": 0.4, "use_1st_decoder_loss": True, "input_size": input_size,
+            "vocab_size": vocab}
+
+
+# examples/aishell/e_paraformer/conf/e_paraformer_conformer_12e_6d_2048_256.yaml
+EPARAFORMER_TEMPLATE = dict(output_size=256, attention_heads=4, linear_units=2048, enc_blocks=12, dec_blocks=6, kernel=15, l_order=1, r_order=1,
+                            sigma_heads=4, vocab=4234)
+
+
+def eparaformer_state_dict(seed: int, model, cif_bias: float = -1.0) -> Dict[str, torch.Tensor]:
+    """synthetic weights in the layout of `model` (an EParaformer module or the reference's), drawn as conformer_state_dict draws them,
+    then the predictor's own: a DISTINCT sigma per head (0.6 .. 1.8: the heads must not be interchangeable), a small distinct bias per
+    head (it cancels in the softmax; a result that moved with it would show), and a negative `cif_output.bias` so that the alphas sum
+    to a fraction of the frame count (about a token per four frames). The decoder's attention output projections are drawn at 0.3 of
+    the fan-in scale: untrained attention is near uniform, its output the same at every token position, and at full scale that common
+    part drowns what tells the positions apart"""
+    sd = conformer_state_dict(seed, model)
+    for k in sd:
+        if k.startswith("decoder.decoders.") and "_attn.linear_out." in k:
+            sd[k] = sd[k] * 0.3
+    H = sd["predictor.sigma"].numel()
+    sd["predictor.sigma"] = torch.linspace(0.6, 1.8, H) if H > 1 else torch.tensor([0.9])
+    sd["predictor.bias"] = 0.25 * torch.arange(H, dtype=torch.float32) - 0.3
+    sd["predictor.cif_output.bias"] = torch.full_like(sd["predictor.cif_output.bias"], cif_bias)
+    return sd
+
+
 def lcbnet_conf(output_size: int = 128, attention_heads: int = 2, linear_units: int = 256, enc_blocks: int = 2, dec_blocks: int = 2,
                 text_blocks: int = 2, vocab: int = 300, input_size: int = 80) -> dict:
     """constructor arguments of an LCBNet model at a chosen size: transformer_conf plus the text encoder, the one fusion layer and the

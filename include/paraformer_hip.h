@@ -760,6 +760,72 @@ int pf_k_tf_cross_attention(const float* q_dev, int32_t ldq, const float* kv_dev
 int pf_k_text_embed_rows(const float* table_dev, const int32_t* ids_dev, const float* pe_dev, int32_t B, int32_t L, int32_t D, float scale,
                          float* y_dev, void* stream);
 
+/* ---- E-Paraformer (funasr/models/e_paraformer): the parallel integrate-and-fire predictor and the one-pass SAN decoder. The encoder
+ * is pf_conformer.
+ * pf_pif: PifPredictor.forward (pif_predictor.py:84-130), inference path. Tensor names are the reference's keys below `predictor.`:
+ * "cif_conv1d.weight" [D, 1, l_order + r_order + 1], "cif_conv1d.bias" [D], "cif_output.weight" [1, D], "cif_output.bias" [1], "sigma"
+ * [sigma_heads], "bias" [sigma_heads] (constant over the frames: it cancels in the softmax and is never read). Exact fp32 in every
+ * mode, fixed summation orders, no atomics. Two calls around ONE host read of the B token sums:
+ *   pf_pif_alphas: x_dev [B, T, D] rows of the padded batch, lens_host [B] -> alphas_dev [B, T] (exactly 0 at t >= lens[b]) and
+ *     token_num_dev [B], their sums. The depthwise conv is not masked (the reference's is not): it reads the clip's own padded rows and
+ *     zeros outside [0, T), never another clip's.
+ *   the caller rounds the sums half to even (on the fp32 value) -> counts_host [B], Lmax = their maximum (>= 1; a batch without any
+ *     token needs no second call)
+ *   pf_pif_embeds: alphas_dev is normalised IN PLACE by counts[b] / token_num[b] (all zero for a clip with a zero sum or count: no
+ *     division), align_dev [B, T] receives its inclusive prefix sums, embeds_dev [B, Lmax, D] the Gaussian-kernel attention from the
+ *     fire positions l + 0.5 to the frames t < lens[b], per sigma head over its D / sigma_heads channels. Every clip gets all Lmax rows
+ *     (rows at or past its own count are the reference's too); a clip with lens[b] == 0 gets zero rows; rows of x_dev at or past
+ *     lens[b] are not read.
+ * Limits: D <= 1024, 1 .. 8 sigma heads with D / sigma_heads a multiple of 32, l_order / r_order 0 .. 15, T <= 5000, Lmax <= 2048. No sync. */
+typedef struct pf_pif pf_pif;
+typedef struct pf_pif_config {
+    int32_t d_model, l_order, r_order, sigma_heads;
+    float threshold;              /* carried for the record: the inference path does not read it */
+    float smooth_factor, noise_threshold;
+} pf_pif_config;
+pf_pif* pf_pif_create(const pf_pif_config* cfg);
+void pf_pif_destroy(pf_pif* h);
+int pf_pif_set_tensor(pf_pif* h, const char* name, const float* data, int64_t numel);
+int pf_pif_missing(const pf_pif* h);
+int pf_pif_alphas(pf_pif* h, const float* x_dev, const int32_t* lens_host, int32_t B, int32_t T, float* alphas_dev, float* token_num_dev,
+                  void* stream);
+int pf_pif_embeds(pf_pif* h, const float* x_dev, float* alphas_dev, const float* token_num_dev, const int32_t* counts_host,
+                  const int32_t* lens_host, int32_t B, int32_t T, int32_t Lmax, float* align_dev, float* embeds_dev, void* stream);
+/* pf_sandecoder: ParaformerSANDecoder.forward (decoder.py:1201-1251) + log-softmax + row arg-max, ONE pass over all B x L token rows:
+ * the rows are the predictor's embeddings (no lookup, no positional row); per layer x += self_attn(norm1 x) (keys at or past the
+ * clip's token count masked, not causal), x += src_attn(norm2 x, memory) (keys at or past the clip's encoder length masked),
+ * x += w_2(relu(w_1(norm3 x))); then after_norm, output_layer. Tensor names: the reference's keys below `decoder.` without the unused
+ * `embed.*` ("decoders.0.self_attn.linear_q.weight", "decoders.0.src_attn.linear_k.bias", "decoders.0.feed_forward.w_1.weight",
+ * "decoders.0.norm3.weight", "after_norm.bias", "output_layer.weight", ...). Head dim 64, ffn_dim % 32.
+ * precision 3 runs self_attn q / k / v / linear_out, src_attn.linear_q, w_1 and w_2 from two-plane fp16 operands at a-priori
+ * exponents; src_attn.linear_k / linear_v / linear_out (no bound on the caller's memory) and output_layer stay exact fp32.
+ * memory_dev [B, T, D], embeds_dev [B, L, D] -> logp_dev [B, L, V] (log-softmax; may be NULL), ids_dev / best_dev [B, L]: each row's
+ * arg-max (first maximum) and its log-probability. A clip with tok_lens_host[b] == 0 has no self-attention key: its attention output
+ * is zero, its rows stay finite and no other clip reads them. 1 <= T <= 12000, 1 <= L <= 2048. No sync. */
+typedef struct pf_sandecoder pf_sandecoder;
+typedef struct pf_sandecoder_config {
+    int32_t d_model, n_heads, ffn_dim, n_blocks, vocab_size;
+    int32_t precision;            /* 0 fp32, 3 f16x2 */
+    float ln_eps;
+} pf_sandecoder_config;
+pf_sandecoder* pf_sandecoder_create(const pf_sandecoder_config* cfg);
+void pf_sandecoder_destroy(pf_sandecoder* h);
+int pf_sandecoder_set_tensor(pf_sandecoder* h, const char* name, const float* data, int64_t numel);
+int pf_sandecoder_missing(const pf_sandecoder* h);
+int pf_sandecoder_set_precision(pf_sandecoder* h, int32_t precision);
+int pf_sandecoder_forward(pf_sandecoder* h, const float* memory_dev, const int32_t* mem_lens_host, const float* embeds_dev,
+                          const int32_t* tok_lens_host, int32_t B, int32_t T, int32_t L, float* logp_dev, int32_t* ids_dev, float* best_dev,
+                          void* stream);
+/* single-kernel hooks (tests) of the predictor: the alphas and their per-clip sums (lens_dev [B] on the device); the normalisation +
+ * prefix sum (n_dev [B] counts; an_dev may be a_dev); the embeddings. Out-of-range arguments return an error and launch nothing. */
+int pf_k_pif_alphas(const float* h_dev, const float* conv_w_dev, const float* conv_b_dev, const float* out_w_dev, const float* out_b_dev,
+                    const int32_t* lens_dev, int32_t B, int32_t T, int32_t D, int32_t l_order, int32_t r_order, float smooth, float noise,
+                    float* a_dev, float* token_num_dev, void* stream);
+int pf_k_pif_align(const float* a_dev, const float* token_num_dev, const int32_t* n_dev, int32_t B, int32_t T, float* an_dev, float* align_dev,
+                   void* stream);
+int pf_k_pif_embed(const float* align_dev, const float* h_dev, const float* sigma_dev, const int32_t* lens_dev, int32_t B, int32_t T, int32_t L,
+                   int32_t D, int32_t H, float* embeds_dev, void* stream);
+
 /* ---- Transducer (RNN-T) search (funasr/models/transducer: RNNTDecoder + JointNetwork + BeamSearchTransducer.default_beam_search,
  * the one decoding path the reference's Transducer builds: one utterance, is_final, no LM, no length normalisation). One handle
  * holds the prediction network (embedding, n_layers LSTM cells) and the joint network; the search loop runs on the host side of the
