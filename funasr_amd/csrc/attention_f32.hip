@@ -47,6 +47,7 @@ __global__ __launch_bounds__(256, 2) void attention_f32_kernel(AttnArgs p) {
     const float* kbase2 = p.K2 ? p.K2 + (size_t)b * p.T2 * p.ldk2 + head * DK + lc4 * 4 : nullptr;
     const float* vbase2 = p.K2 ? p.V2 + (size_t)b * p.T2 * p.ldv2 + head * DK + lc4 * 4 : nullptr;
 
+    // klen < 1 (an empty key sequence): ntiles <= 0, no K / V row is read and tile_store writes zero rows (l_run == 0)
     const int ntiles = (klen + KT - 1) / KT;
     for (int kt = 0; kt < ntiles; ++kt) {
         const int k0 = kt * KT;
@@ -108,6 +109,13 @@ __global__ __launch_bounds__(256, 2) void attention_f32_dma_kernel(AttnArgs p) {
     floatx16 o[4];
     tile_zero(o);
     float m_run = -INFINITY, l_run = 0.f;
+
+    // an empty key sequence (klen is uniform over the workgroup; no barrier and no DMA has been issued yet): the rows are zero, as
+    // the reference's masked_fill(0) after the softmax leaves them. stage() below clamps to key klen - 1 and must not run then
+    if (klen < 1) {
+        if (q < p.Tq) tile_store(o, 0.f, hh, ((size_t)b * p.Tq + q) * p.ldo + head * DK, p.O, p.O3, p.o_plane);
+        return;
+    }
 
     // DMA pieces: a piece = 2 keys x 512 B; wave w stages pieces 4w .. 4w+3 of both tiles
     const float* kbase = p.K + (size_t)b * p.Tk * p.ldk + head * DK;
@@ -325,12 +333,14 @@ __global__ __launch_bounds__(256) void attention_f32_fewq_kernel(AttnArgs p) {
         float l = 0.f, acc[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int w = 0; w < 4; ++w) {                     // fixed order; a wave without keys has m = -inf, weight 0
-            const float wgt = expf(red_m[w][qq] - m);
+            // (selected, not computed: with an empty key sequence every wave has m = -inf and expf(-inf - -inf) is NaN)
+            const float wgt = red_m[w][qq] > -INFINITY ? expf(red_m[w][qq] - m) : 0.f;
             l += red_l[w][qq] * wgt;
 #pragma unroll
             for (int u = 0; u < 4; ++u) acc[u] += red_o[w][qq][d + u] * wgt;
         }
-        const float o[4] = {acc[0] / l, acc[1] / l, acc[2] / l, acc[3] / l};
+        // l == 0: no wave had a key; the row is zero (masked_fill(0) after the softmax), through O and O2 alike
+        const float o[4] = {l > 0.f ? acc[0] / l : 0.f, l > 0.f ? acc[1] / l : 0.f, l > 0.f ? acc[2] / l : 0.f, l > 0.f ? acc[3] / l : 0.f};
         const size_t row = (size_t)b * p.Tq + q0 + qq;
         if (p.O2) store_split2x4(p.O2 + row * p.ldo2 + head * DK + d, p.o2_plane, o, p.o2_scale);
         else *reinterpret_cast<float4*>(p.O + row * p.ldo + head * DK + d) = make_float4(o[0], o[1], o[2], o[3]);

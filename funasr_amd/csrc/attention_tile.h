@@ -109,7 +109,9 @@ template <int ND, int CH = 32 * ND>
 __device__ __forceinline__ void tile_store(const floatx16 (&o)[ND], float l_run, int hh, size_t orow, float* O, unsigned short* O3,
                                            size_t o_plane) {
     static_assert(CH % 8 == 0 && CH <= 32 * ND, "tile_store: the channel bound is a multiple of 8");
-    const float inv = 1.0f / l_run;
+    // l_run == 0: no tile was taken (an empty key sequence); o is still zero and the row is stored as zeros, the reference's
+    // masked_fill(0) after the softmax. For l_run > 0 the quotient is the one it always was
+    const float inv = l_run > 0.f ? 1.0f / l_run : 0.f;
 #pragma unroll
     for (int d = 0; d < ND; ++d)
 #pragma unroll

@@ -73,9 +73,11 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
-// fp32 -> bf16, round to nearest even (finite inputs)
+// fp32 -> bf16, round to nearest even: the largest finite values round to inf, +-inf stays inf. A NaN stays a NaN of the same sign
+// with the quiet bit set (the rounding add would carry a payload in the low mantissa bits into inf, or wrap 0x7fffffff to -0)
 __device__ __forceinline__ unsigned short f32_to_bf16(float f) {
     unsigned int u = __builtin_bit_cast(unsigned int, f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x0040u);
     u += 0x7fffu + ((u >> 16) & 1u);
     return (unsigned short)(u >> 16);
 }
@@ -472,7 +474,15 @@ struct AttnArgs {
     const float* K; int ldk;      // row (b*Tk + t)
     const float* V; int ldv;
     float* O;       int ldo;
-    const int* klens;             // device int32 [B] valid keys per sequence (>= 1); unused with a second source
+    const int* klens;             // device int32 [B] valid keys per sequence; unused with a second source
+    // An EMPTY key sequence (klens[b] < 1), per source file. Zero rows, the reference's masked_fill(0) after the softmax, and no K / V row
+    // read: attention_f32.hip (all three kernels, fp32 and plane outputs; with a second source klen = n1 + n2 >= 1 always),
+    // attention_relpos.hip, attention_abs.hip, lcbnet.hip (each tests klen < 1 first). attention_mid.hip does the same but keeps
+    // klens >= 1 as its contract. The rest REQUIRE klens[b] >= 1 and their callers guarantee it -- pf_encoder_forward and its kin
+    // refuse lens < 1, pf_decoder_forward refuses memory lens < 1, and the pf_k_* hooks pass the caller's lengths on unchecked:
+    // attention_split3.hip stages tile 0 before its loop with the key row clamped to klen - 1 = -1 (a read in front of the
+    // sequence's first row); attention_bf16.hip and attention_small.hip read nothing and store 0 * inf = NaN rows; attention_f16x2.hip
+    // takes klens in 1 .. Tp (Attn2Args::klens). attention_alibi.hip has packed rows: a sequence of no rows has no query either.
     int B, H, Tq, Tk;
     float scale;
     // optional second key/value source (streaming): keys [0, n1[b]) come from (K, V), the next n2 from (K2, V2)

@@ -1119,6 +1119,15 @@ int pf_k_layernorm(const float* x, int32_t ldx, const float* gamma, const float*
                    int32_t M, int32_t D, int32_t Dpad, float eps, void* stream);
 int pf_k_fsmn(const float* in, int32_t ldin, const float* w, const float* R, int32_t ldr, float* out, int32_t ldo,
               const int32_t* lens_dev, int32_t B, int32_t T, int32_t C, int32_t K, int32_t left_pad, void* stream);
+/* The attention hooks and an EMPTY key sequence (klens_dev[b] < 1); none of them checks the device-side lengths.
+ * pf_k_attention_f32 (attention_f32.hip: the LDS-DMA, the register-staged and the few-query kernel) writes zero rows for that
+ * sequence, as the reference's masked_fill(0) after the softmax does, and reads none of its K / V rows; the other sequences of the
+ * batch are unaffected. pf_k_attention_f32_two_source always has n2 >= 1 keys. pf_k_attention_f32_dk (attention_mid.hip) also
+ * writes zero rows, outside its stated contract. The Conformer / Transformer / LCB-Net attentions (attention_relpos.hip,
+ * attention_abs.hip, lcbnet.hip) write zero rows. Every other hook REQUIRES klens_dev[b] >= 1 and the caller has to guarantee it, as
+ * pf_encoder_forward, pf_decoder_forward and their kin do by refusing lens < 1: pf_k_attention_split3 would read the K / V row in
+ * front of the sequence's first one, pf_k_attention_bf16 and pf_k_attention_small would store NaN rows, pf_k_attention_f16x2 takes
+ * klens in 1 .. Tp. emotion2vec's ALiBi attention works on packed rows, where a sequence without rows has no query either. */
 int pf_k_attention_f32(const float* Q, int32_t ldq, const float* K, int32_t ldk, const float* V, int32_t ldv,
                        float* O, int32_t ldo, const int32_t* klens_dev, int32_t B, int32_t H, int32_t Tq,
                        int32_t Tk, float scale, void* stream);
