@@ -82,6 +82,10 @@ class pf_campplus_config(C.Structure):
                [("bn_eps", C.c_float)]
 
 
+class pf_eres2net_config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("feat_dim", "embedding_size", "m_channels")] + [("num_blocks", C.c_int32 * 4), ("bn_eps", C.c_float)]
+
+
 class pf_emotion2vec_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("embed_dim", "num_heads", "ffn_dim", "prenet_depth", "depth", "num_extra_tokens",
                                           "num_alibi_heads", "alibi_scale_layers", "alibi_scale_heads", "n_conv")] + \
@@ -228,6 +232,19 @@ SIGNATURES = {
     "pf_campplus_set_max_batch": (C.c_int, [_vp, _i32]),
     "pf_campplus_forward": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "pf_campplus_embed_chunks": (C.c_int, [_vp, _vp, _i64, C.POINTER(C.c_int64), _pi32, _i32, _i32, _vp, _vp]),
+    "pf_eres2net_create": (_vp, [C.POINTER(pf_eres2net_config)]),
+    "pf_eres2net_destroy": (None, [_vp]),
+    "pf_eres2net_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),
+    "pf_eres2net_missing": (C.c_int, [_vp]),
+    "pf_eres2net_set_max_batch": (C.c_int, [_vp, _i32]),
+    "pf_eres2net_workspace_bytes": (_i64, [_vp, _i32]),
+    "pf_eres2net_debug_poison": (C.c_int, [_vp]),
+    "pf_eres2net_forward": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
+    "pf_eres2net_forward_stages": (C.c_int, [_vp, _vp, _i32, _i32, _vp, C.POINTER(C.c_void_p), _vp]),
+    "pf_eres2net_embed_chunks": (C.c_int, [_vp, _vp, _i64, C.POINTER(C.c_int64), _pi32, _i32, _i32, _vp, _vp]),
+    "pf_k_eres_conv": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp,
+                                 _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "pf_k_eres_conv_vs_cam_time": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_float), _vp]),
     "pf_emotion2vec_create": (_vp, [C.POINTER(pf_emotion2vec_config)]),
     "pf_emotion2vec_destroy": (None, [_vp]),
     "pf_emotion2vec_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),

@@ -18,7 +18,7 @@ segments; the segments are sorted by length, packed into batches under the refer
 `batch_size_threshold_s` policy, decoded by the HIP path, put back in order and merged (texts joined, per-token
 timestamps shifted by the segment start); with a `punc_model` (CT-Transformer directory or object) the joined text is
 punctuated once per recording (results that carry `words` keep their spelling, funasr_amd/punc_align.py) and
-`sentence_timestamp` cuts it into sentence records. With `spk_model` (a CAM++ directory or module) every sentence record
+`sentence_timestamp` cuts it into sentence records. With `spk_model` (a CAM++ or ERes2NetV2 directory, or a module) every sentence record
 carries a `spk` label (funasr_amd/speaker.py). `vad_model` may also be a local FSMN-VAD
 model directory: the network runs on the GPU (funasr_amd/fsmn_vad.py), its decision logic on the host
 (funasr_amd/vad_decision.py). `generate` hands a requested text-level hotword correction to the reference's own module (`_text_hotword_step`).
@@ -53,6 +53,7 @@ from . import transducer as _transducer  # noqa: F401  (registers Transducer / r
 from . import contextual_paraformer as _contextual_paraformer  # noqa: F401  (registers ContextualParaformer + its decoder)
 from . import ct_transformer as _ct_transformer  # noqa: F401  (registers CTTransformer)
 from . import emotion2vec as _emotion2vec  # noqa: F401  (registers Emotion2vec)
+from . import eres2net as _eres2net  # noqa: F401  (registers ERes2NetV2 / iic/speech_eres2netv2_sv_zh-cn_16k-common)
 from . import fsmn_vad as _fsmn_vad  # noqa: F401  (registers FSMN / FsmnVADStreaming)
 from . import kws as _kws  # noqa: F401  (registers FsmnKWS / SanmKWS)
 from . import monotonic_aligner as _monotonic_aligner  # noqa: F401  (registers MonotonicAligner)

@@ -194,40 +194,52 @@ class CAMPPlus(HipModule):
         """the reference's CAMPPlus.inference (model.py): waveforms (paths, arrays, tensors, a list of numpy chunks as AutoModel
         passes them) -> ([{"spk_embedding": [B, 192]}], meta). Each waveform gets its own kaldi fbank and time-mean removal; a
         batch of unequal lengths is zero-padded after that and the network runs over the padding (extract_feature + pad_list)."""
-        from .audio import load_audio_list
-
-        meta = {}
-        t1 = time.perf_counter()
-        if isinstance(data_in, (list, tuple)):
-            audio = [torch.as_tensor(np.asarray(d, dtype=np.float32)) if isinstance(d, np.ndarray) and d.dtype.kind == "f"
-                     else load_audio_list([d], fs=SAMPLE_RATE, audio_fs=kwargs.get("fs", SAMPLE_RATE))[0] for d in data_in]
-        else:
-            audio = load_audio_list(data_in, fs=SAMPLE_RATE, audio_fs=kwargs.get("fs", SAMPLE_RATE))
-        t2 = time.perf_counter()
-        meta["load_data"] = f"{t2 - t1:0.3f}"
-        dev = self._device()
-        feats = [self.fbank(a.to(dev)) for a in audio]
-        T = max(f.shape[0] for f in feats)
-        x = torch.zeros(len(feats), T, self.feat_dim, device=dev)
-        for i, f in enumerate(feats):
-            x[i, : f.shape[0]] = f
-        meta["extract_feat"] = f"{time.perf_counter() - t2:0.3f}"
-        meta["batch_data_time"] = float(sum(int(a.shape[0]) for a in audio)) / SAMPLE_RATE
-        return [{"spk_embedding": self.forward(x)}], meta
+        return speaker_inference(self, data_in, **kwargs)
 
     def fbank(self, wav: torch.Tensor) -> torch.Tensor:
         """extract_feature for one waveform on the device: kaldi fbank (CAM++ options) minus its time mean -> [T, 80]"""
-        n = int(wav.numel())
-        if n < 400:
-            raise ValueError("CAMPPlus: a waveform must hold at least one 25-ms analysis window")
-        dev = self._device()
-        fe = self.__dict__.setdefault("_fe", {}).get(dev)         # one frontend per device the module has lived on
-        if fe is None:
-            from .wav_frontend import WavFrontend
+        return speaker_fbank(self, wav)
 
-            fe = WavFrontend(window="povey", n_mels=self.feat_dim, frame_length=25, frame_shift=10, lfr_m=1, lfr_n=1, dither=0.0,
-                             upsacle_samples=False, device=dev)
-            self.__dict__["_fe"][dev] = fe
-        feats, flens = fe(wav.to(torch.float32).reshape(1, -1), [n])
-        f = feats[0, : int(flens[0])]
-        return f - f.mean(dim=0, keepdim=True)
+
+# The feature path of the reference's speaker models (campplus/utils.py extract_feature), shared by every module that has `feat_dim`,
+# `forward` and HipModule's `_device` (CAMPPlus, ERes2NetV2SV).
+def speaker_fbank(module, wav: torch.Tensor) -> torch.Tensor:
+    """extract_feature for one waveform on the device: kaldi fbank (povey window, no 2^15 scaling, dither 0) minus its time mean"""
+    n = int(wav.numel())
+    if n < 400:
+        raise ValueError(f"{type(module).__name__}: a waveform must hold at least one 25-ms analysis window")
+    dev = module._device()
+    fe = module.__dict__.setdefault("_fe", {}).get(dev)         # one frontend per device the module has lived on
+    if fe is None:
+        from .wav_frontend import WavFrontend
+
+        fe = WavFrontend(window="povey", n_mels=module.feat_dim, frame_length=25, frame_shift=10, lfr_m=1, lfr_n=1, dither=0.0,
+                         upsacle_samples=False, device=dev)
+        module.__dict__["_fe"][dev] = fe
+    feats, flens = fe(wav.to(torch.float32).reshape(1, -1), [n])
+    f = feats[0, : int(flens[0])]
+    return f - f.mean(dim=0, keepdim=True)
+
+
+def speaker_inference(module, data_in, **kwargs):
+    """waveforms -> ([{"spk_embedding": [B, E]}], meta): per-waveform fbank and mean removal, zero-padding to the longest, forward"""
+    from .audio import load_audio_list
+
+    meta = {}
+    t1 = time.perf_counter()
+    if isinstance(data_in, (list, tuple)):
+        audio = [torch.as_tensor(np.asarray(d, dtype=np.float32)) if isinstance(d, np.ndarray) and d.dtype.kind == "f"
+                 else load_audio_list([d], fs=SAMPLE_RATE, audio_fs=kwargs.get("fs", SAMPLE_RATE))[0] for d in data_in]
+    else:
+        audio = load_audio_list(data_in, fs=SAMPLE_RATE, audio_fs=kwargs.get("fs", SAMPLE_RATE))
+    t2 = time.perf_counter()
+    meta["load_data"] = f"{t2 - t1:0.3f}"
+    dev = module._device()
+    feats = [module.fbank(a.to(dev)) for a in audio]
+    T = max(f.shape[0] for f in feats)
+    x = torch.zeros(len(feats), T, module.feat_dim, device=dev)
+    for i, f in enumerate(feats):
+        x[i, : f.shape[0]] = f
+    meta["extract_feat"] = f"{time.perf_counter() - t2:0.3f}"
+    meta["batch_data_time"] = float(sum(int(a.shape[0]) for a in audio)) / SAMPLE_RATE
+    return [{"spk_embedding": module.forward(x)}], meta

@@ -327,6 +327,49 @@ def campplus_state_dict(seed: int = 0, embedding_size: int = 192) -> Dict[str, t
     return sd
 
 
+def eres2net_conf(feat_dim: int = 16, embedding_size: int = 32, m_channels: int = 16, num_blocks=(1, 1, 2, 1)) -> dict:
+    """an ERes2NetV2 model_conf at a chosen size (default: the tiny configuration of the tests; the published model is
+    feat_dim 80, embedding_size 192, m_channels 64, num_blocks [3, 4, 6, 3])"""
+    return {"feat_dim": feat_dim, "embedding_size": embedding_size, "m_channels": m_channels, "baseWidth": 26, "scale": 2,
+            "expansion": 2, "num_blocks": list(num_blocks), "pooling_func": "TSTP", "two_emb_layer": False}
+
+
+def eres2net_state_dict(seed: int = 0, module_or_shapes=None, gain: float = 1.1) -> Dict[str, torch.Tensor]:
+    """An ERes2NetV2 state dict in the reference's layout (funasr/models/eres2net/model.py: "model."-prefixed keys, 557 at the default
+    configuration) for a module, a {name: shape} mapping, or (None) the default configuration. Conv weights are He-scaled times
+    `gain` and the BatchNorm statistics are non-trivial (weight near 1, bias / running_mean off zero, running_var in [0.5, 2]), so
+    that folding is exercised and the block outputs reach both ends of their clamp(0, 20) (a plain ReLU then fails the parity tests)."""
+    if module_or_shapes is None:
+        from .eres2net import ERes2NetV2SV
+
+        module_or_shapes = ERes2NetV2SV()
+    shapes = module_or_shapes if isinstance(module_or_shapes, dict) else {k: tuple(v.shape) for k, v in module_or_shapes.state_dict().items()}
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for k, shp in shapes.items():
+        shp = tuple(shp)
+        bn = len(shp) <= 1 and not k.endswith("seg_1.bias") and not (k.endswith(("local_att.0.bias", "local_att.3.bias")))
+        if k.endswith("num_batches_tracked"):
+            sd[k] = torch.tensor(0, dtype=torch.long)
+        elif k.endswith("running_mean"):
+            sd[k] = 0.2 * torch.randn(shp, generator=g)
+        elif k.endswith("running_var"):
+            sd[k] = 0.5 + 1.5 * torch.rand(shp, generator=g)
+        elif bn:
+            sd[k] = (1.0 + 0.2 * torch.randn(shp, generator=g)) if k.endswith("weight") else 0.3 * torch.randn(shp, generator=g)
+        elif k.endswith("bias"):
+            sd[k] = 0.1 * torch.randn(shp, generator=g)
+        else:
+            fan_in = 1
+            for d in shp[1:]:
+                fan_in *= d
+            # layer3_ds has no BatchNorm behind it and seg_1 sums thousands of statistics of order 10: scaled down so that
+            # fuse34's two inputs are of one size and the embedding is of order one
+            scale = 0.02 if k.endswith("seg_1.weight") else (0.25 if k.endswith("layer3_ds.weight") else gain)
+            sd[k] = torch.randn(shp, generator=g) * scale * (2.0 / fan_in) ** 0.5
+    return sd
+
+
 def emotion2vec_conf(embed_dim: int = 256, num_heads: int = 4, prenet_depth: int = 1, depth: int = 2, num_alibi_heads: int = None,
                      per_head: bool = True) -> dict:
     """an emotion2vec model_conf (template.yaml's layout) at a chosen size; the conv encoder is the real 512-channel stack"""

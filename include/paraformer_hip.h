@@ -28,6 +28,7 @@
  *                                                            funasr/models/fsmn_kws/model.py, sanm_kws/model.py, utils/kws_utils.py
  *   pf_k_lstm     <-> torch.nn.LSTM layer (hotword encoder of SeACo, seaco_paraformer/model.py:388-424)
  *   pf_campplus   <-> CAMPPlus.forward (speaker embedding)  funasr/models/campplus/model.py, components.py
+ *   pf_eres2net   <-> ERes2NetV2SV.forward (speaker embedding)  funasr/models/eres2net/model.py, eres2netv2.py, fusion.py
  *
  * The handle style (opaque pointer, int return codes, library-owned scratch) follows the reference's own C
  * API for the same path, runtime/onnxruntime/include/funasrruntime.h:21-24,58-73. Tensor names accepted by
@@ -458,6 +459,64 @@ int pf_campplus_forward(pf_campplus* h, const float* feats_dev, int32_t B, int32
  * chunk's time mean -> the network -> emb_dev [N, embedding_size]. Every chunk's embedding is bitwise independent of N. No sync. */
 int pf_campplus_embed_chunks(pf_campplus* h, const float* wav_dev, int64_t n_samples, const int64_t* starts_host,
                              const int32_t* valid_host, int32_t N, int32_t chunk_len, float* emb_dev, void* stream);
+
+/* ---- ERes2NetV2 speaker embedding (funasr/models/eres2net/model.py ERes2NetV2SV.forward, eres2netv2.py, fusion.py; baseWidth 26,
+ * scale 2, expansion 2, TSTP pooling, one embedding layer). Tensor names are the reference's state_dict keys: "model.conv1.weight",
+ * "model.bn1.running_mean", "model.layer1.0.convs.1.weight", "model.layer2.0.shortcut.1.running_var",
+ * "model.layer3.0.fuse_models.0.local_att.0.bias", "model.layer3_ds.weight", "model.fuse34.local_att.4.weight", "model.seg_1.bias", ...
+ * (every parameter and BatchNorm running statistic; num_batches_tracked is not taken). Every BatchNorm is folded into the conv in
+ * front of it at the first forward after a set_tensor. Built: feat_dim 8 .. 128 and m_channels 8 .. 64 in multiples of 8, any four
+ * positive num_blocks, embedding_size >= 1. fp32-class arithmetic on the exact-f32 MFMA, the only mode. */
+typedef struct pf_eres2net pf_eres2net;
+typedef struct pf_eres2net_config {
+    int32_t feat_dim, embedding_size, m_channels;
+    int32_t num_blocks[4];
+    float bn_eps;             /* 1e-5 (torch BatchNorm default) */
+} pf_eres2net_config;
+pf_eres2net* pf_eres2net_create(const pf_eres2net_config* cfg);
+void pf_eres2net_destroy(pf_eres2net* h);
+int pf_eres2net_set_tensor(pf_eres2net* h, const char* name, const float* data, int64_t numel);
+int pf_eres2net_missing(const pf_eres2net* h);
+/* chunks per launch sequence (default 256); never changes a result bit. The workspace of a sub-batch is
+ * pf_eres2net_workspace_bytes(h, T) per chunk of T frames: twice the largest block input / output ([T, F, 2 m_channels] floats at
+ * layer 1), twice the largest split / concat buffer ([T, F, 2 pad4(width)]), and the smaller AFF, layer3_ds, pool and embedding
+ * buffers -- about 20 MB per 1.5-s chunk (150 frames) at the default configuration, 5.2 GB for 256 chunks. One long utterance through
+ * pf_eres2net_forward needs that for its whole length. */
+int pf_eres2net_set_max_batch(pf_eres2net* h, int32_t max_chunks);
+int64_t pf_eres2net_workspace_bytes(const pf_eres2net* h, int32_t T);
+/* test hook: fills every workspace buffer the handle owns with NaN bytes (after a device synchronise) */
+int pf_eres2net_debug_poison(pf_eres2net* h);
+/* feats_dev [B, T, feat_dim] (already mean-normalised, as extract_feature gives them) -> emb_dev [B, embedding_size].
+ * T >= 9: fewer frames leave one after the three stride-2 stages and the pool's standard deviation is undefined. No sync. */
+int pf_eres2net_forward(pf_eres2net* h, const float* feats_dev, int32_t B, int32_t T, float* emb_dev, void* stream);
+/* test hook: pf_eres2net_forward of one sub-batch (B <= max_batch) that also copies out what the network computes on the way.
+ * stages_dev: host array of 8 device pointers, each nullable: the stem, layer1 .. layer4, layer3_ds and fuse34 outputs
+ * (channels-last [B, t, f, c]) and the pooled statistics [B, 2 S]. */
+int pf_eres2net_forward_stages(pf_eres2net* h, const float* feats_dev, int32_t B, int32_t T, float* emb_dev, float* const* stages_dev,
+                               void* stream);
+/* as pf_campplus_embed_chunks (same gather, fbank with feat_dim bins, mean removal and zero-padding rule for short segments), then
+ * this network. Chunks of fewer than 9 frames are refused. Every chunk's embedding is bitwise independent of N. No sync. */
+int pf_eres2net_embed_chunks(pf_eres2net* h, const float* wav_dev, int64_t n_samples, const int64_t* starts_host,
+                             const int32_t* valid_host, int32_t N, int32_t chunk_len, float* emb_dev, void* stream);
+/* single-kernel hook (tests): ONE launch of the network's implicit-GEMM conv kernel on caller-supplied device buffers.
+ * Activations are channels-last [n_chunks, t, f, c] with row strides (lda, lda2, ldc, ...) in floats; a_col / a2_col / c_col select a
+ * column slice of a wider buffer (a_col, a2_col and the strides of A, A2 and W are multiples of 4, their bases 16-byte aligned).
+ * C[m, n] = epilogue(sum_k A[m, k] W[n, k]) over rows m = ((chunk * To + to) * Fo + fo), To = (tin - 1) / st + 1, Fo likewise:
+ *   taps 1 or 9 (3x3, padding 1, tap = kf * 3 + kt), strides st (time) and sf (frequency) in {1, 2}; k = tap * pad4(cin) + c;
+ *   zero outside the row's own chunk; channels c >= cin of A are never used (W's columns there must be zero).
+ *   a2_mode 0: none; 1: A2 (same geometry) is added to A by the loader; 2: K continues with pad4(cin2) columns, a 1x1 conv of
+ *   A2 [n_chunks, tin2, fin2, lda2] sampled at (to * st2, fo * sf2).
+ *   epilogue: + bias_dev[n] (nullable), + r_dev[m, n] (nullable), act 0 none / 1 max(., 0) / 2 min(max(., 0), 20) / 3 SiLU, then with
+ *   x_dev and y_dev (both or neither): C = x[m, n] (1 + tanh v) + y[m, n] (1 - tanh v). */
+int pf_k_eres_conv(const float* a_dev, int32_t lda, int32_t a_col, int32_t cin, const float* a2_dev, int32_t lda2, int32_t a2_col,
+                   int32_t cin2, int32_t a2_mode, int32_t tin2, int32_t fin2, int32_t st2, int32_t sf2, const float* w_dev, int32_t ldw,
+                   const float* bias_dev, const float* r_dev, int32_t ldr, const float* x_dev, int32_t ldx, const float* y_dev,
+                   int32_t ldy, float* c_dev, int32_t ldc, int32_t c_col, int32_t n_chunks, int32_t tin, int32_t fin, int32_t taps,
+                   int32_t st, int32_t sf, int32_t N, int32_t act, void* stream);
+/* measurement hook (tools/bench_eres2net.py): one 3x3 stride-1 conv of [n_chunks, T, F, C] (C % 4 == 0) to N channels with ReLU, weight
+ * [N, 9 C] tap-major, timed over `iters` launches on this network's conv kernel (ms_out[0]) and on CAM++'s (ms_out[1]). Synchronises. */
+int pf_k_eres_conv_vs_cam_time(const float* a_dev, const float* w_dev, float* c_dev, int32_t n_chunks, int32_t T, int32_t F, int32_t C,
+                               int32_t N, int32_t iters, float* ms_out, void* stream);
 
 /* ---- emotion2vec (funasr/models/emotion2vec/model.py Emotion2vec.extract_features + the inference head): waveform norm, the
  * 512-channel conv encoder (extractor_mode "layer_norm"), project_features, the grouped positional conv, extra tokens, context
