@@ -696,9 +696,13 @@ def transducer_conf(encoder: str = "ConformerEncoder", output_size: int = 128, a
                     enc_blocks: int = 2, embed_size: int = 48, hidden_size: int = 64, num_layers: int = 2, joint_space_size: int = 96,
                     vocab: int = 61, input_size: int = 80) -> dict:
     """constructor arguments of a Transducer model (the layout of funasr/models/rwkv_bat/template.yaml's prediction and joint
-    networks over one of the two built encoders) at a chosen size"""
-    enc = (conformer_conf if encoder == "ConformerEncoder" else transformer_conf)(
-        output_size=output_size, attention_heads=attention_heads, linear_units=linear_units, enc_blocks=enc_blocks)["encoder_conf"]
+    networks over one of the built encoders) at a chosen size. For RWKVEncoder `linear_units` is its linear_size and
+    `attention_heads` is unused; the template's time_reduction_factor 2 is kept"""
+    if encoder == "RWKVEncoder":
+        enc = rwkv_encoder_conf(output_size=output_size, linear_size=linear_units, num_blocks=enc_blocks)
+    else:
+        enc = (conformer_conf if encoder == "ConformerEncoder" else transformer_conf)(
+            output_size=output_size, attention_heads=attention_heads, linear_units=linear_units, enc_blocks=enc_blocks)["encoder_conf"]
     return {"encoder": encoder, "encoder_conf": enc, "decoder": "rnnt_decoder",
             "decoder_conf": {"embed_size": embed_size, "hidden_size": hidden_size, "num_layers": num_layers, "embed_dropout_rate": 0.1,
                              "dropout_rate": 0.1, "use_embed_mask": False},
@@ -707,6 +711,51 @@ def transducer_conf(encoder: str = "ConformerEncoder", output_size: int = 128, a
 
 
 TRANSDUCER_TEMPLATE = dict(embed_size=512, hidden_size=512, num_layers=1, joint_space_size=512, vocab=4234)
+
+# funasr/models/rwkv_bat/template.yaml: D 512, 18 blocks, every second frame kept; linear_size and context_size are the constructor's
+# defaults (4 D, 1024)
+RWKV_TEMPLATE = dict(output_size=512, num_blocks=18, time_reduction_factor=2)
+
+
+def rwkv_encoder_conf(output_size: int = 64, linear_size: int = 160, num_blocks: int = 3, time_reduction_factor: int = 2,
+                      context_size: int = None) -> dict:
+    """the encoder_conf of an RWKVEncoder in the layout of funasr/models/rwkv_bat/template.yaml at a chosen size (linear_size None:
+    the constructor's 4 x output_size)"""
+    conf = {"kernel": 3, "subsampling_factor": 4, "output_size": output_size, "num_blocks": num_blocks,
+            "time_reduction_factor": time_reduction_factor, "att_dropout_rate": 0.1, "ffn_dropout_rate": 0.1, "dropout_rate": 0.1}
+    if linear_size is not None:
+        conf["linear_size"] = linear_size
+    if context_size is not None:
+        conf["context_size"] = context_size
+    return conf
+
+
+def rwkv_encoder_state_dict(seed: int, model, prefix: str = "") -> Dict[str, torch.Tensor]:
+    """synthetic weights of the RWKVEncoder `model` (this package's or the reference's) under `prefix`, drawn in the sorted order of the
+    keys: He-scaled convs (six ReLUs in a row keep their scale), LayerNorms near identity, time_decay uniform over [-5, 3] (the span of
+    the reference's initialisation: w = -exp(.) from -0.007 to -20), time_first of order 0.5, token-shift mixes uniform over [0, 1],
+    fan-in scaled linears with the time mix's proj_key three times wider, so that |k| reaches about 12 and stays within a few tens"""
+    g = torch.Generator().manual_seed(seed)
+    shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
+    sd = {}
+    for k in sorted(shapes):
+        shp = shapes[k]
+        if k.endswith("time_decay"):
+            t = -5.0 + 8.0 * torch.rand(shp, generator=g)
+        elif k.endswith("time_first"):
+            t = 0.5 * torch.randn(shp, generator=g)
+        elif "time_mix_" in k:
+            t = torch.rand(shp, generator=g)
+        elif len(shp) == 1:
+            t = (1.0 + 0.2 * torch.randn(shp, generator=g)) if ("norm" in k and k.endswith("weight")) else 0.1 * torch.randn(shp, generator=g)
+        else:
+            fan_in = 1
+            for d in shp[1:]:
+                fan_in *= d
+            gain = 2.0 ** 0.5 if len(shp) == 4 else (3.0 if k.endswith("att.proj_key.weight") else 1.0)
+            t = torch.randn(shp, generator=g) * gain * (1.0 / fan_in) ** 0.5
+        sd[prefix + k] = t
+    return sd
 
 
 def transducer_state_dict(seed: int, model, n_planted: int = 10, threshold: float = 0.7) -> Dict[str, torch.Tensor]:
@@ -724,6 +773,8 @@ def transducer_state_dict(seed: int, model, n_planted: int = 10, threshold: floa
         reads dimension i only): ~ 0.74 then, ~ 0 otherwise, whatever came before. `lin_dec` row i turns it into -12, so a label is
         not emitted twice in a row and the frame falls back to blank."""
     sd = conformer_state_dict(seed, model)
+    if "encoder.rwkv_blocks.0.att.time_decay" in sd:                 # an RWKV encoder has its own drawing rule
+        sd.update(rwkv_encoder_state_dict(seed, model.encoder, prefix="encoder."))
     g = torch.Generator().manual_seed(seed + 7919)
     gains = {"weight_ih_l0": 2.0, "weight_hh_l0": 0.5, "joint_network.lin_enc.weight": 0.5, "joint_network.lin_dec.weight": 0.5,
              "joint_network.lin_out.weight": 1.5}

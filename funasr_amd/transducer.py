@@ -4,7 +4,8 @@ funasr/models/transducer/model.py, rnnt_decoder.py, joint_network.py, beam_searc
   * `RNNTDecoder` (decoder_classes "rnnt_decoder"): the prediction network -- an embedding and `num_layers` one-layer LSTMs -- as a
     parameter holder under the reference's keys (`embed.weight`, `rnn.{l}.weight_ih_l0` ...).
   * `JointNetwork` (joint_network_classes "joint_network"): `lin_enc`, `lin_dec` (no bias), `lin_out`, tanh.
-  * `Transducer` (model_classes): the encoder is the Conformer's or the Transformer's HIP handle; the model itself owns ONE
+  * `Transducer` (model_classes): the encoder is the Conformer's, the Transformer's or the RWKV encoder's HIP handle (the last is the
+    reference template's own, funasr_amd/rwkv_encoder.py); the model itself owns ONE
     `pf_transducer` handle (csrc/engine_transducer.hip) that holds both networks and runs the reference's one decoding path --
     `BeamSearchTransducer(decoder, joint_network, beam_size, nbest=1)` with the default search, one utterance per call, no LM --
     inside the library: a prediction step (csrc/transducer.hip) only for a new label prefix, two launches per joint evaluation,
@@ -15,7 +16,7 @@ non-finite joint value and more than `max_expansions_per_frame` (default 64 x be
 RuntimeError.
 
 Not built (each refused by name): `rnn_type: gru`, joint activations other than tanh, encoders other than ConformerEncoder /
-TransformerEncoder, `model: BAT` (refused where AutoModel resolves the name), `beam_size > 16`; the tsd / alsd / maes searches, LM fusion, chunk-by-chunk search and batched
+TransformerEncoder / RWKVEncoder (and, for RWKVEncoder, encoder_conf keys its constructor does not name), `model: BAT` (refused where AutoModel resolves the name), `beam_size > 16`; the tsd / alsd / maes searches, LM fusion, chunk-by-chunk search and batched
 search do not exist here. `use_embed_mask: true` is a training-time augmentation: accepted and ignored.
 """
 from __future__ import annotations
@@ -33,7 +34,7 @@ from .hip_module import HipModule, Holder, ParamHolder, linear, stream_ptr
 from .register import tables
 
 MAX_DIM, MAX_LAYERS, MAX_BEAM = 1024, 4, 16           # csrc/transducer.h
-_ENCODERS = ("ConformerEncoder", "TransformerEncoder")
+_ENCODERS = ("ConformerEncoder", "TransformerEncoder", "RWKVEncoder")
 
 
 def _check_dim(who: str, name: str, value: int):
@@ -120,7 +121,7 @@ class Transducer(PaddedBatchFront, HipModule):
         super().__init__()
         if encoder not in _ENCODERS:
             raise NotImplementedError(f"Transducer(HIP): encoder: {encoder} is not built (only {' / '.join(_ENCODERS)}; "
-                                      "ChunkConformerEncoder and RWKVEncoder are not)")
+                                      "ChunkConformerEncoder is not)")
         if decoder != "rnnt_decoder":
             raise NotImplementedError(f"Transducer(HIP): decoder: {decoder} is not built (only rnnt_decoder)")
         if joint_network != "joint_network":
@@ -129,8 +130,14 @@ class Transducer(PaddedBatchFront, HipModule):
             raise NotImplementedError(f"Transducer(HIP): blank_id: {blank_id} is not built (the search takes row 0 as the blank)")
         if encoder == "ConformerEncoder":
             from . import conformer  # noqa: F401  (registers it)
-        else:
+        elif encoder == "TransformerEncoder":
             from . import transformer  # noqa: F401
+        else:
+            from . import rwkv_encoder
+            foreign = rwkv_encoder.foreign_keys(encoder_conf)
+            if foreign:                                           # the reference swallows them in **kwargs and builds another geometry
+                raise NotImplementedError(f"Transducer(HIP): encoder: RWKVEncoder does not take encoder_conf keys {foreign} (its "
+                                          f"constructor's are {', '.join(rwkv_encoder.CONF_KEYS)}); the reference ignores them silently")
         enc_conf = dict(encoder_conf or {})
         enc_conf.pop("input_size", None)
         self.encoder = tables.encoder_classes[encoder](input_size=input_size, **enc_conf)
@@ -161,7 +168,8 @@ class Transducer(PaddedBatchFront, HipModule):
             self.set_precision(kwargs["precision"])
 
     def set_precision(self, mode=None):
-        """the encoder's arithmetic ("f16x2" default, "fp32"); the search is exact fp32 in both"""
+        """the encoder's arithmetic ("f16x2" default, "fp32"; the RWKV encoder has fp32 only, and None leaves it there); the search is
+        exact fp32 in both"""
         self.encoder.set_precision(mode)
         return self
 

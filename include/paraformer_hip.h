@@ -610,6 +610,51 @@ int32_t pf_tfencoder_num_frames(const pf_tfencoder* h, int32_t n_frames, int32_t
 int pf_tfencoder_forward(pf_tfencoder* h, const float* feats_dev, const int32_t* lens_host, int32_t B, int32_t Tin, float* out_dev,
                          int32_t* out_lens_host, void* stream);
 
+/* ---- RWKV encoder (funasr/models/rwkv_bat/rwkv_encoder.py RWKVEncoder, the encoder of the reference's Transducer template: the VGG
+ * front RWKVConvInput at subsampling_factor 4 -- six 3x3 convs + ReLU, an output linear --, embed_norm, blocks of time mix (token
+ * shift, WKV recurrence, receptance gate) and channel mix (token shift, relu^2 feed-forward, receptance gate), final_norm, then every
+ * time_reduction-th frame). fp32 throughout. Tensor names are the reference's keys below `encoder.`: "embed.conv.0.weight" ..
+ * "embed.conv.10.bias", "embed.output.weight", "embed_norm.weight", "rwkv_blocks.0.layer_norm_att.weight", "rwkv_blocks.0.att.time_decay",
+ * "rwkv_blocks.0.att.time_mix_key" ([1, 1, D]), "rwkv_blocks.0.att.proj_key.weight", "rwkv_blocks.0.ffn.proj_value.bias", "final_norm.bias".
+ * Unlike the encoders above, the front runs CLIP BY CLIP at the clip's own length: clip b of a batch gets bit for bit what it gets
+ * alone (the reference itself handles one clip per call). Behind the front every block looks back only: row n of a block's output
+ * depends on the front's rows 0 .. n of the same clip (the front's six 3x3 convs each look one frame ahead, so an OUTPUT frame does
+ * depend on a few feature frames after it). */
+typedef struct pf_rwkvencoder pf_rwkvencoder;
+typedef struct pf_rwkvencoder_config {
+    int32_t input_dim;            /* 8 .. 256, a multiple of 4 */
+    int32_t d_model;              /* output_size = attention_size: a multiple of 32 up to 1024 */
+    int32_t linear_size;          /* a multiple of 32 up to 4096 */
+    int32_t n_blocks, time_reduction;
+    float ln_eps;
+} pf_rwkvencoder_config;
+pf_rwkvencoder* pf_rwkvencoder_create(const pf_rwkvencoder_config* cfg);
+void pf_rwkvencoder_destroy(pf_rwkvencoder* h);
+int pf_rwkvencoder_set_tensor(pf_rwkvencoder* h, const char* name, const float* data, int64_t numel);
+int pf_rwkvencoder_missing(const pf_rwkvencoder* h);
+/* output frames of a clip of n_frames: floor((ceil(ceil(n / 2) / 2) - 1) / time_reduction) + 1; -1 on a null handle or n < 1 */
+int32_t pf_rwkvencoder_num_frames(const pf_rwkvencoder* h, int32_t n_frames);
+/* feats_dev [B, Tin, input_dim], lens_host[b] in 1 .. Tin -> out_dev [B, num_frames(Tin), d_model], rows at or past
+ * out_lens_host[b] (optional) = num_frames(lens_host[b]) are zeros. No sync. */
+int pf_rwkvencoder_forward(pf_rwkvencoder* h, const float* feats_dev, const int32_t* lens_host, int32_t B, int32_t Tin, float* out_dev,
+                           int32_t* out_lens_host, void* stream);
+/* tests: the same, and stages_dev[0 .. n_blocks + 2) (a host array of device pointers, each nullable) receive [B, T2, d_model] copies,
+ * T2 = ceil(ceil(Tin / 2) / 2), of the front's output (rows past a clip's own T2 unspecified), embed_norm's, and every block's */
+int pf_rwkvencoder_forward_stages(pf_rwkvencoder* h, const float* feats_dev, const int32_t* lens_host, int32_t B, int32_t Tin,
+                                  float* out_dev, int32_t* out_lens_host, float* const* stages_dev, void* stream);
+/* tests: fill every workspace buffer with 0xff bytes (a forward must not read what it did not write) */
+int pf_rwkvencoder_debug_poison(pf_rwkvencoder* h);
+/* single-kernel hooks (csrc/rwkv.h). pf_k_rwkv_chunk: frames per WKV chunk. pf_k_rwkv_mix: y[row, j D + c] = LN(x[row]) mu_j + LN(x[row
+ * - 1]) (1 - mu_j), two operands when mix2_dev is null. pf_k_rwkv_wkv: out = sigmoid(r) wkv(k, v; w = -exp(time_decay), u = time_first);
+ * scratch_dev holds B * ceil(T / chunk) * 3 * D floats. lens_dev: device int32 [B]; rows at or past a length are written as zeros. */
+int pf_k_rwkv_chunk(void);
+int pf_k_rwkv_mix(const float* x_dev, int32_t ldx, const float* gamma_dev, const float* beta_dev, float eps, const float* mix0_dev,
+                  const float* mix1_dev, const float* mix2_dev, float* y_dev, int32_t ldy, const int32_t* lens_dev, int32_t B, int32_t T,
+                  int32_t D, void* stream);
+int pf_k_rwkv_wkv(const float* k_dev, const float* v_dev, const float* r_dev, int32_t ld, const float* w_dev, const float* u_dev,
+                  const int32_t* lens_dev, int32_t B, int32_t T, int32_t D, float* out_dev, int32_t ldo, float* scratch_dev,
+                  int64_t scratch_floats, void* stream);
+
 /* ---- E-Branchformer encoder (funasr/models/e_branchformer/encoder.py EBranchformerEncoder: Conv2dSubsampling, then blocks of two
  * parallel branches -- relative-position self-attention ("latest" or "legacy", head dim 64) and the convolutional gating MLP
  * (branchformer/cgmlp.py: Linear + exact GELU, LayerNorm + depthwise conv gate, Linear) -- merged by a depthwise conv over their
