@@ -107,6 +107,11 @@ class pf_rwkvencoder_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("input_dim", "d_model", "linear_size", "n_blocks", "time_reduction")] + [("ln_eps", C.c_float)]
 
 
+class pf_chunkconformer_config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("input_dim", "d_model", "n_heads", "ffn_dim", "n_blocks", "kernel_size", "subsampling",
+                                          "causal_conv", "left_chunk", "time_reduction")] + [("ln_eps", C.c_float), ("bn_eps", C.c_float)]
+
+
 class pf_ebranchformer_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("input_dim", "d_model", "n_heads", "ffn_dim", "n_blocks", "cgmlp_units", "cgmlp_kernel",
                                           "merge_kernel", "use_ffn", "macaron", "legacy", "precision")] + [("ln_eps", C.c_float)]
@@ -279,6 +284,18 @@ SIGNATURES = {
     "pf_rwkvencoder_forward": (C.c_int, [_vp, _vp, _pi32, _i32, _i32, _vp, _pi32, _vp]),
     "pf_rwkvencoder_forward_stages": (C.c_int, [_vp, _vp, _pi32, _i32, _i32, _vp, _pi32, C.POINTER(_vp), _vp]),
     "pf_rwkvencoder_debug_poison": (C.c_int, [_vp]),
+    "pf_chunkconformer_create": (_vp, [C.POINTER(pf_chunkconformer_config)]),
+    "pf_chunkconformer_destroy": (None, [_vp]),
+    "pf_chunkconformer_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),
+    "pf_chunkconformer_missing": (C.c_int, [_vp]),
+    "pf_chunkconformer_set_precision": (C.c_int, [_vp, _i32]),
+    "pf_chunkconformer_num_frames": (_i32, [_vp, _i32]),
+    "pf_chunkconformer_forward": (C.c_int, [_vp, _vp, _pi32, _i32, _i32, _i32, _i32, _vp, _vp, _pi32, C.POINTER(_vp), _vp]),
+    "pf_chunkconformer_front": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "pf_chunkconformer_debug_poison": (C.c_int, [_vp]),
+    "pf_k_cc_window_attention": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "pf_k_cc_glu_dw": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "pf_k_cc_copy_rows": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
     "pf_k_rwkv_chunk": (C.c_int, []),
     "pf_k_rwkv_mix": (C.c_int, [_vp, _i32, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
     "pf_k_rwkv_wkv": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _vp]),

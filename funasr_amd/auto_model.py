@@ -50,6 +50,7 @@ from . import sanm as _sanm  # noqa: F401  (registers SANM / FsmnDecoder)
 from . import uniasr as _uniasr  # noqa: F401  (registers UniASR / FsmnDecoderSCAMAOpt)
 from . import lcbnet as _lcbnet  # noqa: F401  (registers LCBNet / TransformerTextEncoder / FusionSANEncoder / ConvBiasPredictor)
 from . import transducer as _transducer  # noqa: F401  (registers Transducer / rnnt_decoder / joint_network)
+from . import chunk_conformer as _chunk_conformer  # noqa: F401  (registers ChunkConformerEncoder, the encoder of the reference's streaming / unified RNN-T recipes)
 from . import rwkv_encoder as _rwkv_encoder  # noqa: F401  (registers RWKVEncoder, the encoder of the reference's Transducer template)
 from . import contextual_paraformer as _contextual_paraformer  # noqa: F401  (registers ContextualParaformer + its decoder)
 from . import ct_transformer as _ct_transformer  # noqa: F401  (registers CTTransformer)

@@ -1,5 +1,5 @@
 // The tile step of the swapped-MFMA attention kernels: attention_f32_kernel, attention_f32_dma_kernel, attention_bf16_kernel,
-// attention_split3_kernel, relpos_attention_kernel and attention_mid_kernel.
+// attention_split3_kernel, relpos_attention_kernel, cc_window_attention_kernel and attention_mid_kernel.
 //
 // Mapping. A wave owns 32 queries and a lane owns ONE of them (q = lane & 31); both products are issued "swapped", so the keys
 // of a 32-key tile and then the output channels run over the lane's accumulator registers:
@@ -80,6 +80,34 @@ __device__ __forceinline__ void tile_softmax(S& s, float& m_run, float& l_run, f
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         s[r] = ex(s[r] - m_new);
+        psum += s[r];
+    }
+    psum += __shfl_xor(psum, 32, 64);
+    l_run = l_run * alpha + psum;
+    m_run = m_new;
+#pragma unroll
+    for (int d = 0; d < ND; ++d)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
+}
+
+// tile_softmax (libm expf) for kernels whose mask can leave a query NO valid key in a tile, or in every tile so far
+// (launch_cc_window_attention: a tile is taken when ANY of the workgroup's queries sees a key of it): while the running maximum is
+// still -inf the exponent's reference point is 0, so a masked score gives exp(-inf) = 0 instead of exp(-inf + inf) = NaN. Where the
+// new maximum is finite this is tile_softmax<ND, false> operation for operation.
+template <int ND, class S>
+__device__ __forceinline__ void tile_softmax_masked(S& s, float& m_run, float& l_run, floatx16 (&o)[ND]) {
+    float mx = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[r]);
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float m_new = fmaxf(m_run, mx);
+    const float m_ref = m_new == -INFINITY ? 0.f : m_new;
+    const float alpha = expf(m_run - m_ref);
+    float psum = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        s[r] = expf(s[r] - m_ref);
         psum += s[r];
     }
     psum += __shfl_xor(psum, 32, 64);

@@ -697,9 +697,12 @@ def transducer_conf(encoder: str = "ConformerEncoder", output_size: int = 128, a
                     vocab: int = 61, input_size: int = 80) -> dict:
     """constructor arguments of a Transducer model (the layout of funasr/models/rwkv_bat/template.yaml's prediction and joint
     networks over one of the built encoders) at a chosen size. For RWKVEncoder `linear_units` is its linear_size and
-    `attention_heads` is unused; the template's time_reduction_factor 2 is kept"""
+    `attention_heads` is unused; the template's time_reduction_factor 2 is kept. ChunkConformerEncoder gets chunk_conformer_conf's
+    dynamic mode"""
     if encoder == "RWKVEncoder":
         enc = rwkv_encoder_conf(output_size=output_size, linear_size=linear_units, num_blocks=enc_blocks)
+    elif encoder == "ChunkConformerEncoder":
+        enc = chunk_conformer_conf(output_size=output_size, attention_heads=attention_heads, linear_units=linear_units, num_blocks=enc_blocks)
     else:
         enc = (conformer_conf if encoder == "ConformerEncoder" else transformer_conf)(
             output_size=output_size, attention_heads=attention_heads, linear_units=linear_units, enc_blocks=enc_blocks)["encoder_conf"]
@@ -727,6 +730,24 @@ def rwkv_encoder_conf(output_size: int = 64, linear_size: int = 160, num_blocks:
         conf["linear_size"] = linear_size
     if context_size is not None:
         conf["context_size"] = context_size
+    return conf
+
+
+def chunk_conformer_conf(output_size: int = 64, attention_heads: int = 1, linear_units: int = 128, num_blocks: int = 2,
+                         cnn_module_kernel: int = 15, subsampling_factor: int = 4, time_reduction_factor: int = 2, mode: str = "dynamic",
+                         default_chunk_size: int = 4, left_chunk_size: int = 1, **more) -> dict:
+    """the encoder_conf of a ChunkConformerEncoder (funasr/models/conformer/encoder.py:914) at a chosen size, in one of its three
+    forward modes: "full" (neither flag), "dynamic" (dynamic_chunk_training) or "unified" (unified_model_training). Its synthetic
+    weights are drawn by conformer_state_dict's rule."""
+    if mode not in ("full", "dynamic", "unified"):
+        raise ValueError(f"chunk_conformer_conf: mode {mode!r} (full, dynamic or unified)")
+    conf = {"output_size": output_size, "attention_heads": attention_heads, "linear_units": linear_units, "num_blocks": num_blocks,
+            "dropout_rate": 0.1, "positional_dropout_rate": 0.1, "attention_dropout_rate": 0.1, "embed_vgg_like": False,
+            "normalize_before": True, "activation_type": "swish", "cnn_module_kernel": cnn_module_kernel,
+            "subsampling_factor": subsampling_factor, "time_reduction_factor": time_reduction_factor,
+            "dynamic_chunk_training": mode == "dynamic", "unified_model_training": mode == "unified",
+            "default_chunk_size": default_chunk_size, "left_chunk_size": left_chunk_size, "jitter_range": 2}
+    conf.update(more)
     return conf
 
 

@@ -4,8 +4,8 @@ funasr/models/transducer/model.py, rnnt_decoder.py, joint_network.py, beam_searc
   * `RNNTDecoder` (decoder_classes "rnnt_decoder"): the prediction network -- an embedding and `num_layers` one-layer LSTMs -- as a
     parameter holder under the reference's keys (`embed.weight`, `rnn.{l}.weight_ih_l0` ...).
   * `JointNetwork` (joint_network_classes "joint_network"): `lin_enc`, `lin_dec` (no bias), `lin_out`, tanh.
-  * `Transducer` (model_classes): the encoder is the Conformer's, the Transformer's or the RWKV encoder's HIP handle (the last is the
-    reference template's own, funasr_amd/rwkv_encoder.py); the model itself owns ONE
+  * `Transducer` (model_classes): the encoder is the Conformer's, the Transformer's, the RWKV encoder's (the reference template's own,
+    funasr_amd/rwkv_encoder.py) or the chunk Conformer's HIP handle (funasr_amd/chunk_conformer.py); the model itself owns ONE
     `pf_transducer` handle (csrc/engine_transducer.hip) that holds both networks and runs the reference's one decoding path --
     `BeamSearchTransducer(decoder, joint_network, beam_size, nbest=1)` with the default search, one utterance per call, no LM --
     inside the library: a prediction step (csrc/transducer.hip) only for a new label prefix, two launches per joint evaluation,
@@ -16,7 +16,7 @@ non-finite joint value and more than `max_expansions_per_frame` (default 64 x be
 RuntimeError.
 
 Not built (each refused by name): `rnn_type: gru`, joint activations other than tanh, encoders other than ConformerEncoder /
-TransformerEncoder / RWKVEncoder (and, for RWKVEncoder, encoder_conf keys its constructor does not name), `model: BAT` (refused where AutoModel resolves the name), `beam_size > 16`; the tsd / alsd / maes searches, LM fusion, chunk-by-chunk search and batched
+TransformerEncoder / RWKVEncoder / ChunkConformerEncoder (and, for the last two, encoder_conf keys their constructors do not name), `model: BAT` (refused where AutoModel resolves the name), `beam_size > 16`; the tsd / alsd / maes searches, LM fusion, chunk-by-chunk search and batched
 search do not exist here. `use_embed_mask: true` is a training-time augmentation: accepted and ignored.
 """
 from __future__ import annotations
@@ -34,7 +34,7 @@ from .hip_module import HipModule, Holder, ParamHolder, linear, stream_ptr
 from .register import tables
 
 MAX_DIM, MAX_LAYERS, MAX_BEAM = 1024, 4, 16           # csrc/transducer.h
-_ENCODERS = ("ConformerEncoder", "TransformerEncoder", "RWKVEncoder")
+_ENCODERS = ("ConformerEncoder", "TransformerEncoder", "RWKVEncoder", "ChunkConformerEncoder")
 
 
 def _check_dim(who: str, name: str, value: int):
@@ -120,8 +120,7 @@ class Transducer(PaddedBatchFront, HipModule):
                  share_embedding: bool = False, **kwargs):
         super().__init__()
         if encoder not in _ENCODERS:
-            raise NotImplementedError(f"Transducer(HIP): encoder: {encoder} is not built (only {' / '.join(_ENCODERS)}; "
-                                      "ChunkConformerEncoder is not)")
+            raise NotImplementedError(f"Transducer(HIP): encoder: {encoder} is not built (only {' / '.join(_ENCODERS)})")
         if decoder != "rnnt_decoder":
             raise NotImplementedError(f"Transducer(HIP): decoder: {decoder} is not built (only rnnt_decoder)")
         if joint_network != "joint_network":
@@ -132,6 +131,12 @@ class Transducer(PaddedBatchFront, HipModule):
             from . import conformer  # noqa: F401  (registers it)
         elif encoder == "TransformerEncoder":
             from . import transformer  # noqa: F401
+        elif encoder == "ChunkConformerEncoder":
+            from . import chunk_conformer
+            foreign = chunk_conformer.foreign_keys(encoder_conf)
+            if foreign:                                           # the reference's constructor has no **kwargs: TypeError there
+                raise NotImplementedError(f"Transducer(HIP): encoder: ChunkConformerEncoder does not take encoder_conf keys {foreign} (its "
+                                          f"constructor's are {', '.join(chunk_conformer.CONF_KEYS)})")
         else:
             from . import rwkv_encoder
             foreign = rwkv_encoder.foreign_keys(encoder_conf)
@@ -168,10 +173,21 @@ class Transducer(PaddedBatchFront, HipModule):
             self.set_precision(kwargs["precision"])
 
     def set_precision(self, mode=None):
-        """the encoder's arithmetic ("f16x2" default, "fp32"; the RWKV encoder has fp32 only, and None leaves it there); the search is
+        """the encoder's arithmetic ("f16x2" default, "fp32"; the RWKV and chunk Conformer encoders have fp32 only, and None leaves them there); the search is
         exact fp32 in both"""
         self.encoder.set_precision(mode)
         return self
+
+    def encode(self, speech: torch.Tensor, speech_lengths, **kwargs):
+        """transducer/model.py encode: (encoder_out [B, T, D], lengths). With a unified-mode ChunkConformerEncoder the reference
+        unpacks (x_utt, x_chunk, olens) positionally and hands x_chunk on as "lengths", which its inference never reads; here the
+        utt branch runs alone and the lengths are the true ones."""
+        if not hasattr(self.encoder, "forward_utt"):
+            return super().encode(speech, speech_lengths, **kwargs)
+        if self.normalize is not None:
+            dev = self.encoder._device()
+            speech, speech_lengths = self.normalize(speech.to(device=dev, dtype=torch.float32).contiguous(), speech_lengths)
+        return self.encoder.forward_utt(speech, speech_lengths)
 
     def _make_config(self):
         c = _lib.pf_transducer_config()

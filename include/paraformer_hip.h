@@ -655,6 +655,60 @@ int pf_k_rwkv_wkv(const float* k_dev, const float* v_dev, const float* r_dev, in
                   const int32_t* lens_dev, int32_t B, int32_t T, int32_t D, float* out_dev, int32_t ldo, float* scratch_dev,
                   int64_t scratch_floats, void* stream);
 
+/* ---- Chunk Conformer encoder (funasr/models/conformer/encoder.py ConformerChunkEncoder, registered as ChunkConformerEncoder: the
+ * StreamingConvInput front at 1/2, 1/4 or 1/6 subsampling (vgg_like = False), blocks of macaron feed-forward, chunk-masked
+ * relative-position self-attention (head dim 64), the convolution module (causal or symmetric), feed-forward and norm_final, then
+ * norm_blocks and every time_reduction-th frame). fp32 throughout. Tensor names are the reference's keys below `encoder.`:
+ * "embed.conv.0.weight", "embed.conv.2.bias", "embed.output.weight", "encoders.blocks.0.self_att.linear_pos.weight",
+ * "encoders.blocks.0.self_att.pos_bias_u", "encoders.blocks.0.feed_forward_macaron.w_1.weight",
+ * "encoders.blocks.0.conv_mod.norm.running_mean", "encoders.blocks.0.norm_self_att.weight", "encoders.norm_blocks.bias", ... plus
+ * "pos_table" as for pf_conformer's "latest" form (9999 rows). The ZERO-PADDED batch goes in and every row of it is computed. The
+ * front's workspace grows with the batch (its first conv's output, B pieces x frames / 2 x features / 2 x d_model floats, is the
+ * largest part: 1.9 GB for sixteen 30-s clips at d_model 512); a batch whose first-conv output would pass 8 GB is refused. */
+typedef struct pf_chunkconformer pf_chunkconformer;
+typedef struct pf_chunkconformer_config {
+    int32_t input_dim;            /* 16 .. 256 */
+    int32_t d_model, n_heads;     /* d_model = 64 n_heads, up to 2048 */
+    int32_t ffn_dim;              /* a multiple of 32 */
+    int32_t n_blocks;
+    int32_t kernel_size;          /* odd, up to 31 */
+    int32_t subsampling;          /* 2, 4 or 6 */
+    int32_t causal_conv;          /* dynamic_chunk_training or unified_model_training: the depthwise conv pads kernel_size - 1 on the left only */
+    int32_t left_chunk;           /* left_chunk_size: chunks of the past a query sees beside its own (< 0: all of the past) */
+    int32_t time_reduction;
+    float ln_eps, bn_eps;
+} pf_chunkconformer_config;
+pf_chunkconformer* pf_chunkconformer_create(const pf_chunkconformer_config* cfg);
+void pf_chunkconformer_destroy(pf_chunkconformer* h);
+int pf_chunkconformer_set_tensor(pf_chunkconformer* h, const char* name, const float* data, int64_t numel);
+int pf_chunkconformer_missing(const pf_chunkconformer* h);
+/* 0 (fp32) is the one arithmetic built; anything else is refused */
+int pf_chunkconformer_set_precision(pf_chunkconformer* h, int32_t precision);
+/* output frames of a clip of n_frames: floor((ceil(ceil(n / 2) / s2) - 1) / time_reduction) + 1, s2 = subsampling / 2; -1 on error */
+int32_t pf_chunkconformer_num_frames(const pf_chunkconformer* h, int32_t n_frames);
+/* feats_dev [B, Tin, input_dim], lens_host[b] in 1 .. Tin. chunk > 0: the front convolves pieces of chunk * subsampling frames on their
+ * own; chunk == 0: whole clips. branches: bit 0 = the blocks WITHOUT a chunk mask -> out_utt_dev, bit 1 = the blocks under the chunk
+ * mask of (chunk, left_chunk) -> out_chunk_dev (chunk == 0: no mask either); both read one run of the front. Outputs
+ * [B, num_frames(Tin), d_model]; out_lens_host (optional) = num_frames(lens_host[b]). stages_dev (tests; nullable, entries nullable):
+ * a host array of n_blocks + 2 device pointers that receive [B, T, d_model] copies (T = frames before the time reduction) of the
+ * front's rows, every block's output and norm_blocks' output, of the chunk branch where it runs, else of the utt branch. No sync. */
+int pf_chunkconformer_forward(pf_chunkconformer* h, const float* feats_dev, const int32_t* lens_host, int32_t B, int32_t Tin, int32_t chunk,
+                              int32_t branches, float* out_utt_dev, float* out_chunk_dev, int32_t* out_lens_host,
+                              float* const* stages_dev, void* stream);
+/* tests: the front alone -> out_dev [B, ceil(ceil(Tin / 2) / s2), d_model] */
+int pf_chunkconformer_front(pf_chunkconformer* h, const float* feats_dev, int32_t B, int32_t Tin, int32_t chunk, float* out_dev, void* stream);
+/* tests: fill every workspace buffer with 0xff bytes (a forward must not read what it did not write) */
+int pf_chunkconformer_debug_poison(pf_chunkconformer* h);
+/* single-kernel hooks (csrc/chunk_conformer.h). pf_k_cc_window_attention: pf_k_relpos_attention's "latest" form where query i sees keys
+ * [start_i, end_i) of (chunk, left) below klens_dev[b] only (chunk == 0: no chunk mask); rows without a visible key are zeros.
+ * pf_k_cc_glu_dw: pf_k_conformer_glu_dw with causal != 0 padding taps - 1 rows on the left only. pf_k_cc_copy_rows:
+ * y[b, t] = x[b, t * step], t < To, x of Ti rows per sequence. */
+int pf_k_cc_window_attention(const float* qkv_dev, const float* P_dev, const float* u_dev, const float* v_dev, const int32_t* klens_dev,
+                             int32_t B, int32_t T, int32_t H, int32_t chunk, int32_t left, float* out_dev, void* stream);
+int pf_k_cc_glu_dw(const float* g_dev, const float* dw_dev, const float* dw_bias_dev, const float* bn_scale_dev, const float* bn_shift_dev,
+                   int32_t B, int32_t T, int32_t D, int32_t taps, int32_t causal, float* y_dev, void* stream);
+int pf_k_cc_copy_rows(const float* x_dev, int32_t Ti, int32_t step, float* y_dev, int32_t B, int32_t To, int32_t D, void* stream);
+
 /* ---- E-Branchformer encoder (funasr/models/e_branchformer/encoder.py EBranchformerEncoder: Conv2dSubsampling, then blocks of two
  * parallel branches -- relative-position self-attention ("latest" or "legacy", head dim 64) and the convolutional gating MLP
  * (branchformer/cgmlp.py: Linear + exact GELU, LayerNorm + depthwise conv gate, Linear) -- merged by a depthwise conv over their
