@@ -272,6 +272,8 @@ struct GemmArgs {
     int conv_taps, conv_D, conv_T, conv_left; const float* conv_zero;
 };
 int launch_gemm_f32(const GemmArgs& a, hipStream_t stream);
+// rows of the block tile launch_gemm_f32 takes for an M x N problem: 64 or 128 (the launcher's own rule, read by the tests)
+int gemm_f32_block_rows(int M, int N);
 // small-M weight-streaming variant (gemm_skinny.hip); same contract, no fused arg-max
 bool gemm_skinny_applicable(const GemmArgs& a);
 // the small-M GEMM for up to 16 weight matrices sharing A / M / N / K / strides (gemm_skinny.hip): one launch, a row's bits

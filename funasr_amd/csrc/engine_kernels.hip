@@ -27,6 +27,7 @@ int pf_k_ln_consts(const float* W, int32_t ldw, int32_t N, int32_t K, const floa
     return launch_ln_consts(W, ldw, N, K, gamma, beta, bias, c, c + N, reinterpret_cast<hipStream_t>(stream));
 }
 int pf_set_skinny_max_m(int32_t m) { g_skinny_max_m = m; return 0; }
+int pf_k_gemm_f32_block_rows(int32_t M, int32_t N) { return gemm_f32_block_rows(M, N); }
 
 int pf_k_gemm_f32(const float* A, int32_t lda, const float* W, int32_t ldw, const float* bias, const float* R1,
                   int32_t ldr1, const float* R2, int32_t ldr2, float* C, int32_t ldc, int32_t M, int32_t N, int32_t K,

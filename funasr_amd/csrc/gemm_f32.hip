@@ -51,7 +51,7 @@ constexpr int MODE_ARGMAX = 4;   // MODE bit 0: + R1, bit 1: + R2; 4: fused arg-
 
 // TM = 32-row MFMA tiles per wave in M: 2 -> the 128 x 128 block tile; 1 -> a 64 x 128 block tile, chosen by the
 // launcher when the 128-row grid would leave most CUs idle (decoder-sized problems: twice the workgroups, same
-// per-element fma chain, so the choice never changes a bit of the result)
+// per-element fma chain, so the choice never changes a bit of the result: tests/test_gemm_f32_edges_gpu.py)
 // CONV: the A operand is the im2col of a Conv1d over time, gathered by the DMA sources (GemmArgs.conv_*)
 template <int MODE, bool BF16, int TM, bool CONV = false>
 __global__ __launch_bounds__(256, 2) void gemm_f32_mfma_kernel(GemmArgs p, int nM, int nN) {
@@ -303,16 +303,18 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_mfma_kernel(GemmArgs p, int n
 
 }  // namespace
 
+// 64-row block tiles when the 128-row grid cannot even give every CU its two workgroups (2 x 256 CUs)
+int gemm_f32_block_rows(int M, int N) { return ceil_div(M, 128) * ceil_div(N, BN) < 512 ? 64 : 128; }
+
 int launch_gemm_f32(const GemmArgs& a, hipStream_t stream) {
     PF_REQUIRE(a.M > 0 && a.N > 0 && a.K > 0, "gemm: empty problem");
     const int bk = a.ab_bf16 ? 64 : 32, align = a.ab_bf16 ? 8 : 4;
     PF_REQUIRE(a.K % bk == 0, "gemm: K must be a multiple of 32 (fp32) / 64 (bf16): pad the operand");
     PF_REQUIRE(a.lda % align == 0 && a.ldw % align == 0, "gemm: operand row strides must be multiples of 16 bytes");
     PF_REQUIRE(((uintptr_t)a.A & 15) == 0 && ((uintptr_t)a.W & 15) == 0, "gemm: operands must be 16-B aligned");
-    // 64-row block tiles when the 128-row grid cannot even give every CU its two workgroups (2 x 256 CUs)
     const int nN = ceil_div(a.N, BN);
-    const bool half_tile = ceil_div(a.M, 128) * nN < 512;
-    const int BMr = half_tile ? 64 : 128;
+    const int BMr = gemm_f32_block_rows(a.M, a.N);
+    const bool half_tile = BMr == 64;
     const int nM = ceil_div(a.M, BMr);
     if (a.amax_val) PF_REQUIRE(a.amax_ld >= 2 * nN, "gemm: amax_ld too small");
     const int nMpad = (nM + 7) / 8 * 8;

@@ -326,7 +326,8 @@ int launch_skinny(const GemmArgs& a, hipStream_t stream) {
 bool gemm_skinny_applicable(const GemmArgs& a) { return a.amax_val == nullptr && a.K % 16 == 0; }
 
 int launch_gemm_skinny(const GemmArgs& a, hipStream_t stream) {
-    PF_REQUIRE(a.M > 0 && a.N > 0 && a.K > 0 && a.K % 16 == 0, "gemm_skinny: K must be a multiple of 16");
+    PF_REQUIRE(a.M > 0 && a.N > 0 && a.K > 0, "gemm_skinny: empty problem");
+    PF_REQUIRE(a.K % 16 == 0, "gemm_skinny: K must be a multiple of 16");
     PF_REQUIRE(a.lda % 4 == 0 && a.ldw % 4 == 0, "gemm_skinny: row strides must be multiples of 4 floats");
     PF_REQUIRE(((uintptr_t)a.A & 15) == 0 && ((uintptr_t)a.W & 15) == 0 && a.C, "gemm_skinny: operands must be 16-B aligned");
     if (a.ln_stats_out) PF_REQUIRE(a.N % 16 == 0 && ((uintptr_t)a.ln_stats_out & 7) == 0, "gemm_skinny: LayerNorm partials need N % 16 == 0");

@@ -1191,6 +1191,9 @@ int pf_k_ln_consts(const float* W, int32_t ldw, int32_t N, int32_t K, const floa
 /* test hook: pf_k_gemm_f32 takes the small-M weight-streaming kernel (the streaming step's GEMM) for M <= m;
  * default 0 = the 128x128 tile kernel (the offline path's GEMM) */
 int pf_set_skinny_max_m(int32_t m);
+/* read-only: rows of the block tile (64 or 128) the tile kernel takes for an M x N problem, fp32 and bf16 operands alike: the
+ * launcher's own rule, so that a test can tell which form a shape reaches; both forms give a row the same bits */
+int pf_k_gemm_f32_block_rows(int32_t M, int32_t N);
 int pf_k_gemm_f32(const float* A, int32_t lda, const float* W, int32_t ldw, const float* bias, const float* R1,
                   int32_t ldr1, const float* R2, int32_t ldr2, float* C, int32_t ldc, int32_t M, int32_t N,
                   int32_t K, int32_t relu, void* stream);
