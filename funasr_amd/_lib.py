@@ -107,6 +107,11 @@ class pf_rwkvencoder_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("input_dim", "d_model", "linear_size", "n_blocks", "time_reduction")] + [("ln_eps", C.c_float)]
 
 
+class pf_qwen3_config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("vocab_size", "hidden_size", "intermediate_size", "n_layers", "n_heads", "n_kv_heads", "head_dim",
+                                          "tie_word_embeddings")] + [("rms_eps", C.c_float)]
+
+
 class pf_chunkconformer_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("input_dim", "d_model", "n_heads", "ffn_dim", "n_blocks", "kernel_size", "subsampling",
                                           "causal_conv", "left_chunk", "time_reduction")] + [("ln_eps", C.c_float), ("bn_eps", C.c_float)]
@@ -284,6 +289,25 @@ SIGNATURES = {
     "pf_rwkvencoder_forward": (C.c_int, [_vp, _vp, _pi32, _i32, _i32, _vp, _pi32, _vp]),
     "pf_rwkvencoder_forward_stages": (C.c_int, [_vp, _vp, _pi32, _i32, _i32, _vp, _pi32, C.POINTER(_vp), _vp]),
     "pf_rwkvencoder_debug_poison": (C.c_int, [_vp]),
+    "pf_qwen3_create": (_vp, [C.POINTER(pf_qwen3_config)]),
+    "pf_qwen3_destroy": (None, [_vp]),
+    "pf_qwen3_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),
+    "pf_qwen3_missing": (C.c_int, [_vp]),
+    "pf_qwen3_set_rope_table": (C.c_int, [_vp, _vp, _vp, _i32]),
+    "pf_qwen3_rope_positions": (_i32, [_vp]),
+    "pf_qwen3_embed": (C.c_int, [_vp, _vp, _i32, _vp, _vp]),
+    "pf_qwen3_prefill": (C.c_int, [_vp, _vp, _pi32, _i32, _i32, _pi32, _vp, _vp]),
+    "pf_qwen3_step": (C.c_int, [_vp, _pi32, _pi32, _vp, _vp]),
+    "pf_qwen3_generate": (C.c_int, [_vp, _i32, _pi32, _i32, _i32, _pi32, _pi32, _vp]),
+    "pf_qwen3_debug_poison": (C.c_int, [_vp]),
+    "pf_k_qwen3_tiles": (C.c_int, [_i32, _i32, _pi32, _pi32, _pi32]),
+    "pf_k_qwen3_rmsnorm": (C.c_int, [_vp, _i32, _vp, _f32, _vp, _i32, _i32, _i32, _vp]),
+    "pf_k_qwen3_qk_rope": (C.c_int, [_vp, _i32, _vp, _vp, _f32, _vp, _vp, _i32, _pi32, _pi32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32,
+                                     _i32, _i32, _vp]),
+    "pf_k_qwen3_prefill_attention": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _pi32, _pi32, _pi32, _pi32, _i32, _i32, _i32,
+                                               _i32, _f32, _vp]),
+    "pf_k_qwen3_decode_attention": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _pi32, _pi32, _i32, _i32, _i32, _i32, _f32, _vp]),
+    "pf_k_qwen3_swiglu": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _vp]),
     "pf_chunkconformer_create": (_vp, [C.POINTER(pf_chunkconformer_config)]),
     "pf_chunkconformer_destroy": (None, [_vp]),
     "pf_chunkconformer_set_tensor": (C.c_int, [_vp, C.c_char_p, _vp, _i64]),

@@ -49,6 +49,7 @@ from . import e_paraformer as _e_paraformer  # noqa: F401  (registers EParaforme
 from . import sanm as _sanm  # noqa: F401  (registers SANM / FsmnDecoder)
 from . import uniasr as _uniasr  # noqa: F401  (registers UniASR / FsmnDecoderSCAMAOpt)
 from . import lcbnet as _lcbnet  # noqa: F401  (registers LCBNet / TransformerTextEncoder / FusionSANEncoder / ConvBiasPredictor)
+from . import fun_asr_nano as _fun_asr_nano  # noqa: F401  (registers FunASRNano, the adaptor_classes, and through tokenizer.py HuggingfaceTokenizer)
 from . import transducer as _transducer  # noqa: F401  (registers Transducer / rnnt_decoder / joint_network)
 from . import chunk_conformer as _chunk_conformer  # noqa: F401  (registers ChunkConformerEncoder, the encoder of the reference's streaming / unified RNN-T recipes)
 from . import rwkv_encoder as _rwkv_encoder  # noqa: F401  (registers RWKVEncoder, the encoder of the reference's Transducer template)
@@ -198,6 +199,22 @@ def load_model_dir(model_dir: str) -> dict:
     if os.path.exists(bpe):
         kwargs.setdefault("tokenizer_conf", {})
         kwargs["tokenizer_conf"] = dict(kwargs["tokenizer_conf"] or {}, bpemodel=bpe)
+    # nested entries of file_path_metas that name an `init_param_path` (FunASRNano's llm_conf / tokenizer_conf: the LM's config and
+    # tokenizer sub-directory): the model directory is put in front when the result exists. add_file_root_path
+    # (download_model_from_hub.py:191-221) does that for EVERY nested string; only the key `init_param_path` is rooted here, which is
+    # all FunASRNano's directories need and leaves what the other models' directories resolve to as it was. Without configuration.json the path stays as config.yaml has it -- absolute, or relative to
+    # the working directory, which is how the reference hands it to transformers.
+    def root_init_param_paths(meta: dict, cfg: dict):
+        for k, v in meta.items():
+            if isinstance(v, dict):
+                sub = cfg.get(k) if isinstance(cfg.get(k), dict) else {}
+                root_init_param_paths(v, sub)
+                if sub:
+                    cfg[k] = sub
+            elif k == "init_param_path" and isinstance(v, str) and os.path.exists(os.path.join(model_dir, v)):
+                cfg[k] = os.path.join(model_dir, v)
+
+    root_init_param_paths({k: v for k, v in metas.items() if isinstance(v, dict)}, kwargs)
     kwargs["model_path"] = model_dir
     return kwargs
 

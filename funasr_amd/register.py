@@ -13,7 +13,7 @@ import logging
 TABLE_NAMES = ("model_classes", "frontend_classes", "specaug_classes", "normalize_classes", "encoder_classes",
                "decoder_classes", "joint_network_classes", "predictor_classes", "stride_conv_classes",
                "tokenizer_classes", "dataloader_classes", "batch_sampler_classes", "dataset_classes",
-               "index_ds_classes")
+               "index_ds_classes", "adaptor_classes")
 
 
 class RegisterTables:

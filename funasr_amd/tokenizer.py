@@ -233,3 +233,17 @@ class SentencepiecesTokenizer:
 
     def tokens2ids(self, *args, **kwargs):
         return self.encode(*args, **kwargs)
+
+
+@tables.register("tokenizer_classes", "HuggingfaceTokenizer")
+def HuggingfaceTokenizer(init_param_path, **kwargs):
+    """funasr/tokenizer/hf_tokenizer.py: the `transformers` tokenizer stored in the LOCAL directory `init_param_path` (host side, as in
+    the reference). No hub is ever contacted: anything that is not a directory on this machine is refused."""
+    try:
+        from transformers import AutoTokenizer
+    except Exception as e:
+        raise ImportError("HuggingfaceTokenizer requires the 'transformers' package") from e
+    import os
+    if not os.path.isdir(str(init_param_path)):
+        raise FileNotFoundError(f"HuggingfaceTokenizer: {init_param_path!r} is not a local directory (no hub is contacted)")
+    return AutoTokenizer.from_pretrained(str(init_param_path), local_files_only=True)

@@ -655,6 +655,86 @@ int pf_k_rwkv_wkv(const float* k_dev, const float* v_dev, const float* r_dev, in
                   const int32_t* lens_dev, int32_t B, int32_t T, int32_t D, float* out_dev, int32_t ldo, float* scratch_dev,
                   int64_t scratch_floats, void* stream);
 
+/* ---- Qwen3 causal LM decoder with a KV cache (the LM of funasr/models/fun_asr_nano/model.py FunASRNano; transformers'
+ * Qwen3ForCausalLM): per layer input_layernorm (RMSNorm) -> one fused q | k | v projection -> per-head q_norm / k_norm + rotary
+ * embedding, rotated K and plain V written into the cache -> causal grouped-query attention -> o_proj + residual ->
+ * post_attention_layernorm -> one fused gate | up projection -> SwiGLU -> down_proj + residual; then the final norm and the vocabulary
+ * projection with its arg-max. fp32 throughout, greedy search only, no biases (attention_bias = false). Tensor names are the
+ * upstream state-dict keys: "model.embed_tokens.weight", "model.layers.0.input_layernorm.weight",
+ * "model.layers.0.self_attn.q_proj.weight" (k_proj, v_proj, o_proj), "model.layers.0.self_attn.q_norm.weight" (k_norm),
+ * "model.layers.0.post_attention_layernorm.weight", "model.layers.0.mlp.gate_proj.weight" (up_proj, down_proj), "model.norm.weight"
+ * and, unless tie_word_embeddings, "lm_head.weight".
+ * KV cache: K and V each [layer][sequence][kv_head][position][head_dim], sized by pf_qwen3_prefill for the longest prompt plus
+ * max_new_tokens; a sequence's rows at or past its own length are never read. A batch is 1 .. 16 sequences, each at its own length (no
+ * padding rows anywhere): every kernel takes per-row (sequence, position), so a sequence computes what it computes alone up to the
+ * summation order of the GEMM tile its rows fall into.
+ * Prefill runs the tile GEMM, a decode step the small-M weight-streaming GEMM; one decode step is 10 launches per layer plus 5 around
+ * them, one of which is the read-back of the step's ids. */
+typedef struct pf_qwen3 pf_qwen3;
+typedef struct pf_qwen3_config {
+    int32_t vocab_size;
+    int32_t hidden_size;          /* a multiple of 32 */
+    int32_t intermediate_size;    /* a multiple of 32 */
+    int32_t n_layers;
+    int32_t n_heads;              /* num_attention_heads */
+    int32_t n_kv_heads;           /* divides n_heads */
+    int32_t head_dim;             /* 64 or 128 */
+    int32_t tie_word_embeddings;  /* != 0: the vocabulary projection reads model.embed_tokens.weight, lm_head.weight is no tensor */
+    float rms_eps;
+} pf_qwen3_config;
+pf_qwen3* pf_qwen3_create(const pf_qwen3_config* cfg);
+void pf_qwen3_destroy(pf_qwen3* h);
+int pf_qwen3_set_tensor(pf_qwen3* h, const char* name, const float* data, int64_t numel);
+int pf_qwen3_missing(const pf_qwen3* h);
+/* cos / sin of the rotary embedding, [positions, head_dim / 2] each (host or device memory; copied before the call returns). The
+ * caller computes them in float32 as upstream does; the library never evaluates a sine. A prefill or step that needs a position the
+ * table does not hold is refused. pf_qwen3_rope_positions: rows the table holds now. */
+int pf_qwen3_set_rope_table(pf_qwen3* h, const float* cos_t, const float* sin_t, int32_t positions);
+int32_t pf_qwen3_rope_positions(const pf_qwen3* h);
+/* out_dev [n, hidden_size] = model.embed_tokens.weight[ids_dev[i]] (ids clamped into the vocabulary). No sync. */
+int pf_qwen3_embed(pf_qwen3* h, const int32_t* ids_dev, int32_t n, float* out_dev, void* stream);
+/* Start B sequences: inputs_embeds_dev holds their rows back to back ([sum of rows_host, hidden_size], rows_host[b] >= 1), the cache is
+ * sized for max(rows_host) + max_new_tokens positions per sequence and every sequence's length becomes rows_host[b]. first_ids_host[b]
+ * = arg-max of the logits of sequence b's last row. logits_dev (tests; nullable): [sum of rows_host, vocab_size] logits of EVERY row.
+ * Synchronises. */
+int pf_qwen3_prefill(pf_qwen3* h, const float* inputs_embeds_dev, const int32_t* rows_host, int32_t B, int32_t max_new_tokens,
+                     int32_t* first_ids_host, float* logits_dev, void* stream);
+/* one decode step of every sequence of the last prefill: ids_host[b] is embedded, appended at position length[b], and next_ids_host[b]
+ * = arg-max of its logits. logits_dev (tests; nullable): [B, vocab_size]. Refused when a cache is full. Synchronises. */
+int pf_qwen3_step(pf_qwen3* h, const int32_t* ids_host, int32_t* next_ids_host, float* logits_dev, void* stream);
+/* greedy generation after pf_qwen3_prefill, the loop inside the library: column 0 of out_ids_host [B, max_new_tokens] is the prefill's
+ * first id; a sequence that has emitted one of eos_ids_host[0 .. n_eos) is finished, takes no further step and emits pad_id; the loop
+ * ends when every sequence is finished or after max_new_tokens columns (at most the max_new_tokens the prefill reserved). *n_out =
+ * columns written; the columns behind hold pad_id. One read-back of the step's ids per step; no HIP graph. */
+int pf_qwen3_generate(pf_qwen3* h, int32_t max_new_tokens, const int32_t* eos_ids_host, int32_t n_eos, int32_t pad_id,
+                      int32_t* out_ids_host, int32_t* n_out, void* stream);
+/* tests: fill the KV cache and every workspace buffer with 0xff bytes (NaN) */
+int pf_qwen3_debug_poison(pf_qwen3* h);
+/* single-kernel hooks (csrc/qwen3.h). Caches: K and V of ONE layer, each [slots, Hkv, cap, hd]. Every *_host array is checked against
+ * slots / cap / the table before the launch and copied to the device; each hook synchronises.
+ * pf_k_qwen3_tiles: query rows per workgroup of the prefill attention for G = Hq / Hkv, keys per LDS tile for hd, keys per workgroup of
+ * the decode attention. */
+int pf_k_qwen3_tiles(int32_t G, int32_t hd, int32_t* q_tile, int32_t* k_tile, int32_t* k_split);
+int pf_k_qwen3_rmsnorm(const float* x_dev, int32_t ldx, const float* w_dev, float eps, float* y_dev, int32_t ldy, int32_t M, int32_t D,
+                       void* stream);
+/* qkv_dev [M, (Hq + 2 Hkv) hd]; cos_dev / sin_dev [table_rows, hd / 2]; row r = position row_pos_host[r] of slot row_seq_host[r] */
+int pf_k_qwen3_qk_rope(const float* qkv_dev, int32_t ld, const float* qw_dev, const float* kw_dev, float eps, const float* cos_dev,
+                       const float* sin_dev, int32_t table_rows, const int32_t* row_seq_host, const int32_t* row_pos_host, float* q_out_dev,
+                       int32_t ldq, float* kcache_dev, float* vcache_dev, int32_t slots, int32_t cap, int32_t M, int32_t Hq, int32_t Hkv,
+                       int32_t hd, void* stream);
+/* sequence i: rows [row0_host[i], row0_host[i] + nrows_host[i]) of q_dev / out_dev [M, Hq hd] at positions p0_host[i] .. of slot
+ * seq_host[i]; row j attends to cache rows 0 .. p0 + j */
+int pf_k_qwen3_prefill_attention(const float* q_dev, int32_t ldq, const float* kcache_dev, const float* vcache_dev, int32_t slots,
+                                 int32_t cap, float* out_dev, int32_t ldo, int32_t M, const int32_t* seq_host, const int32_t* row0_host,
+                                 const int32_t* nrows_host, const int32_t* p0_host, int32_t nseq, int32_t Hq, int32_t Hkv, int32_t hd,
+                                 float scale, void* stream);
+/* row r of q_dev / out_dev [M, Hq hd] attends to rows 0 .. row_len_host[r] - 1 of slot row_seq_host[r] */
+int pf_k_qwen3_decode_attention(const float* q_dev, int32_t ldq, const float* kcache_dev, const float* vcache_dev, int32_t slots,
+                                int32_t cap, float* out_dev, int32_t ldo, const int32_t* row_seq_host, const int32_t* row_len_host, int32_t M,
+                                int32_t Hq, int32_t Hkv, int32_t hd, float scale, void* stream);
+/* out_dev [M, I] = silu(gu_dev[:, 0 .. I)) * gu_dev[:, I .. 2 I) */
+int pf_k_qwen3_swiglu(const float* gu_dev, int32_t ld, float* out_dev, int32_t ldo, int32_t M, int32_t I, void* stream);
+
 /* ---- Chunk Conformer encoder (funasr/models/conformer/encoder.py ConformerChunkEncoder, registered as ChunkConformerEncoder: the
  * StreamingConvInput front at 1/2, 1/4 or 1/6 subsampling (vgg_like = False), blocks of macaron feed-forward, chunk-masked
  * relative-position self-attention (head dim 64), the convolution module (causal or symmetric), feed-forward and norm_final, then
